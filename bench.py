@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Both forms work for N > 1: typed plainly, this process starts the N ranks itself (one fresh process per GPU, RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1 rendezvous), never touches the GPU, relays rank 0's line and exits
@@ -16,9 +16,18 @@ segments and block tables are concatenated on every rank (rcx_allgatherv_segment
 over xGMI) while the decode runs.  `config.workload` says which BASELINE.json config the line is.
 
 Prints ONE JSON line on rank 0.  `value` = uncompressed MB/s through the whole round trip
-(all ranks' bytes / max-over-ranks time).  `roofline` prices the dominant kernel against the
-HBM roof (this is integer/byte work, no MFMA); `cpu_baseline` times the reference's own CPU
-coder (oracle/_ref, or the oracle port when that build did not travel) on this box's cores.
+(all ranks' bytes / max-over-ranks time), `ms_per_step` the mean time of one of the K timed steps.
+`roofline` prices the dominant kernel against the HBM roof (this is integer/byte work, no MFMA).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the measurements
+that take runs of their own, after the timed steps: `cpu_baseline` times the reference's own CPU
+coder (oracle/_ref, or the oracle port where that build is absent) on the host's cores, and
+`end_to_end` the host-buffer (PCIe-inclusive) calls.
+
+--dump-outputs DIR writes what the last timed step handed its caller, on rank 0, as float32 / float64
+.npy files: offsets.npy (the block table, offsets[nblocks + 1]), compressed.npy (the compacted
+stream's bytes) and decoded.npy (the decoder's output bytes), each whole or, past its budget (64 MB
+in all), a fixed seeded sample of 4 KiB windows (dump_outputs).
 """
 from __future__ import annotations
 
@@ -236,6 +245,32 @@ def end_to_end(ctx, host_src: np.ndarray, block: int, coder: int):
     }
 
 
+DUMP_SEED = 2024  # the sample positions of --dump-outputs: the same for the same arguments, run after run
+DUMP_WINDOW = 4096
+
+
+def _dump_sample(t, budget: int, seed: int):
+    """t (1-D) itself if it has at most `budget` elements, else budget // DUMP_WINDOW windows of DUMP_WINDOW
+    consecutive elements at sorted positions drawn from np.random.default_rng(seed) (windows may overlap)."""
+    import torch
+    n = t.numel()
+    if n <= budget:
+        return t
+    starts = np.sort(np.random.default_rng(seed).integers(0, n - DUMP_WINDOW + 1, size=budget // DUMP_WINDOW))
+    idx = torch.from_numpy(starts).to(t.device)[:, None] + torch.arange(DUMP_WINDOW, device=t.device)
+    return t[idx.reshape(-1)]
+
+
+def dump_outputs(dirname: str, offsets, compressed, decoded) -> None:
+    """--dump-outputs: the block table (int64 -> float64, exact below 2^53), the compacted stream and the decoded bytes
+    (u8 -> float32), whole or sampled: 1 Mi + 8 Mi + 4 Mi elements at most, 58.7 MB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t, budget, dtype, seed in (("offsets", offsets, 1 << 20, np.float64, DUMP_SEED),
+                                         ("compressed", compressed, 8 << 20, np.float32, DUMP_SEED + 1),
+                                         ("decoded", decoded, 4 << 20, np.float32, DUMP_SEED + 2)):
+        np.save(os.path.join(dirname, name + ".npy"), _dump_sample(t.reshape(-1), budget, seed).cpu().numpy().astype(dtype))
+
+
 # The contract is ONE line on stdout.  RCCL prints a version banner to stdout when a communicator is created
 # (and other libraries may chat as well): everything written to file descriptor 1 during the run goes to stderr,
 # and the JSON line is written to the real stdout at the end.
@@ -271,7 +306,13 @@ def main() -> None:
                     help="rehearse the launcher without a GPU: every rank prints the environment it was started with and exits")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds the self-started ranks get before they are stopped")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline that take runs of their own: cpu_baseline and end_to_end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (block table, compressed stream, decoded bytes) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_launch):
         # typed plainly: this process only starts the ranks (it has imported nothing that initialises HIP)
@@ -484,7 +525,9 @@ def main() -> None:
             line["codec_only_MBps"] = round(world * n / 1e6 / (codec_ms * 1e-3), 1)
             line["codec_plus_allgatherv_MBps"] = line["value"]
             line["allgatherv_in_GBps_per_gpu"] = round((world - 1) * total / 1e9 / (ag_ms * 1e-3), 2) if world > 1 else 0.0
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, offs, comp[:total], out)
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 sample = host_src[: min(n, args.cpu_sample_mib << 20) // block * block or n]
                 if args.blksort:  # the transform costs the CPU ~ 5 ms a block: a smaller sample (whole 32 KiB blocks)
@@ -499,7 +542,7 @@ def main() -> None:
                 line["cpu_baseline"]["block_sizes_equal_gpu"] = bool(np.array_equal(gpu_sizes, cpu_sizes[:k].astype(np.int64)))
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
                 line["cpu_baseline"] = {"value": None, "unit": "MB/s", "cores": usable_cpus(), "kind": "port", "sample": f"failed: {e}"}
-        if world == 1 and not args.no_end_to_end and not args.blksort:
+        if world == 1 and args.full and not args.no_end_to_end and not args.blksort:
             try:
                 line["end_to_end"] = end_to_end(ctx, host_src, block, coder)
             except Exception as e:  # a report beside the number, never a reason to lose it

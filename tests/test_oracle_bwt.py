@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import agreement_cases
 import bwt_cases
 from cpprcoder_amd import workloads
 
@@ -79,11 +80,8 @@ def test_inverse_takes_any_row_of_a_tie(oracle):
 
 
 def test_reference_build_agrees(reference, oracle, inputs):
-    if reference is None or reference.bwt is None:
-        pytest.skip("oracle/_ref/libblksort_ref.so not present")
-    for name in ("random 2 blocks + tail", "four letters", "repeat of 5000", "period 16384 (seed 19, 256 symbols)",
-                 "three blocks: periodic, random, zeros"):
-        data = inputs[name]
-        a, b = reference.bwt_encode(data, threads=4), oracle.bwt_encode(data, threads=4)
-        assert np.array_equal(a, b), name
-        assert np.array_equal(reference.bwt_decode(a), oracle.bwt_decode(a)), name
+    """BlkSort::encode / decode on agreement_cases.BWT_NAMES: the oracle's output is the reference build's, stored in
+    tests/golden/reference_agreement.json, and the build itself where oracle/_ref/libblksort_ref.so is present."""
+    live = reference is not None and reference.bwt is not None
+    agreement_cases.agree(agreement_cases.stored("bwt"), agreement_cases.bwt(oracle, inputs),
+                          agreement_cases.bwt(reference, inputs) if live else None)

@@ -9,6 +9,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import agreement_cases
 import oracle_lib
 from cpprcoder_amd import workloads
 
@@ -159,33 +160,10 @@ def test_chunked_equals_oneshot(oracle):
 
 
 def test_against_reference_build(oracle, reference):
-    if reference is None:
-        pytest.skip("oracle/_ref not built here (needs /root/reference)")
-    rs = np.random.RandomState(2024)
-    cases = [workloads.uniform(5000, 1), workloads.zipf(70000, 2), workloads.runs(150000, 3), workloads.canterbury_tiled(100000)[7:],
-             np.zeros(1, np.uint8), np.full(300000, 255, np.uint8)]
-    for _ in range(40):
-        n = int(rs.randint(0, 3000))
-        alpha = int(rs.randint(1, 257))
-        cases.append(rs.randint(0, alpha, size=n).astype(np.uint8))
-    for v in cases:
-        assert oracle.adaptive_encode(v) == reference.adaptive_encode(v)
-        assert oracle.static_encode(v) == reference.static_encode(v)
-        comp = oracle.adaptive_encode(v)[1]
-        assert oracle.adaptive_decode(comp, max(len(v), 1)) == reference.adaptive_decode(comp, max(len(v), 1))
-        for cap in (len(comp) // 2, 16):
-            assert oracle.adaptive_encode(v, sink_capacity=cap) == reference.adaptive_encode(v, sink_capacity=cap)
-        for piece in (0, 333):
-            assert oracle.adaptive_encode_chunked(v, piece) == reference.adaptive_encode_chunked(v, piece)
-        # corrupt / random streams must decode to the same bytes and status too
-        junk = rs.randint(0, 256, size=max(len(comp), 12)).astype(np.uint8)
-        junk[:4] = np.frombuffer(np.uint32(min(len(v), 500)).tobytes(), np.uint8)
-        assert oracle.adaptive_decode(junk, 600) == reference.adaptive_decode(junk, 600)
-    data = workloads.zipf(1 << 20, 9)
-    for block in (4096, 65536):
-        so, zo = oracle.encode_blocks(data, block, threads=4)
-        sr, zr = reference.encode_blocks(data, block, threads=4)
-        assert np.array_equal(zo, zr) and np.array_equal(so, sr)
+    """The range coders' results on agreement_cases.adaptive are the reference build's: stored in
+    tests/golden/reference_agreement.json, and the build itself where oracle/_ref is present."""
+    agreement_cases.agree(agreement_cases.stored("adaptive"), agreement_cases.adaptive(oracle),
+                          agreement_cases.adaptive(reference) if reference is not None else None)
 
 
 def long_inputs():

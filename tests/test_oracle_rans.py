@@ -4,8 +4,8 @@ oracle/_ref/libcppans_ref.so is present.  The reference publishes no rANS number
 import hashlib
 
 import numpy as np
-import pytest
 
+import agreement_cases
 import oracle_lib
 from cpprcoder_amd import workloads
 
@@ -82,18 +82,7 @@ def test_rans_damaged_streams_are_refused(oracle):
 
 
 def test_rans_against_reference_build(oracle, reference):
-    if reference is None or reference.ans is None:
-        pytest.skip("oracle/_ref/libcppans_ref.so not built here (needs /root/reference)")
-    rs = np.random.RandomState(77)
-    cases = [workloads.uniform(5000, 1), workloads.zipf(70000, 2), workloads.runs(150000, 3), workloads.canterbury_tiled(100000)[7:],
-             np.zeros(1, np.uint8), np.full(30000, 255, np.uint8)]
-    for _ in range(120):
-        n = int(rs.randint(1, 3000))
-        cases.append(rs.randint(0, int(rs.randint(1, 257)), size=n).astype(np.uint8))
-    for n in range(1, 24):  # fewer symbols than states
-        cases.append(rs.randint(0, 256, size=n).astype(np.uint8))
-    for v in cases:
-        for simd in (False, True):
-            a, b = oracle.rans_encode(v, simd), reference.rans_encode(v, simd)
-            assert a == b, (len(v), simd)
-            assert oracle.rans_decode(a, len(v), simd) == reference.rans_decode(a, len(v), simd) == (True, v.tobytes())
+    """The rANS coders' streams and round trips on agreement_cases.rans are the reference build's: stored in
+    tests/golden/reference_agreement.json, and the build itself where oracle/_ref/libcppans_ref.so is present."""
+    live = reference is not None and reference.ans is not None
+    agreement_cases.agree(agreement_cases.stored("rans"), agreement_cases.rans(oracle), agreement_cases.rans(reference) if live else None)
