@@ -75,6 +75,7 @@ struct rcx_ctx {
     bool bwt_lds_set = false;   // the block-sort kernels have been allowed their dynamic LDS
     bool bwt_atomic = false;    // their counting passes rank with ds_add_rtn_u32 (checked on this device) instead of ballots
     DivEntry* divtab = nullptr;
+    u32* divq = nullptr;        // the same entries as the quad decoder reads them (rcx_oct.hpp, RCX_QUAD_DIVQ_DW), behind divtab
     u32 divtab_block = 0;
     u32* status = nullptr;      // device: [flags, first bad block, track0, track1]
     u32* status_host = nullptr; // pinned, same 4 words
@@ -134,11 +135,18 @@ int grow(void** p, u64* have, u64 want)
     return RCX_OK;
 }
 
-// Entry i serves total = 256 + i (rcx_divtab.hpp); built on the device, 16 bytes per symbol of the largest block.
-__global__ void rcx_divtab_k(DivEntry* __restrict__ tab, u64 entries)
+// Entry i serves total = 256 + i (rcx_divtab.hpp); built on the device, 16 bytes per symbol of the largest block, and
+// 8 more for the quad decoder's copy: multiplier and increment (the addend is 0 or the multiplier), 16 entries a group.
+__global__ void rcx_divtab_k(DivEntry* __restrict__ tab, u32* __restrict__ divq, u64 entries)
 {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < entries) tab[i] = rcx_make_div_entry((u32)(256 + i));
+    if (i < entries) {
+        const DivEntry e = rcx_make_div_entry((u32)(256 + i));
+        tab[i] = e;
+        u32* g = divq + (i >> 4) * RCX_QUAD_DIVQ_DW + (i & 15u);
+        g[0] = e.mul;
+        g[16] = e.add == 0 ? 0u : 1u;
+    }
 }
 
 int ensure_divtab(rcx_ctx* c, u32 block)
@@ -147,12 +155,14 @@ int ensure_divtab(rcx_ctx* c, u32 block)
     // round up so that a sweep of block sizes builds the table once or twice
     u32 cover = 1u << 16;
     while (cover < block) cover <<= 1;
-    const u64 entries = (u64)cover + 2 * RCX_STAGE;
+    const u64 entries = (u64)cover + 2 * RCX_STAGE; // a multiple of 16
     if (c->divtab) (void)hipFree(c->divtab);
     c->divtab = nullptr;
+    c->divq = nullptr;
     c->divtab_block = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&c->divtab), entries * sizeof(DivEntry)) != hipSuccess) return RCX_E_NOMEM;
-    hipLaunchKernelGGL(rcx_divtab_k, dim3((u32)((entries + 255) / 256)), dim3(256), 0, nullptr, c->divtab, entries);
+    if (hipMalloc(reinterpret_cast<void**>(&c->divtab), entries * (sizeof(DivEntry) + 2 * sizeof(u32))) != hipSuccess) return RCX_E_NOMEM;
+    c->divq = reinterpret_cast<u32*>(c->divtab + entries);
+    hipLaunchKernelGGL(rcx_divtab_k, dim3((u32)((entries + 255) / 256)), dim3(256), 0, nullptr, c->divtab, c->divq, entries);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return RCX_E_HIP;
     c->divtab_block = cover;
     return RCX_OK;
@@ -613,12 +623,12 @@ int decode_range(rcx_ctx* c, int coder, const void* d_comp, u64 comp_size, const
                 const u64 per_wg = (u64)quads * RCX_QUAD_DEC_WAVES;
                 const u32 grid = (u32)((nblocks + per_wg - 1) / per_wg);
                 hipLaunchKernelGGL(rcx_dec_quad_k<RCX_QUAD_DEC_WAVES>, dim3(grid), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
-                                   static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks, block, n, static_cast<u8*>(d_dst), c->divtab,
+                                   static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks, block, n, static_cast<u8*>(d_dst), c->divq,
                                    c->status, redo, quads);
             } else {
                 const u32 grid = (u32)((nblocks + quads - 1) / quads);
                 hipLaunchKernelGGL(rcx_dec_quad_k<1>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
-                                   block, n, static_cast<u8*>(d_dst), c->divtab, c->status, redo, quads);
+                                   block, n, static_cast<u8*>(d_dst), c->divq, c->status, redo, quads);
             }
 #if defined(RCX_WITH_VARIANTS)
         } else if (decode_lanes(c, nblocks) == 8) {
@@ -1073,7 +1083,7 @@ int rcx_stream_decode(rcx_ctx* c, int coder, const uint8_t* comp, uint64_t comp_
         // cpprcoder.h:901-903; a target past the table) it reports, and the exact one-lane decoder below redoes it.
         if ((r = ensure_redo(c, 1)) != RCX_OK) return r;
         hipLaunchKernelGGL(rcx_dec_quad_k<RCX_QUAD_DEC_WAVES>, dim3(1), dim3(64 * RCX_QUAD_DEC_WAVES), 0, nullptr, c->h_in, (u64)comp_size, c->h_off,
-                           (u64)1, block, count, c->h_out, c->divtab, c->status, c->redo, 1u);
+                           (u64)1, block, count, c->h_out, c->divq, c->status, c->redo, 1u);
         if (hipGetLastError() != hipSuccess) return RCX_E_HIP;
         u32 marked = 0;
         const int fast = rcx_ctx_sync_status(c, nullptr, nullptr); // (clears the latch)
