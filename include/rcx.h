@@ -128,6 +128,29 @@ int rcx_encode_blocks_device(rcx_ctx* ctx, int coder, const void* d_src, uint64_
  *   d_offsets  nblocks+1 u64 as written by the encoder
  *   n          total decoded size; block b must declare min(block, n - b*block) bytes
  *   d_dst      n output bytes
+ *
+ * What the device calls write and read (pointers of any alignment):
+ *   - encode writes exactly [d_dst, d_dst + offsets[nblocks]) and d_offsets[0 .. nblocks], and nothing else; it reads
+ *     [d_src, d_src + n) and nothing past it.  If the streams do not fit dst_cap the call latches RCX_E_CAPACITY and
+ *     writes nothing from d_dst + dst_cap on.
+ *   - decode writes exactly [d_dst, d_dst + n), and neither d_comp nor d_offsets.  It may read up to 15 bytes past
+ *     comp_size -- within the 16-byte aligned piece that holds the stream's last byte (QuadInput::load16) -- and its
+ *     result never depends on them.
+ *   - Calls on distinct buffers may run at the same time from two contexts, even into adjacent bytes of one allocation.
+ * Damaged streams, per block, as the reference decodes the block's stream on its own:
+ *   - adaptive and rANS: if the reference decodes all the block's symbols (a damaged payload still decodes to some bytes,
+ *     including find()'s fall-through for a target at or past the total, cpprcoder.h:1220-1242), the block gets exactly
+ *     those bytes;
+ *   - static: likewise.  find() never fails (cpprcoder.h:521-535): a target at or past the total falls through to symbol
+ *     255 and decoding goes on, and the block gets the reference's bytes.  Only a decoded symbol of count 0 -- such a
+ *     target landing on a trailing symbol of count 0 -- makes the range 0, and the reference can only end that by
+ *     running dry (:506-513): the call latches RCX_E_CORRUPT;
+ *   - a stream that runs out of input before its last symbol (truncated, or a damaged payload that asks for more bytes
+ *     than the stream has), or whose header disagrees with the layout, latches RCX_E_CORRUPT; the bytes of such a block
+ *     are unspecified.  A stream cut only by bytes the reference never reads still decodes completely and gets the
+ *     reference's bytes (the adaptive decoder need not read the last byte the encoder flushes).
+ *   rcx_ctx_sync_status() then reports the lowest failing block, and every other block of the call is decoded as if it
+ *   were alone (tests/test_gpu_damaged.py; the single-stream calls below follow the same rule with their own statuses).
  */
 int rcx_decode_blocks_device(rcx_ctx* ctx, int coder, const void* d_comp, uint64_t comp_size,
                              const uint64_t* d_offsets, uint64_t nblocks, uint32_t block,

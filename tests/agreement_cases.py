@@ -17,7 +17,7 @@ STORED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref
 
 
 def stored(part: str) -> dict:
-    """The reference build's digests of one check ("adaptive", "rans" or "bwt"), key -> digest."""
+    """The reference build's digests of one check ("adaptive", "rans", "bwt" or "damaged"), key -> digest."""
     with open(STORED) as f:
         return json.load(f)[part]
 
@@ -108,3 +108,41 @@ def bwt(chk, inputs):
         enc = chk.bwt_encode(inputs[name], threads=4)
         yield f"{name}/encode", (enc.tobytes(),)
         yield f"{name}/decode", (chk.bwt_decode(enc).tobytes(),)
+
+
+def damaged(chk):
+    """Damaged streams the reference decodes without running dry (a RandomState of its own, so that the other checks' keys
+    and digests stay as they are): the static coder's payload flips and count edits that keep the total nonzero
+    (cpprcoder.h:460-535), and the rANS coders' payload flips with the table intact (cppans.h:532-564, :609-649).  Every
+    stream is followed by random bytes, so that no decoder reads past its input.  Left out, as the reference leaves them
+    undefined: a zero total, a bad rANS table, a payload that runs dry."""
+    rs = np.random.RandomState(31337)
+    cases = [workloads.uniform(5000, 21), workloads.zipf(40000, 22), workloads.canterbury_tiled(30000)[3:], workloads.runs(20000, 23)]
+    for _ in range(12):
+        n = int(rs.randint(1, 4000))
+        cases.append(rs.randint(0, int(rs.randint(2, 257)), size=n).astype(np.uint8))
+    for i, v in enumerate(cases):
+        pad = rs.randint(0, 256, size=len(v) + 2048).astype(np.uint8)
+        comp = np.frombuffer(chk.static_encode(v)[1], np.uint8)
+        for kind in ("flips", "count to 0", "count moved"):
+            s = np.concatenate([comp, pad])
+            if kind == "flips":
+                for _ in range(1 + i % 3):
+                    s[int(rs.randint(517, max(len(comp), 518)))] ^= int(rs.randint(1, 256))
+            else:
+                counts = s[4:516].view("<u2").copy()
+                used = np.nonzero(counts)[0]
+                if len(used) < 2:
+                    continue
+                a, b = (int(x) for x in rs.choice(used, 2, replace=False))
+                if kind == "count moved":
+                    counts[b] = min(int(counts[b]) + int(counts[a]), 0xFFFF)
+                counts[a] = 0
+                s[4:516] = counts.view(np.uint8)
+            yield f"{i}/static_decode {kind}", chk.static_decode(s, max(len(v), 1))
+        for simd in (False, True):
+            comp = np.frombuffer(chk.rans_encode(v, simd), np.uint8)
+            s = np.concatenate([comp, pad])
+            for _ in range(1 + i % 4):
+                s[int(rs.randint(1032 + 4, max(len(comp), 1032 + 5)))] ^= int(rs.randint(1, 256))
+            yield f"{i}/simd={simd}/decode flips", chk.rans_decode(s, len(v), simd)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate tests/golden/reference_agreement.json from the REAL reference build: a digest of every result of the checks in
-tests/agreement_cases.py (range coders, rANS, block sort), so that the tests that compare the oracle with the reference
+tests/agreement_cases.py (range coders, rANS, block sort, damaged streams), so that the tests that compare the oracle with the reference
 build run where oracle/_ref/ is not present too.  Runs only where oracle/_ref/ was built (`make -C oracle ref`, see
 make_golden.py).  Outputs are data: digests of the reference's outputs.
 
@@ -29,8 +29,9 @@ def main() -> None:
            "source": "oracle/_ref/ (the unmodified reference headers compiled by `make -C oracle ref`)",
            "adaptive": {k: agreement_cases.digest(r) for k, r in agreement_cases.adaptive(ref)},
            "rans": {k: agreement_cases.digest(r) for k, r in agreement_cases.rans(ref)},
-           "bwt": {k: agreement_cases.digest(r) for k, r in agreement_cases.bwt(ref, bwt_cases.cases())}}
-    for part in ("adaptive", "rans", "bwt"):
+           "bwt": {k: agreement_cases.digest(r) for k, r in agreement_cases.bwt(ref, bwt_cases.cases())},
+           "damaged": {k: agreement_cases.digest(r) for k, r in agreement_cases.damaged(ref)}}
+    for part in ("adaptive", "rans", "bwt", "damaged"):
         print(part, len(out[part]), "results", flush=True)
     with open(os.path.join(HERE, "reference_agreement.json"), "w") as f:
         json.dump(out, f, indent=1)

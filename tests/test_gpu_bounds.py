@@ -1,0 +1,234 @@
+"""Buffer bounds of the device calls, all four coders (include/rcx.h: what the device calls write and read).
+
+Every buffer is a view into a larger tensor with guard bytes on both sides (test_gpu_parity.Guarded).  Encode writes
+exactly [dst, dst + offsets[nblocks]) and offsets[0 .. nblocks]; decode writes exactly [dst, dst + n); neither writes
+its input, and neither result depends on the bytes behind src + n or comp_size.  The cases reach every residue of the
+three pointers modulo 16, block sizes that are and are not multiples of 16 and 64, and last blocks whose length is 1, 15,
+16, 17, 63, 64 or 65 plus a multiple of 64 (residues 1, 15, 16, 17, 63 and 0 modulo 64) -- the aligned fast loops, the
+unaligned and symbol-by-symbol tail paths and the rANS decoders' word alignment.
+"""
+import numpy as np
+import pytest
+
+from cpprcoder_amd import rcx, workloads
+from test_gpu_parity import GUARD, Guarded, gpu_decode, gpu_encode
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+CODERS = (rcx.CODER_ADAPTIVE, rcx.CODER_STATIC, rcx.CODER_RANS, rcx.CODER_RANS8)
+LASTS = (1, 15, 16, 17, 63, 64, 65)  # the last block's length, plus a multiple of 64 (65: residue 1 with a whole 64 in front)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    c = rcx.Context(0)
+    yield c
+    c.close()
+
+
+def alignments():
+    """(src, comp, dst) offsets: each residue 0..15 of one with the others at 0, and some mixed triples."""
+    out = [(r, 0, 0) for r in range(16)] + [(0, r, 0) for r in range(1, 16)] + [(0, 0, r) for r in range(1, 16)]
+    return out + [(3, 7, 11), (15, 1, 9), (8, 13, 5), (1, 1, 1), (9, 15, 15)]
+
+
+def make_input(block, i, seed):
+    last = LASTS[i % len(LASTS)] + 64 * (i % 3) * 4  # 1 .. 577 + 64: below the smallest block size here (1000)
+    wl = ("zipf", "uniform", "canterbury")[i % 3]
+    return workloads.by_name(wl, 2 * block + last, seed)
+
+
+@pytest.mark.parametrize("block", [4096, 4112, 1000])
+@pytest.mark.parametrize("coder", CODERS)
+def test_alignment_sweep(ctx, oracle, coder, block):
+    cache = {}
+    for i, (s, c, d) in enumerate(alignments()):
+        key = i % (3 * len(LASTS))
+        if key not in cache:
+            data = make_input(block, key, 1000 * coder + block + key)
+            cache[key] = (data,) + oracle.compact(*oracle.encode_blocks(data, block, coder=coder, threads=4))
+        data, want_p, want_o = cache[key]
+        payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=s, coder=coder, dst_offset=c)
+        assert np.array_equal(offsets, want_o) and np.array_equal(payload, want_p), (coder, block, s, c, d, len(data))
+        back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block, dst_offset=d, comp_offset=c, coder=coder)
+        assert st == rcx.OK and np.array_equal(back, data), (coder, block, s, c, d, len(data))
+
+
+def damaged_padded(oracle, data, block, coder, seed):
+    """Oracle streams of `data` whose middle block has two flipped payload bytes and is followed by random bytes, so
+    that the oracle decodes it completely -> (payload, offsets, what the oracle decodes)."""
+    slots, sizes = oracle.encode_blocks(data, block, coder=coder, threads=4)
+    rs = np.random.RandomState(seed)
+    pad = 2 * block + 64
+    big = np.zeros((len(sizes), slots.shape[1] + pad), np.uint8)
+    big[:, : slots.shape[1]] = slots
+    b = len(sizes) // 2
+    z = int(sizes[b])
+    head = {0: 9, 1: 520, 2: 1032, 3: 1032 + 16}[coder]
+    for at in (head + (z - head) // 3, head + 2 * (z - head) // 3):
+        big[b, at] ^= 0x5A
+    big[b, z: z + pad] = rs.randint(0, 256, pad)
+    sizes = sizes.copy()
+    sizes[b] = z + pad
+    want, ok = oracle.decode_blocks(big, sizes, block, len(data), coder=coder, threads=4)
+    assert ok, "the oracle should decode the padded stream completely"
+    return oracle.compact(big, sizes) + (want,)
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_results_do_not_depend_on_the_bytes_behind_the_inputs(ctx, oracle, coder):
+    """The same encode and decode with the guard pattern behind src + n and comp_size, and with its complement."""
+    block = 1000
+    data = workloads.zipf(7 * block + 333, 40 + coder)
+    runs = []
+    for invert in (False, True):
+        payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=5, coder=coder, dst_offset=3, invert=invert)
+        back, st, bad = gpu_decode(ctx, payload, offsets, len(data), block, dst_offset=7, comp_offset=3, coder=coder, invert=invert)
+        runs.append((payload, offsets, back, st, bad))
+    (p0, o0, b0, s0, _), (p1, o1, b1, s1, _) = runs
+    assert np.array_equal(p0, p1) and np.array_equal(o0, o1) and np.array_equal(b0, b1) and s0 == s1 == rcx.OK
+    assert np.array_equal(b0, data)
+    # a damaged stream (decoded in full by the oracle) likewise
+    payload, offsets, want = damaged_padded(oracle, data, block, coder, 7 + coder)
+    got = [gpu_decode(ctx, payload, offsets, len(data), block, dst_offset=1, comp_offset=15, coder=coder, invert=inv) for inv in (False, True)]
+    assert got[0][1] == got[1][1] == rcx.OK and np.array_equal(got[0][0], got[1][0])
+    assert np.array_equal(got[0][0], want)
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_capacity_refusal_writes_nothing_past_dst_cap(ctx, oracle, coder):
+    block = 4096
+    data = workloads.by_name("canterbury", 9 * block + 77, 3)
+    _, want_o = oracle.compact(*oracle.encode_blocks(data, block, coder=coder, threads=4))
+    total = int(want_o[-1])
+    nblocks = len(want_o) - 1
+    for k in (1, 16, 100):
+        src = Guarded(len(data), 3, data, salt=1)
+        dst = Guarded(total - k, 5, salt=2)
+        offs = Guarded(8 * (nblocks + 1), 0, salt=3)
+        ctx.encode_blocks_device(src.view, block, dst.view, offs.view.view(torch.int64), coder=coder)
+        st, _ = ctx.sync_status(raise_on_error=False)
+        assert st == rcx.E_CAPACITY, (coder, k, st)
+        src.check(0, "src")
+        offs.check(8 * (nblocks + 1), "offsets")
+        dst.check(total - k, "dst")
+
+
+def two_inputs(oracle, coder):
+    block = 4096
+    a = workloads.zipf(5 * block + 1001, 11)
+    b = workloads.by_name("canterbury", 3 * block + 17, 12)
+    return block, [(d,) + oracle.compact(*oracle.encode_blocks(d, block, coder=coder, threads=4)) for d in (a, b)]
+
+
+def run_pair(ctxs, calls, order):
+    """calls[i](ctx, stream) enqueues call i; order: (0, 1), (1, 0) or "both" (two contexts, two side streams at once)."""
+    if order == "both":
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        for s in streams:
+            s.wait_stream(torch.cuda.current_stream())
+        for i in (0, 1):
+            calls[i](ctxs[i], streams[i])
+        sts = [ctxs[i].sync_status(stream=streams[i], raise_on_error=False)[0] for i in (0, 1)]
+        for s in streams:
+            torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+    else:
+        sts = [None, None]
+        for i in order:
+            calls[i](ctxs[0], None)
+            sts[i] = ctxs[0].sync_status(raise_on_error=False)[0]
+    return sts
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_adjacent_slices_of_one_tensor(ctx, oracle, coder):
+    """Two decodes into adjacent slices of one output tensor, and two encodes into adjacent slices of one payload tensor,
+    the boundary 16-aligned but not 64-aligned or at an odd address: one after the other in both orders, and at the same
+    time from two contexts on two streams."""
+    block, ins = two_inputs(oracle, coder)
+    (da, pa, oa), (db, pb, ob) = ins
+    other = rcx.Context(0)
+    try:
+        ta, tb = int(oa[-1]), int(ob[-1])
+        for odd in (False, True):
+            # where the first slice starts, so that the boundary between the slices lands at 48 mod 64, or at an odd address
+            # (tensors start 256-aligned)
+            lead = (1 - len(da) % 2) if odd else (48 - GUARD - len(da)) % 64
+            lead_e = (1 - ta % 2) if odd else (48 - GUARD - ta) % 64
+            for order in ((0, 1), (1, 0), "both"):
+                # decode
+                out = Guarded(len(da) + len(db), lead, salt=6)
+                comps = [(Guarded(len(p), 0, p, salt=4), Guarded(8 * len(o), 0, o.astype(np.int64).view(np.uint8), salt=5)) for p, o in ((pa, oa), (pb, ob))]
+                views = (out.view[: len(da)], out.view[len(da):])
+                ns = (len(da), len(db))
+                calls = [lambda c, s, i=i: c.decode_blocks_device(comps[i][0].view, comps[i][0].size, comps[i][1].view.view(torch.int64), ns[i],
+                                                                  block, views[i], coder=coder, stream=s) for i in (0, 1)]
+                assert run_pair((ctx, other), calls, order) == [rcx.OK, rcx.OK], (odd, order)
+                assert (out.at + len(da)) % 2 == 1 if odd else (out.at + len(da)) % 64 == 48
+                got = out.view.cpu().numpy()
+                assert np.array_equal(got[: len(da)], da) and np.array_equal(got[len(da):], db), (coder, odd, order)
+                out.check(len(da) + len(db), "the two outputs")
+                for comp, table in comps:
+                    comp.check(0, "comp")
+                    table.check(0, "offsets")
+                # encode: the first call's dst_cap is exactly its total, so the second call's streams begin right behind
+                dst = Guarded(ta + tb, lead_e, salt=2)
+                srcs = [Guarded(len(d), 1, d, salt=1) for d in (da, db)]
+                tabs = [Guarded(8 * len(o), 0, salt=3) for o in (oa, ob)]
+                dviews = (dst.view[:ta], dst.view[ta:])
+                calls = [lambda c, s, i=i: c.encode_blocks_device(srcs[i].view, block, dviews[i], tabs[i].view.view(torch.int64), coder=coder,
+                                                                  stream=s) for i in (0, 1)]
+                assert run_pair((ctx, other), calls, order) == [rcx.OK, rcx.OK], (odd, order)
+                assert (dst.at + ta) % 2 == 1 if odd else (dst.at + ta) % 64 == 48
+                got = dst.view.cpu().numpy()
+                assert np.array_equal(got[:ta], pa) and np.array_equal(got[ta:], pb), (coder, odd, order)
+                dst.check(ta + tb, "the two payloads")
+                for i, o in enumerate((oa, ob)):
+                    assert np.array_equal(tabs[i].view.view(torch.int64).cpu().numpy().astype(np.uint64), o)
+                    tabs[i].check(8 * len(o), "offsets")
+                    srcs[i].check(0, "src")
+    finally:
+        other.close()
+
+
+@pytest.mark.parametrize("serial", [False, True])
+def test_host_buffer_calls_stay_inside_their_buffers(monkeypatch, serial):
+    """rcx_encode_blocks / rcx_decode_blocks, chunked (three decode chunks, five encode chunks) and RCX_HOST_SERIAL=1, with
+    dst, the table and out as contiguous views into larger arrays: nothing is written in front of or behind them."""
+    if serial:
+        monkeypatch.setenv("RCX_HOST_SERIAL", "1")
+    else:
+        monkeypatch.delenv("RCX_HOST_SERIAL", raising=False)
+    block = 4096
+    data = workloads.by_name("zipf", (40 << 20) + 1234, 9)
+    n = len(data)
+    nblocks = rcx.block_count(n, block)
+    ctx = rcx.Context(0)
+    try:
+        for coder in CODERS:
+            cap = rcx.encode_bound(n, block, coder)
+            i = np.arange(cap + 2 * GUARD + 3)
+            big = ((i * 37 + 11) % 251 + 1).astype(np.uint8)
+            before = big.copy()
+            dst = big[GUARD + 3: GUARD + 3 + cap]
+            tab = np.full(nblocks + 1 + 64, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+            offsets = tab[32: 32 + nblocks + 1]
+            size = ctx.encode_blocks_into(data, block, dst, offsets, coder)
+            assert size == int(offsets[-1])
+            assert np.array_equal(big[: GUARD + 3], before[: GUARD + 3]), "written in front of dst"
+            assert np.array_equal(big[GUARD + 3 + size:], before[GUARD + 3 + size:]), "written past the size reported"
+            assert bool((tab[:32] == 0x5A5A5A5A5A5A5A5A).all() and (tab[32 + nblocks + 1:] == 0x5A5A5A5A5A5A5A5A).all()), "written around the table"
+            j = np.arange(n + 2 * GUARD + 7)
+            outbig = ((j * 53 + 5) % 251 + 1).astype(np.uint8)
+            out_before = outbig.copy()
+            comp = big[GUARD + 3: GUARD + 3 + size].copy()
+            got = ctx.decode_blocks_into(comp, size, offsets.copy(), block, outbig[GUARD + 7: GUARD + 7 + n], coder)
+            assert got == n and np.array_equal(outbig[GUARD + 7: GUARD + 7 + n], data), coder
+            assert np.array_equal(outbig[: GUARD + 7], out_before[: GUARD + 7]), "written in front of out"
+            assert np.array_equal(outbig[GUARD + 7 + n:], out_before[GUARD + 7 + n:]), "written behind out"
+    finally:
+        ctx.close()

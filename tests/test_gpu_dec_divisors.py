@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from test_gpu_parity import Guarded  # noqa: E402
+
 
 @pytest.fixture(scope="module")
 def ctx():
@@ -25,17 +27,29 @@ def ctx():
 
 
 def round_trip(ctx, data, block, dst_offset=0):
+    """Encode and decode on the device, every buffer guarded (test_gpu_parity.Guarded): the encoder writes only the
+    streams and the table, the decoder only its n output bytes, and neither writes its input."""
     n = len(data)
-    src = torch.from_numpy(np.ascontiguousarray(data, dtype=np.uint8)).cuda()
+    data = np.ascontiguousarray(data, dtype=np.uint8)
     nblocks = rcx.block_count(n, block)
-    dst = torch.zeros(rcx.encode_bound(n, block), dtype=torch.uint8, device="cuda")
-    offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
-    ctx.encode_blocks_device(src, block, dst, offs)
+    src = Guarded(n, 0, data, salt=1)
+    dst = Guarded(rcx.encode_bound(n, block), 0, salt=2)
+    offs = Guarded(8 * (nblocks + 1), 0, salt=3)
+    table = offs.view.view(torch.int64)
+    ctx.encode_blocks_device(src.view, block, dst.view, table)
     ctx.sync_status()
-    out = torch.zeros(n + dst_offset + 16, dtype=torch.uint8, device="cuda")
-    ctx.decode_blocks_device(dst, int(offs[-1].item()), offs, n, block, out[dst_offset:])
+    total = int(table[-1].item())
+    src.check(0, "encode src")
+    offs.check(8 * (nblocks + 1), "encode offsets")
+    dst.check(total, "encode dst")
+    dst.before, offs.before = dst.tensor.clone(), offs.tensor.clone()  # the decoder's inputs: nothing may change now
+    out = Guarded(n, dst_offset, salt=6)
+    ctx.decode_blocks_device(dst.view, total, table, n, block, out.view)
     st, _ = ctx.sync_status(raise_on_error=False)
-    return out[dst_offset:dst_offset + n].cpu().numpy(), st
+    dst.check(0, "decode comp")
+    offs.check(0, "decode offsets")
+    out.check(n, "decode dst")
+    return out.view.cpu().numpy(), st
 
 
 def lengths_around_powers_of_two(top):

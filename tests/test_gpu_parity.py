@@ -26,31 +26,71 @@ def ctx():
     c.close()
 
 
-def gpu_encode(ctx, data, block, src_offset=0, coder=0):
-    """-> (payload np.uint8, offsets np.uint64) through the device-pointer entry points."""
+GUARD = 256  # bytes of guard pattern on each side of every buffer a device call is handed
+
+
+class Guarded:
+    """A buffer handed to a kernel, as a view into a larger cuda tensor: GUARD bytes, `offset` more, the buffer, GUARD
+    bytes.  Everything that is not buffer content holds a position-dependent pattern (nonzero; its complement with
+    `invert`), and a copy of the whole tensor is kept, so that a check after the call sees any byte written outside
+    the range the call may write, and any byte of an input that the call changed."""
+
+    def __init__(self, size, offset=0, content=None, salt=0, invert=False):
+        self.at = GUARD + offset
+        self.size = size
+        i = np.arange(self.at + size + GUARD, dtype=np.int64)
+        image = ((i * 37 + salt * 101 + 11) % 251 + 1).astype(np.uint8)
+        if invert:
+            image = ~image
+        if content is not None:
+            image[self.at: self.at + len(content)] = np.frombuffer(np.ascontiguousarray(content).tobytes(), np.uint8)
+        self.tensor = torch.from_numpy(image).cuda()
+        self.before = self.tensor.clone()
+        self.view = self.tensor[self.at: self.at + size]
+
+    def check(self, written=0, what="buffer"):
+        """Nothing changed but the first `written` bytes of the buffer."""
+        hi = self.at + written
+        for lo_, hi_ in ((0, self.at), (hi, self.tensor.numel())):
+            if not torch.equal(self.tensor[lo_:hi_], self.before[lo_:hi_]):
+                first = lo_ + int(torch.nonzero(self.tensor[lo_:hi_] != self.before[lo_:hi_])[0, 0])
+                raise AssertionError(f"{what}: byte {first - self.at} changed, outside the {written} bytes from 0 it may write")
+
+
+def gpu_encode(ctx, data, block, src_offset=0, coder=0, dst_offset=0, invert=False):
+    """-> (payload np.uint8, offsets np.uint64) through the device-pointer entry points.  Every buffer is guarded
+    (Guarded): the source is not written, and nothing is written past offsets[nblocks] of dst or around the table."""
     from cpprcoder_amd import rcx
     data = np.ascontiguousarray(data, dtype=np.uint8)
     n = len(data)
-    buf = torch.zeros(n + src_offset + 16, dtype=torch.uint8, device="cuda")
-    buf[src_offset:src_offset + n] = torch.from_numpy(data.copy()).cuda()  # (a copy: the input may be a read-only view)
-    src = buf[src_offset:src_offset + n]
     nblocks = rcx.block_count(n, block)
-    dst = torch.zeros(rcx.encode_bound(n, block, coder), dtype=torch.uint8, device="cuda")
-    offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
-    ctx.encode_blocks_device(src, block, dst, offs, coder=coder)
+    src = Guarded(n, src_offset, data, salt=1, invert=invert)
+    dst = Guarded(rcx.encode_bound(n, block, coder), dst_offset, salt=2, invert=invert)
+    offs = Guarded(8 * (nblocks + 1), 0, salt=3, invert=invert)
+    ctx.encode_blocks_device(src.view, block, dst.view, offs.view.view(torch.int64), coder=coder)
     ctx.sync_status()
-    offsets = offs.cpu().numpy().astype(np.uint64)
-    return dst[: int(offsets[-1])].cpu().numpy(), offsets, (dst, offs)
+    offsets = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
+    src.check(0, "encode src")
+    offs.check(8 * (nblocks + 1), "encode offsets")
+    dst.check(int(offsets[-1]), "encode dst")
+    return dst.view[: int(offsets[-1])].cpu().numpy(), offsets, (dst.view, offs.view.view(torch.int64))
 
 
-def gpu_decode(ctx, payload, offsets, n, block, dst_offset=0, comp_offset=0, coder=0):
-    comp = torch.zeros(len(payload) + comp_offset + 16, dtype=torch.uint8, device="cuda")
-    comp[comp_offset:comp_offset + len(payload)] = torch.from_numpy(np.ascontiguousarray(payload)).cuda()
-    offs = torch.from_numpy(np.asarray(offsets).astype(np.int64)).cuda()
-    out = torch.zeros(n + dst_offset + 16, dtype=torch.uint8, device="cuda")
-    ctx.decode_blocks_device(comp[comp_offset:], len(payload), offs, n, block, out[dst_offset:], coder=coder)
+def gpu_decode(ctx, payload, offsets, n, block, dst_offset=0, comp_offset=0, coder=0, invert=False):
+    """Decode through the device-pointer entry point -> (out np.uint8, status, first bad block).  The compressed bytes
+    and the table are guarded inputs (not written; what lies behind comp_size is the guard pattern, not zeros), and
+    nothing is written outside the n output bytes."""
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
+    table = np.ascontiguousarray(np.asarray(offsets).astype(np.int64))
+    offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
+    out = Guarded(n, dst_offset, salt=6, invert=invert)
+    ctx.decode_blocks_device(comp.view, len(payload), offs.view.view(torch.int64), n, block, out.view, coder=coder)
     st, bad = ctx.sync_status(raise_on_error=False)
-    return out[dst_offset:dst_offset + n].cpu().numpy(), st, bad
+    comp.check(0, "decode comp")
+    offs.check(0, "decode offsets")
+    out.check(n, "decode dst")
+    return out.view.cpu().numpy(), st, bad
 
 
 def assert_same_blocks(payload, offsets, slots, sizes):

@@ -166,6 +166,14 @@ def test_against_reference_build(oracle, reference):
                           agreement_cases.adaptive(reference) if reference is not None else None)
 
 
+def test_damaged_streams_against_reference_build(oracle, reference):
+    """The oracle decodes damaged streams as the reference build does (agreement_cases.damaged): the static coder's payload
+    flips and count edits, the rANS coders' payload flips.  tests/test_gpu_damaged.py holds the GPU to the oracle there."""
+    live = reference is not None and reference.ans is not None
+    agreement_cases.agree(agreement_cases.stored("damaged"), agreement_cases.damaged(oracle),
+                          agreement_cases.damaged(reference) if live else None)
+
+
 def long_inputs():
     """The recipes of tests/golden/make_golden_long.py (label -> bytes)."""
     no_halving = (1 << 24) - 256
