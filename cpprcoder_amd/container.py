@@ -19,6 +19,22 @@ Layout (little-endian):
 
 The header functions are plain Python; pack()/unpack() go through the HIP library (there is no CPU coder
 here: without librcx.so and a GPU they raise).
+
+unpack_range(blob, start, stop) decodes only the blocks that cover [start, stop), through the item call
+(rcx_decode_items: any subset of a set of streams).  It is refused for block-sorted containers, whose bytes are
+not in place before the whole inverse transform has run.
+
+The item container holds independent buffers of differing sizes (include/rcx.h, "Item calls"), each coded as the
+reference codes a file of those bytes; an item of length 0 has no stream.  Its own magic, so that parse() keeps
+rejecting what it does not know:
+    0   4  magic  b"RCXI"
+    4   1  version (1)
+    5   1  coder
+    6   2  flags (0)
+    8   8  nitems
+    16  8 * nitems        the items' lengths
+    ..  8 * (nitems + 1)  offsets of the item streams in the payload
+    ..  payload: the item streams back to back
 """
 import struct
 
@@ -28,6 +44,10 @@ MAGIC = b"RCXB"
 VERSION = 1
 FLAG_BLKSORT = 1
 _FIXED = struct.Struct("<4sBBHIQQ")
+ITEM_MAGIC = b"RCXI"
+ITEM_VERSION = 1
+_ITEM_FIXED = struct.Struct("<4sBBHQ")
+MAX_ITEM = (1 << 24) - 256  # RCX_MAX_BLOCK
 
 
 def coded_size(n: int, flags: int) -> int:
@@ -99,6 +119,99 @@ def unpack(blob, ctx=None) -> bytes:
         if c["flags"] & FLAG_BLKSORT:
             out = ctx.bwt_decode(out)
         return out.tobytes()
+    finally:
+        if own:
+            ctx.close()
+
+
+def unpack_range(blob, start: int, stop: int, ctx=None) -> bytes:
+    """The bytes [start, stop) of the original, decoding only the blocks that cover them."""
+    from . import rcx
+    c = parse(blob)
+    if c["flags"] & FLAG_BLKSORT:
+        raise ContainerError("a block-sorted container has no byte ranges: unpack() it")
+    if not 0 <= start <= stop <= c["n"]:
+        raise ContainerError("range outside the data")
+    if start == stop:
+        return b""
+    block, n = c["block"], c["n"]
+    first, last = start // block, (stop - 1) // block
+    pick = np.arange(first, last + 1, dtype=np.uint64)
+    lengths = np.full(c["nblocks"], block, dtype=np.uint64)
+    lengths[-1] = n - (c["nblocks"] - 1) * block
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        parts = ctx.decode_items(c["payload"], c["offsets"], lengths, pick=pick, coder=c["coder"])
+    finally:
+        if own:
+            ctx.close()
+    out = np.concatenate(parts)
+    return out[start - first * block: stop - first * block].tobytes()
+
+
+def item_header_bytes(coder: int, lengths, offsets) -> bytes:
+    lengths = np.ascontiguousarray(lengths, dtype="<u8")
+    offsets = np.ascontiguousarray(offsets, dtype="<u8")
+    if len(offsets) != len(lengths) + 1:
+        raise ContainerError("offsets do not match the number of items")
+    if len(lengths) and int(lengths.max()) > MAX_ITEM:
+        raise ContainerError("an item is longer than the coder takes")
+    return _ITEM_FIXED.pack(ITEM_MAGIC, ITEM_VERSION, coder, 0, len(lengths)) + lengths.tobytes() + offsets.tobytes()
+
+
+def parse_items(blob):
+    """-> dict(coder, nitems, lengths uint64[nitems], offsets uint64[nitems+1], payload uint8 view)"""
+    buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+    if len(buf) < _ITEM_FIXED.size:
+        raise ContainerError("shorter than a header")
+    magic, version, coder, flags, nitems = _ITEM_FIXED.unpack(bytes(buf[: _ITEM_FIXED.size]))
+    if magic != ITEM_MAGIC:
+        raise ContainerError("not an RCXI container")
+    if version != ITEM_VERSION or coder not in (0, 1, 2, 3) or flags:
+        raise ContainerError("unsupported container version, coder or flags")
+    mid = _ITEM_FIXED.size + 8 * nitems
+    end = mid + 8 * (nitems + 1)
+    if nitems > len(buf) or len(buf) < end:
+        raise ContainerError("truncated tables")
+    lengths = np.frombuffer(bytes(buf[_ITEM_FIXED.size:mid]), dtype="<u8").astype(np.uint64)
+    offsets = np.frombuffer(bytes(buf[mid:end]), dtype="<u8").astype(np.uint64)
+    if nitems and int(lengths.max()) > MAX_ITEM:
+        raise ContainerError("an item is longer than the coder takes")
+    sizes = np.diff(offsets.astype(np.int64))
+    if offsets[0] != 0 or np.any(sizes < 0) or end + int(offsets[-1]) != len(buf):
+        raise ContainerError("offset table does not match the payload")
+    if np.any((lengths == 0) != (sizes == 0)):
+        raise ContainerError("an item of length 0 has no stream, and only such an item")
+    return {"coder": coder, "nitems": nitems, "lengths": lengths, "offsets": offsets, "payload": buf[end:]}
+
+
+def pack_items(items, coder: int = 0, ctx=None) -> bytes:
+    """items: a list of buffers -> an RCXI container."""
+    from . import rcx
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        parts = [np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if not isinstance(x, np.ndarray) else x, dtype=np.uint8) for x in items]
+        payload, offsets = ctx.encode_items(parts, coder=coder)
+        return item_header_bytes(coder, [len(x) for x in parts], offsets) + payload.tobytes()
+    finally:
+        if own:
+            ctx.close()
+
+
+def unpack_items(blob, pick=None, ctx=None) -> list:
+    """-> the list of the picked items' bytes (all of them, in order, if pick is None); picks may repeat."""
+    from . import rcx
+    c = parse_items(blob)
+    if pick is not None and any(not 0 <= int(k) < c["nitems"] for k in pick):
+        raise ContainerError("no such item")
+    if c["nitems"] == 0 or (pick is not None and len(pick) == 0):
+        return []
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        return [x.tobytes() for x in ctx.decode_items(c["payload"], c["offsets"], c["lengths"], pick=pick, coder=c["coder"])]
     finally:
         if own:
             ctx.close()

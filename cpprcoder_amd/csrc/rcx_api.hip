@@ -46,6 +46,21 @@ inline hipError_t rcx_enter_device(int device)
 
 struct HostPipe; // rcx_host.hpp: streams, threads' staging and bookkeeping of the host-buffer entry points
 
+// What the host plans for an item call (rcx_items.hpp): the work order, its tables, the length classes of the scratch slots.
+struct ItemClass {
+    u64 first, count; // work entries
+    u64 stride;       // bytes between their scratch slots
+    u64 slot_base;    // where the class's slots begin in the context's slots
+};
+
+struct ItemPlan {
+    std::vector<u64> at;
+    std::vector<u32> len, id, stream, inv;
+    std::vector<ItemClass> classes; // longest first (encode only)
+    u64 nwork = 0, slots_bytes = 0;
+    u32 longest = 0;
+};
+
 } // namespace
 
 struct rcx_ctx {
@@ -58,6 +73,7 @@ struct rcx_ctx {
     int cus = 256;           // compute units of the device
     bool rans1_lds_set = false; // rcx_enc_rans1_k has been allowed its 128 KiB of dynamic LDS
     bool rans1w_lds_set = false; // the same for rcx_enc_rans1w_k
+    bool rans1_items_lds_set = false, rans1w_items_lds_set = false; // ... and for their item instantiations
     bool rans_track = false; // the single-stream rANS decode wants the payload bytes consumed (status[2])
     // scratch
     u8* slots = nullptr;
@@ -77,6 +93,10 @@ struct rcx_ctx {
     DivEntry* divtab = nullptr;
     u32* divq = nullptr;        // the same entries as the quad decoder reads them (rcx_oct.hpp, RCX_QUAD_DIVQ_DW), behind divtab
     u32 divtab_block = 0;
+    u8* itab = nullptr;         // item calls: the work tables of the last call (rcx_items.hpp)
+    u64 itab_bytes = 0;
+    std::vector<u64> itab_host; // ... as they are put together for the upload
+    ItemPlan plan;              // ... and the plan they come from (kept for its vectors' capacity)
     u32* status = nullptr;      // device: [flags, first bad block, track0, track1]
     u32* status_host = nullptr; // pinned, same 4 words
     // staging for the host-pointer entry points
@@ -365,6 +385,7 @@ void rcx_ctx_destroy(rcx_ctx* c)
     if (c->starts) (void)hipFree(c->starts);
     if (c->models) (void)hipFree(c->models);
     if (c->redo) (void)hipFree(c->redo);
+    if (c->itab) (void)hipFree(c->itab);
     if (c->ties) (void)hipFree(c->ties);
     if (c->divtab) (void)hipFree(c->divtab);
     if (c->status) (void)hipFree(c->status);
@@ -429,45 +450,42 @@ int rcx_encode_blocks_device(rcx_ctx* c, int coder, const void* d_src, uint64_t 
 namespace
 {
 
-// The encode launches for blocks whose scratch (slots, sizes, starts, models, redo) begins `rg.first` blocks into the
-// context's arrays, which the caller has reserved.  The many-block call above is the whole range; the host-buffer
-// pipeline (rcx_host.hpp) runs several chunks of one buffer at once, each on its own stream and its own part of the
-// scratch, `packed` = every workgroup / wave carries its full load of blocks, so that chunks share the machine.
-int encode_range(rcx_ctx* c, int coder, const void* d_src, u64 n, u32 block, void* d_dst, u64 dst_cap, u64* d_offsets, hipStream_t s,
-                 ScratchRange rg)
+// The coding launches of pass 1 for `nblocks` work entries of geometry G (rcx_geom.hpp) whose scratch is `v`, slots `slot` bytes
+// apart: all the blocks of a range (RcxBlocks), or the entries of one length class of an item call (RcxItems).
+template <class G>
+int encode_launches(rcx_ctx* c, int coder, const void* d_src, u64 n, u32 block, u64 nblocks, ScratchView v, u64 slot, hipStream_t s, bool packed, G g)
 {
-    const u64 nblocks = rcx_block_count(n, block);
-    const u64 slot = rcx_block_bound_for(coder, block);
-    ScratchView v{c->slots + rg.first * slot, c->sizes + rg.first, c->starts ? c->starts + rg.first : nullptr,
-                  c->models ? c->models + rg.first * RCX_RANS_MODEL_DW : nullptr, c->redo + rg.first};
+    bool& rans1w_set = G::items ? c->rans1w_items_lds_set : c->rans1w_lds_set;
+    bool& rans1_set = G::items ? c->rans1_items_lds_set : c->rans1_lds_set;
+    const int variant = (G::items && c->enc_variant != 0) ? 3 : c->enc_variant; // (the superseded kernels of the diagnostic build know blocks only)
     // Static coder: with fewer than 32768 blocks (two one-wave workgroups per CU) the three-wave kernel, which
     // spreads 64 blocks over three SIMDs, is faster (157 vs 112 GB/s at 16384 blocks); with more, the one-wave
     // kernel fills the machine by itself (202 vs 157 GB/s at 32768 blocks).
-    const bool static3 = coder == RCX_CODER_STATIC && c->enc_variant >= 2 && nblocks < 32768;
+    const bool static3 = coder == RCX_CODER_STATIC && variant >= 2 && nblocks < 32768;
     {
         Timed t(c, s, RCX_T_ENCODE);
         if (is_rans(coder)) { // cppans.h: a block is an octet of lanes, four 8-block waves per workgroup
             const u64 per_wg = 4 * RCX_RANS_BLOCKS;
             const u32 grid = (u32)((nblocks + per_wg - 1) / per_wg);
             if (coder == RCX_CODER_RANS8)
-                hipLaunchKernelGGL(rcx_enc_rans_k<true>, dim3(grid), dim3(256), 0, s, static_cast<const u8*>(d_src), n, block, nblocks, v.slots,
-                                   slot, v.sizes, v.starts, c->status);
+                hipLaunchKernelGGL((rcx_enc_rans_k<true, G>), dim3(grid), dim3(256), 0, s, static_cast<const u8*>(d_src), n, block, nblocks, v.slots,
+                                   slot, v.sizes, v.starts, c->status, g);
             else {
                 // one state per block = one chain per block: the model by octets, then the coding loop one lane per
                 // block, `lanes` blocks per wave so that every SIMD has a wave before any wave carries 64
-                hipLaunchKernelGGL(rcx_rans_model_k<14>, dim3(grid), dim3(256), 0, s, static_cast<const u8*>(d_src), n, block, nblocks, v.models);
+                hipLaunchKernelGGL((rcx_rans_model_k<14, G>), dim3(grid), dim3(256), 0, s, static_cast<const u8*>(d_src), n, block, nblocks, v.models, g);
                 // The coding loop: two waves per 64 blocks (coder, writer), 2 KiB of table per block: one workgroup per CU.
                 // RCX_RANS1_WAVES=1 (diagnostic): the one-wave kernel it replaced, 16 blocks per wave (RCX_RANS1_LANES),
                 // four waves per workgroup.
                 const char* one = getenv("RCX_RANS1_WAVES");
                 if (!(one && atoi(one) == 1)) {
-                    if (!c->rans1w_lds_set) { // more than the 64 KiB a kernel gets without asking
-                        if (hipFuncSetAttribute(reinterpret_cast<const void*>(rcx_enc_rans1w_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RCX_R1W_LDS_BYTES) != hipSuccess)
+                    if (!rans1w_set) { // more than the 64 KiB a kernel gets without asking
+                        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rcx_enc_rans1w_k<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RCX_R1W_LDS_BYTES) != hipSuccess)
                             return RCX_E_HIP;
-                        c->rans1w_lds_set = true;
+                        rans1w_set = true;
                     }
-                    hipLaunchKernelGGL(rcx_enc_rans1w_k, dim3((u32)((nblocks + 63) / 64)), dim3(128), RCX_R1W_LDS_BYTES, s, static_cast<const u8*>(d_src), n, block,
-                                       nblocks, static_cast<const u32*>(v.models), v.slots, slot, v.sizes, v.starts, c->status);
+                    hipLaunchKernelGGL(rcx_enc_rans1w_k<G>, dim3((u32)((nblocks + 63) / 64)), dim3(128), RCX_R1W_LDS_BYTES, s, static_cast<const u8*>(d_src), n, block,
+                                       nblocks, static_cast<const u32*>(v.models), v.slots, slot, v.sizes, v.starts, c->status, g);
                 } else {
                     u32 lanes = 16;
                     if (const char* v2 = getenv("RCX_RANS1_LANES")) { const int q = atoi(v2); if (q == 1 || q == 2 || q == 4 || q == 8 || q == 16) lanes = (u32)q; }
@@ -479,60 +497,78 @@ int encode_range(rcx_ctx* c, int coder, const void* d_src, u64 n, u32 block, voi
                     if (getenv("RCX_RANS1_ALONE") && lds_bytes < 84u * 1024u) lds_bytes = 84u * 1024u;
                     u32 lanes_shift = 0;
                     while ((1u << lanes_shift) < lanes) ++lanes_shift;
-                    if (!c->rans1_lds_set) {
-                        if (hipFuncSetAttribute(reinterpret_cast<const void*>(rcx_enc_rans1_k), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
+                    if (!rans1_set) {
+                        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rcx_enc_rans1_k<G>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
                             return RCX_E_HIP;
-                        c->rans1_lds_set = true;
+                        rans1_set = true;
                     }
-                    hipLaunchKernelGGL(rcx_enc_rans1_k, dim3(grid1), dim3(64 * RCX_RANS1_ENC_WAVES), lds_bytes, s, static_cast<const u8*>(d_src), n, block,
-                                       nblocks, static_cast<const u32*>(v.models), v.slots, slot, v.sizes, v.starts, c->status, lanes_shift);
+                    hipLaunchKernelGGL(rcx_enc_rans1_k<G>, dim3(grid1), dim3(64 * RCX_RANS1_ENC_WAVES), lds_bytes, s, static_cast<const u8*>(d_src), n, block,
+                                       nblocks, static_cast<const u32*>(v.models), v.slots, slot, v.sizes, v.starts, c->status, lanes_shift, g);
                 }
             }
         } else if (static3) {
-            const u32 lanes = rg.packed ? RCX_LANES : encode_lanes(c, nblocks);
+            const u32 lanes = packed ? RCX_LANES : encode_lanes(c, nblocks);
             const u32 grid = (u32)((nblocks + lanes - 1) / lanes);
-            hipLaunchKernelGGL(rcx_enc_static3_k, dim3(grid), dim3(RCX_ST3_THREADS), 0, s, static_cast<const u8*>(d_src), n, block,
-                               nblocks, v.slots, slot, v.sizes, c->status, v.redo, lanes);
+            hipLaunchKernelGGL(rcx_enc_static3_k<G>, dim3(grid), dim3(RCX_ST3_THREADS), 0, s, static_cast<const u8*>(d_src), n, block,
+                               nblocks, v.slots, slot, v.sizes, c->status, v.redo, lanes, g);
         } else if (coder == RCX_CODER_STATIC) {
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_enc_static_k, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block, nblocks,
-                               v.slots, slot, v.sizes, c->status, static_cast<const u32*>(nullptr));
-        } else if (c->enc_variant == 3) {
-            const u32 lanes = rg.packed ? RCX_LANES : encode_lanes(c, nblocks);
+            hipLaunchKernelGGL(rcx_enc_static_k<G>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block, nblocks,
+                               v.slots, slot, v.sizes, c->status, static_cast<const u32*>(nullptr), g);
+        } else if (variant == 3) {
+            const u32 lanes = packed ? RCX_LANES : encode_lanes(c, nblocks);
             const u32 grid = (u32)((nblocks + lanes - 1) / lanes);
-            hipLaunchKernelGGL(rcx_enc_mc5_k, dim3(grid), dim3(RCX_MC5_THREADS), 0, s, static_cast<const u8*>(d_src), n, block,
-                               nblocks, v.slots, slot, v.sizes, c->divtab, c->status, v.redo, lanes);
+            hipLaunchKernelGGL(rcx_enc_mc5_k<G>, dim3(grid), dim3(RCX_MC5_THREADS), 0, s, static_cast<const u8*>(d_src), n, block,
+                               nblocks, v.slots, slot, v.sizes, c->divtab, c->status, v.redo, lanes, g);
 #if defined(RCX_WITH_VARIANTS)
-        } else if (c->enc_variant == 2) {
+        } else if (variant == 2) {
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
             hipLaunchKernelGGL(rcx_enc_mc_k, dim3(grid), dim3(RCX_MC_THREADS), 0, s, static_cast<const u8*>(d_src), n, block, nblocks,
                                v.slots, slot, v.sizes, c->divtab, c->status);
-        } else if (c->enc_variant == 1) {
+        } else if (variant == 1) {
             const u32 grid = (u32)((nblocks + RCX_OCT_BLOCKS - 1) / RCX_OCT_BLOCKS);
             hipLaunchKernelGGL(rcx_enc_oct_k, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block, nblocks,
                                v.slots, slot, v.sizes, c->divtab, c->status);
 #endif
         } else {
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_enc_adaptive_k<false>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block,
+            hipLaunchKernelGGL((rcx_enc_adaptive_k<false, false, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block,
                                nblocks, v.slots, slot, v.sizes, c->divtab, c->status, 0u, static_cast<u32*>(nullptr),
-                               static_cast<const u32*>(nullptr));
+                               static_cast<const u32*>(nullptr), g);
         }
         // (the second passes are part of the encode time: on adversarial data they are not free)
         if (static3) { // the same for the static coder
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_enc_static_k, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block, nblocks,
-                               v.slots, slot, v.sizes, c->status, static_cast<const u32*>(v.redo));
+            hipLaunchKernelGGL(rcx_enc_static_k<G>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block, nblocks,
+                               v.slots, slot, v.sizes, c->status, static_cast<const u32*>(v.redo), g);
         }
-        if (coder == RCX_CODER_ADAPTIVE && c->enc_variant == 3) {
+        if (coder == RCX_CODER_ADAPTIVE && variant == 3) {
             // Blocks in which a carry ran through more output bytes than the five-wave kernel keeps in LDS were
             // marked, not finished: the one-wave kernel encodes them again.  Nothing is marked on ordinary data
             // and every wave of this launch returns at once.
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_enc_adaptive_k<false>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block,
+            hipLaunchKernelGGL((rcx_enc_adaptive_k<false, false, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_src), n, block,
                                nblocks, v.slots, slot, v.sizes, c->divtab, c->status, 0u, static_cast<u32*>(nullptr),
-                               static_cast<const u32*>(v.redo));
+                               static_cast<const u32*>(v.redo), g);
         }
+    }
+    return RCX_OK;
+}
+
+// The encode launches for blocks whose scratch (slots, sizes, starts, models, redo) begins `rg.first` blocks into the
+// context's arrays, which the caller has reserved.  The many-block call above is the whole range; the host-buffer
+// pipeline (rcx_host.hpp) runs several chunks of one buffer at once, each on its own stream and its own part of the
+// scratch, `packed` = every workgroup / wave carries its full load of blocks, so that chunks share the machine.
+int encode_range(rcx_ctx* c, int coder, const void* d_src, u64 n, u32 block, void* d_dst, u64 dst_cap, u64* d_offsets, hipStream_t s,
+                 ScratchRange rg)
+{
+    const u64 nblocks = rcx_block_count(n, block);
+    const u64 slot = rcx_block_bound_for(coder, block);
+    ScratchView v{c->slots + rg.first * slot, c->sizes + rg.first, c->starts ? c->starts + rg.first : nullptr,
+                  c->models ? c->models + rg.first * RCX_RANS_MODEL_DW : nullptr, c->redo + rg.first};
+    {
+        const int e = encode_launches(c, coder, d_src, n, block, nblocks, v, slot, s, rg.packed, RcxBlocks{});
+        if (e != RCX_OK) return e;
     }
     {
         Timed t(c, s, RCX_T_SCAN);
@@ -578,60 +614,60 @@ int rcx_decode_blocks_device(rcx_ctx* c, int coder, const void* d_comp, uint64_t
 namespace
 {
 
-// The decode launches for `nblocks` blocks whose redo marks begin `rg.first` entries into the context's array (see
-// encode_range); the divisor table and the redo array are in place.
-int decode_range(rcx_ctx* c, int coder, const void* d_comp, u64 comp_size, const u64* d_offsets, u64 nblocks, u32 block, u64 n, void* d_dst,
-                 hipStream_t s, ScratchRange rg)
+// The decode launches for `nblocks` work entries of geometry G (see encode_launches); `redo` = their marks.
+template <class G>
+int decode_launches(rcx_ctx* c, int coder, const void* d_comp, u64 comp_size, const u64* d_offsets, u64 nblocks, u32 block, u64 n, void* d_dst,
+                    hipStream_t s, u32* redo, bool packed, G g)
 {
-    u32* const redo = c->redo ? c->redo + rg.first : nullptr;
+    const int lanes_per = (G::items && decode_lanes(c, nblocks) == 8) ? 4 : decode_lanes(c, nblocks); // (the octet kernel of the diagnostic build knows blocks only)
     if (is_rans(coder)) {
         Timed t(c, s, RCX_T_DECODE);
         const u64 per_wg = 4 * RCX_RANS_BLOCKS;
         const u32 grid = (u32)((nblocks + per_wg - 1) / per_wg);
         if (coder == RCX_CODER_RANS8)
-            hipLaunchKernelGGL(rcx_dec_rans8_k<4>, dim3(grid), dim3(256), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
-                               block, n, static_cast<u8*>(d_dst), c->status);
+            hipLaunchKernelGGL((rcx_dec_rans8_k<4, G>), dim3(grid), dim3(256), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
+                               block, n, static_cast<u8*>(d_dst), c->status, g);
         else {
-            const u32 quads = rg.packed ? RCX_QUAD_BLOCKS : decode_quads(c, nblocks);
+            const u32 quads = packed ? RCX_QUAD_BLOCKS : decode_quads(c, nblocks);
             const u64 per_wg1 = (u64)quads * RCX_QUAD_DEC_WAVES;
             const u32 grid1 = (u32)((nblocks + per_wg1 - 1) / per_wg1);
-            hipLaunchKernelGGL(rcx_dec_rans1_quad_k<RCX_QUAD_DEC_WAVES>, dim3(grid1), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
+            hipLaunchKernelGGL((rcx_dec_rans1_quad_k<RCX_QUAD_DEC_WAVES, G>), dim3(grid1), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
                                static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks, block, n, static_cast<u8*>(d_dst), c->status,
-                               quads, c->rans_track ? c->status + 2 : static_cast<u32*>(nullptr));
+                               quads, c->rans_track ? c->status + 2 : static_cast<u32*>(nullptr), g);
         }
         return hipGetLastError() == hipSuccess ? RCX_OK : RCX_E_HIP;
     }
-    const bool quad = coder == RCX_CODER_ADAPTIVE && decode_lanes(c, nblocks) == 4;
-    const bool squad = coder == RCX_CODER_STATIC && decode_lanes(c, nblocks) != 1;
+    const bool quad = coder == RCX_CODER_ADAPTIVE && lanes_per == 4;
+    const bool squad = coder == RCX_CODER_STATIC && lanes_per != 1;
     {
         Timed t(c, s, RCX_T_DECODE);
-        if (coder == RCX_CODER_STATIC && decode_lanes(c, nblocks) != 1) {
-            const u32 quads = rg.packed ? RCX_QUAD_BLOCKS : decode_quads(c, nblocks);
+        if (coder == RCX_CODER_STATIC && lanes_per != 1) {
+            const u32 quads = packed ? RCX_QUAD_BLOCKS : decode_quads(c, nblocks);
             const u64 per_wg = (u64)quads * RCX_QUAD_DEC_WAVES;
             const u32 grid = (u32)((nblocks + per_wg - 1) / per_wg);
-            hipLaunchKernelGGL(rcx_dec_static_quad_k<RCX_QUAD_DEC_WAVES>, dim3(grid), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
+            hipLaunchKernelGGL((rcx_dec_static_quad_k<RCX_QUAD_DEC_WAVES, G>), dim3(grid), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
                                static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks, block, n, static_cast<u8*>(d_dst), c->status,
-                               redo, quads);
+                               redo, quads, g);
         } else if (coder == RCX_CODER_STATIC) {
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_dec_static_k<false>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
+            hipLaunchKernelGGL((rcx_dec_static_k<false, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
                                block, n, static_cast<u8*>(d_dst), c->status, static_cast<u32*>(nullptr),
-                               static_cast<const u32*>(nullptr));
-        } else if (decode_lanes(c, nblocks) == 4) {
-            const u32 quads = rg.packed ? RCX_QUAD_BLOCKS : decode_quads(c, nblocks);
+                               static_cast<const u32*>(nullptr), g);
+        } else if (lanes_per == 4) {
+            const u32 quads = packed ? RCX_QUAD_BLOCKS : decode_quads(c, nblocks);
             if (wide_workgroups(c, nblocks)) {
                 const u64 per_wg = (u64)quads * RCX_QUAD_DEC_WAVES;
                 const u32 grid = (u32)((nblocks + per_wg - 1) / per_wg);
-                hipLaunchKernelGGL(rcx_dec_quad_k<RCX_QUAD_DEC_WAVES>, dim3(grid), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
+                hipLaunchKernelGGL((rcx_dec_quad_k<RCX_QUAD_DEC_WAVES, G>), dim3(grid), dim3(64 * RCX_QUAD_DEC_WAVES), 0, s,
                                    static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks, block, n, static_cast<u8*>(d_dst), c->divq,
-                                   c->status, redo, quads);
+                                   c->status, redo, quads, g);
             } else {
                 const u32 grid = (u32)((nblocks + quads - 1) / quads);
-                hipLaunchKernelGGL(rcx_dec_quad_k<1>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
-                                   block, n, static_cast<u8*>(d_dst), c->divq, c->status, redo, quads);
+                hipLaunchKernelGGL((rcx_dec_quad_k<1, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
+                                   block, n, static_cast<u8*>(d_dst), c->divq, c->status, redo, quads, g);
             }
 #if defined(RCX_WITH_VARIANTS)
-        } else if (decode_lanes(c, nblocks) == 8) {
+        } else if (lanes_per == 8) {
             if (wide_workgroups(c, nblocks)) {
                 const u64 per_wg = RCX_OCT_BLOCKS * RCX_OCT_DEC_WAVES;
                 const u32 grid = (u32)((nblocks + per_wg - 1) / per_wg);
@@ -646,29 +682,40 @@ int decode_range(rcx_ctx* c, int coder, const void* d_comp, u64 comp_size, const
 #endif
         } else {
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_dec_adaptive_k<false>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets,
+            hipLaunchKernelGGL((rcx_dec_adaptive_k<false, false, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets,
                                nblocks, block, n, static_cast<u8*>(d_dst), c->divtab, c->status, static_cast<u32*>(nullptr),
-                               static_cast<const u32*>(nullptr));
+                               static_cast<const u32*>(nullptr), g);
         }
         if (quad) {
             // Blocks whose stream asked for a symbol past the table (corrupt input) were marked, not decoded, by
             // the quad kernel: the one-lane kernel, which has the reference's fall-through for that case, decodes
             // them again.  On valid input nothing is marked and every wave of this launch returns at once.
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_dec_adaptive_k<false>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets,
+            hipLaunchKernelGGL((rcx_dec_adaptive_k<false, false, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets,
                                nblocks, block, n, static_cast<u8*>(d_dst), c->divtab, c->status, static_cast<u32*>(nullptr),
-                               static_cast<const u32*>(redo));
+                               static_cast<const u32*>(redo), g);
         }
         if (squad) { // the same for the static coder: a target past the table or a symbol of count 0
             const u32 grid = (u32)((nblocks + RCX_LANES - 1) / RCX_LANES);
-            hipLaunchKernelGGL(rcx_dec_static_k<false>, dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
-                               block, n, static_cast<u8*>(d_dst), c->status, static_cast<u32*>(nullptr), static_cast<const u32*>(redo));
+            hipLaunchKernelGGL((rcx_dec_static_k<false, G>), dim3(grid), dim3(64), 0, s, static_cast<const u8*>(d_comp), (u64)comp_size, d_offsets, nblocks,
+                               block, n, static_cast<u8*>(d_dst), c->status, static_cast<u32*>(nullptr), static_cast<const u32*>(redo), g);
         }
     }
     return hipGetLastError() == hipSuccess ? RCX_OK : RCX_E_HIP;
 }
 
+// The decode launches for `nblocks` blocks whose redo marks begin `rg.first` entries into the context's array (see
+// encode_range); the divisor table and the redo array are in place.
+int decode_range(rcx_ctx* c, int coder, const void* d_comp, u64 comp_size, const u64* d_offsets, u64 nblocks, u32 block, u64 n, void* d_dst,
+                 hipStream_t s, ScratchRange rg)
+{
+    u32* const redo = c->redo ? c->redo + rg.first : nullptr;
+    return decode_launches(c, coder, d_comp, comp_size, d_offsets, nblocks, block, n, d_dst, s, redo, rg.packed, RcxBlocks{});
+}
+
 } // namespace
+
+#include "rcx_items.hpp"
 
 extern "C" {
 

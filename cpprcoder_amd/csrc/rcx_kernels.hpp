@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rcx_lane.hpp"
+#include "rcx_geom.hpp"
 
 #define RCX_ST_CAPACITY 1u
 #define RCX_ST_CORRUPT 2u
@@ -55,11 +56,11 @@ __device__ __forceinline__ u32 rcx_byte_of(const U4& w, u32 j)
 // (track[0] = failing symbol or 0xFFFFFFFF, track[1] = 1 if only the final flush fails).
 // LONG = a single stream of more than RCX_MAX_BLOCK symbols: no divisor table, the lane divides by its own total and
 // halves the table at 2^24 (cpprcoder.h:1138-1176).
-template <bool STREAM, bool LONG = false>
+template <bool STREAM, bool LONG = false, class G = RcxBlocks>
 __global__ __launch_bounds__(64) void rcx_enc_adaptive_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks,
                                                          u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes,
                                                          const DivEntry* __restrict__ divtab, u32* status,
-                                                         u32 sink_bytes, u32* track, const u32* __restrict__ only)
+                                                         u32 sink_bytes, u32* track, const u32* __restrict__ only, const G g = G())
 {
     __shared__ U4 lds[RCX_LDS_U4];
     const u32 lane = threadIdx.x;
@@ -71,8 +72,9 @@ __global__ __launch_bounds__(64) void rcx_enc_adaptive_k(const u8* __restrict__ 
         live = live && only[blk] != 0;
         if (!__any(live)) return;
     }
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
 
     Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
     tree.reset();
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(64) void rcx_enc_adaptive_k(const u8* __restrict__ 
 
     const u32 maxlen = rcx_wave_max(len);
     // fast path: every lane has a full block and 16-byte loads are aligned
-    const bool full = !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool full = !G::items && !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
     const u8* in = src + at;
 
     if (LONG) {
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(64) void rcx_enc_adaptive_k(const u8* __restrict__ 
         }
         const u32 bytes = enc.finish();
         sizes[blk] = enc.overflow ? (u32)slot : bytes;
-        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
     }
 }
 
@@ -139,8 +141,9 @@ __global__ __launch_bounds__(64) void rcx_enc_adaptive_k(const u8* __restrict__ 
 // Size prefix: offsets[b] = sum_{i<b} sizes[i], offsets[nblocks] = total.
 // One workgroup of 1024 threads; wave scans via DPP shuffles, 16 wave totals via LDS.
 // ===========================================================================
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(1024) void rcx_scan_sizes_k(const u32* __restrict__ sizes, u64 nblocks, u64* __restrict__ offsets,
-                                                         u64 dst_cap, u32* status)
+                                                         u64 dst_cap, u32* status, const G g = G())
 {
     __shared__ u64 wave_total[16];
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(1024) void rcx_scan_sizes_k(const u32* __restrict__
     const u64 first = (u64)tid * per;
     const u64 last = (first + per) < nblocks ? (first + per) : nblocks;
     u64 mine = 0;
-    for (u64 b = first; b < last; ++b) mine += sizes[b];
+    for (u64 b = first; b < last; ++b) mine += rcx_size_of(g, sizes, b);
     // inclusive wave scan
     u64 incl = mine;
 #pragma unroll
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(1024) void rcx_scan_sizes_k(const u32* __restrict__
     u64 run = before + incl - mine;
     for (u64 b = first; b < last; ++b) {
         offsets[b] = run;
-        run += sizes[b];
+        run += rcx_size_of(g, sizes, b);
     }
     if (tid == 1023) {
         offsets[nblocks] = before + incl;
@@ -176,13 +179,14 @@ __global__ __launch_bounds__(1024) void rcx_scan_sizes_k(const u32* __restrict__
 // destination is written in aligned 16-byte pieces, the (4-byte aligned) source
 // words are byte-shifted into place.
 // ===========================================================================
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(256) void rcx_scatter_k(const u8* __restrict__ slots, u64 slot, const u32* __restrict__ sizes,
                                                      const u64* __restrict__ offsets, u8* __restrict__ dst, u64 dst_cap,
-                                                     const u32* __restrict__ starts)
+                                                     const u32* __restrict__ starts, const G g = G())
 {
     const u64 blk = blockIdx.x;
     const u32 size = sizes[blk];
-    const u64 off = offsets[blk];
+    const u64 off = offsets[rcx_id(g, blk)]; // (the table is in the caller's order, the slots in work order)
     if (off + size > dst_cap) return; // flagged by the scan
     // the stream begins at the start of its slot (range coders) or wherever the backward-writing rANS encoders got to
     const u8* s = slots + blk * slot + (starts ? starts[blk] : 0u);
@@ -219,11 +223,11 @@ static __device__ unsigned long long rcx_dec_stamp_out[8];
 // STREAM = the single-stream entry point: one block whose symbol count n the host took from
 // the header (max(declared,1) clipped to the sink); track[0] = first symbol whose normalize
 // ran out of input, or 0xFFFFFFFF.
-template <bool STREAM, bool LONG = false>
+template <bool STREAM, bool LONG = false, class G = RcxBlocks>
 __global__ __launch_bounds__(64) void rcx_dec_adaptive_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets, u64 nblocks,
                                                          u32 block, u64 n, u8* __restrict__ dst,
                                                          const DivEntry* __restrict__ divtab, u32* status, u32* track,
-                                                         const u32* __restrict__ only)
+                                                         const u32* __restrict__ only, const G g = G())
 {
     __shared__ U4 lds[RCX_DEC_LDS_U4];
     const u32 lane = threadIdx.x;
@@ -234,8 +238,9 @@ __global__ __launch_bounds__(64) void rcx_dec_adaptive_k(const u8* __restrict__ 
         live = live && only[blk] != 0;
         if (!__any(live)) return;
     }
-    const u64 at = live ? blk * (u64)block : 0;
+    u64 at = live ? blk * (u64)block : 0;
     u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
 
     Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
     tree.reset();
@@ -249,16 +254,17 @@ __global__ __launch_bounds__(64) void rcx_dec_adaptive_k(const u8* __restrict__ 
 #endif
     u64 stream_len = 0;
     if (live) {
-        const u64 s0 = offsets[blk], s1 = offsets[blk + 1];
+        const u64 sidx = rcx_stream_of(g, blk);
+        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
         stream_len = s1 - s0;
         if (s1 < s0 || s1 > comp_size || stream_len < (STREAM ? 8u : 9u)) { // cpprcoder.h:878: fewer than 8 bytes cannot even start
-            rcx_flag(status, RCX_ST_CORRUPT, blk);
+            rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
             live = false;
             len = 0;
         } else {
             const u32 declared = dec.begin(comp + s0, comp + s1, ring_col);
             if (!STREAM && declared != len) { // the layout says len; a header that disagrees is not ours
-                rcx_flag(status, RCX_ST_CORRUPT, blk);
+                rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
                 live = false;
                 len = 0;
             }
@@ -267,7 +273,7 @@ __global__ __launch_bounds__(64) void rcx_dec_adaptive_k(const u8* __restrict__ 
     if (!live) dec.idle(comp, ring_col);
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = !G::items && !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
     u8* out = dst + at;
 
     if (LONG) {
@@ -331,7 +337,7 @@ __global__ __launch_bounds__(64) void rcx_dec_adaptive_k(const u8* __restrict__ 
     if (STREAM) {
         if (live) track[0] = dec.short_at;
     } else if (live && dec.taken() > stream_len) {
-        rcx_flag(status, RCX_ST_CORRUPT, blk);
+        rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
     }
 }
 

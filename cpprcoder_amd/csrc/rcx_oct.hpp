@@ -260,11 +260,11 @@ struct QuadInput {
 // A workgroup is WAVES independent waves: with few blocks, 4 waves per workgroup land one on each SIMD of a
 // CU (single-wave workgroups do not: measured 25.4 -> 19.3 ms per GiB at 16384 blocks).
 #define RCX_QUAD_DEC_WAVES 4
-template <int WAVES>
+template <int WAVES, class G = RcxBlocks>
 __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets,
                                                              u64 nblocks, u32 block, u64 n, u8* __restrict__ dst,
                                                              const u32* __restrict__ divq, u32* status,
-                                                             u32* __restrict__ redo, u32 quads_used)
+                                                             u32* __restrict__ redo, u32 quads_used, const G g = G())
 {
     __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_QUAD_LDS_BYTES];
     const u32 lane = threadIdx.x & 63u;
@@ -277,8 +277,9 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     const bool in_use = quad < quads_used;
     const u64 blk = ((u64)blockIdx.x * WAVES + wave_in_wg) * quads_used + (quad & (quads_used - 1u));
     bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
+    u64 at = live ? blk * (u64)block : 0;
     u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
 
     // table group and quarter of this quad (see the layout above)
     const u32 group = 2u * (quad >> 3) + ((0x96u >> (quad & 7u)) & 1u), quarter = (quad & 7u) >> 1;
@@ -300,16 +301,17 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     QuadInput in;
     u64 stream_len = 0;
     if (live) {
-        const u64 s0 = offsets[blk], s1 = offsets[blk + 1];
+        const u64 sidx = rcx_stream_of(g, blk);
+        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
         stream_len = s1 - s0;
         if (s1 < s0 || s1 > comp_size || stream_len < 9) {
-            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, blk);
+            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
             live = false;
             len = 0;
         } else {
             const u32 declared = in.begin(comp + s0, comp + s1, block_ring, parked + 3);
             if (declared != len) {
-                if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, blk);
+                if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
                 live = false;
                 len = 0;
             }
@@ -322,10 +324,12 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     // The fast loop (16 symbols at a go, no per-symbol length test, 16-byte stores) runs as far as every block of the
     // wave has whole groups of 16 and its output is 16-byte aligned; the rest -- the ragged end of a buffer's last
     // block, the whole wave if an output is unaligned -- is decoded symbol by symbol behind it.
+    // The item geometry keeps the fast loop whatever the outputs' alignment (an item begins where the one before it
+    // ends): all quads stay at the same symbol index, and the 16-byte stores go to byte addresses (rcx_store16).
     u32 fast_end;
     {
         u32 mine = live ? (len & ~15u) : 0xFFFFFFF0u; // (a quad without a block sets no limit)
-        if (live && (reinterpret_cast<uintptr_t>(out) & 15u) != 0) mine = 0;
+        if (!G::items && live && (reinterpret_cast<uintptr_t>(out) & 15u) != 0) mine = 0;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const u32 other = (u32)__shfl_xor((int)mine, o, 64);
@@ -528,12 +532,12 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
             in.topup();
             const u32 g = (i0 >> 4) & 3u;
             if (g == 0 && i0 != 0 && leader) {
-                U4* o4 = reinterpret_cast<U4*>(out + (i0 - 64));
+                u8* o4 = out + (i0 - 64);
                 const U4 p0 = parked[0], p1 = parked[1], p2 = parked[2];
-                o4[0] = p0;
-                o4[1] = p1;
-                o4[2] = p2;
-                o4[3] = o_last;
+                rcx_store16<G::items>(o4, p0);
+                rcx_store16<G::items>(o4 + 16, p1);
+                rcx_store16<G::items>(o4 + 32, p2);
+                rcx_store16<G::items>(o4 + 48, o_last);
             }
             u32 w0_ = 0, w1_ = 0, w2_ = 0, w3_ = 0;
             const u32 sh_ = 31u - (u32)__builtin_clz(256u + i0); // floor(log2(total)), the group's shift
@@ -582,11 +586,11 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #endif
         if (leader && fast_end != 0) { // what is still parked: the last 16..64 bytes of the fast region
             const u32 groups = ((fast_end - 1) >> 4 & 3u) + 1;
-            U4* o4 = reinterpret_cast<U4*>(out + ((fast_end - 1) & ~63u));
-            o4[0] = parked[0];
-            if (groups > 1) o4[1] = parked[1];
-            if (groups > 2) o4[2] = parked[2];
-            if (groups > 3) o4[3] = o_last;
+            u8* o4 = out + ((fast_end - 1) & ~63u);
+            rcx_store16<G::items>(o4, parked[0]);
+            if (groups > 1) rcx_store16<G::items>(o4 + 16, parked[1]);
+            if (groups > 2) rcx_store16<G::items>(o4 + 32, parked[2]);
+            if (groups > 3) rcx_store16<G::items>(o4 + 48, o_last);
         }
     }
     {
@@ -631,7 +635,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     // lane's U4 -- the total, 256 + the symbols decoded (cpprcoder.h:1096, :1138) -- then falls short.
     // A marked block is judged (truncated or not) by the kernel that decodes it again.
     const bool marked = live && rcx_quad_or(j == 3 && U4_ != 256u + len ? 1u : 0u) != 0;
-    if (leader && !marked && in.taken() > stream_len) rcx_flag(status, RCX_ST_CORRUPT, blk);
+    if (leader && !marked && in.taken() > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
     if (leader) redo[blk] = marked ? 1u : 0u;
     else if (j == 0 && in_use && blk < nblocks) redo[blk] = 0;
 }
@@ -1098,10 +1102,11 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
 #endif
 }
 
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks,
                                                                 u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes,
                                                                 const DivEntry* __restrict__ divtab, u32* status,
-                                                                u32* __restrict__ redo, u32 lanes_used)
+                                                                u32* __restrict__ redo, u32 lanes_used, const G g = G())
 {
     __shared__ U4 lds[RCX_MC5_LDS_U4];
     const u32 lane = threadIdx.x & 63u;
@@ -1111,8 +1116,9 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     const bool in_use = lane < lanes_used;
     const u64 blk = in_use ? (u64)blockIdx.x * lanes_used + lane : nblocks;
     const bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
 
     Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
     DivEntry* stage = reinterpret_cast<DivEntry*>(lds + RCX_GROUPS * RCX_LANES);
@@ -1125,7 +1131,15 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     u32* out_drained = out_pos + RCX_LANES;    // drain -> writer's finish: bytes stored so far
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = __all(!in_use || (live && len == block)) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    bool full;
+    if constexpr (G::items) {
+        // Items: the FULL pipeline (16-byte loads, no per-symbol length test) where every entry of the workgroup has the
+        // same length, a multiple of 16, at an aligned address -- a batch of equal items is then coded as its blocks
+        // would be.  (A lane without an entry reads the launch's first entry along, which is at least as long: rcx_where.)
+        full = __all((!in_use || (live && len == maxlen)) && ((reinterpret_cast<uintptr_t>(src) + at) & 15u) == 0) && (maxlen % 16u == 0);
+    } else {
+        full = __all(!in_use || (live && len == block)) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    }
     const u8* in = src + at; // (a lane without a block reads the first block along)
     const u32 nchunks = (maxlen + RCX_MC_CHUNK - 1) / RCX_MC_CHUNK;
 
@@ -1175,7 +1189,7 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
         enc.low = final_low[lane];
         const u32 bytes = enc.finish();
         sizes[blk] = enc.overflow ? (u32)slot : bytes;
-        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
         redo[blk] = (wr.redo != 0 && !enc.overflow) ? 1u : 0u;
     } else if (wave == 1 && blk < nblocks) {
         redo[blk] = 0;

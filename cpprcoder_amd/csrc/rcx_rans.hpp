@@ -170,17 +170,18 @@ __device__ __forceinline__ void rcx_rans_write_header_ent(u8* at, u32 n, const u
 // Encode, pass 1: every block's stream ends at the end of its slot; sizes[b] = its length, starts[b] = where it
 // begins in the slot.  WORD = the eight-state format.
 // ===========================================================================
-template <bool WORD>
+template <bool WORD, class G = RcxBlocks>
 __global__ __launch_bounds__(256) void rcx_enc_rans_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks, u8* __restrict__ slots,
-                                                      u64 slot, u32* __restrict__ sizes, u32* __restrict__ starts, u32* status)
+                                                      u64 slot, u32* __restrict__ sizes, u32* __restrict__ starts, u32* status, const G g = G())
 {
     __shared__ __attribute__((aligned(16))) u32 lds_all[4 * RCX_RANS_BLOCKS * RCX_RANS_ENC_LDS_DW];
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * 4 + wave) * RCX_RANS_BLOCKS + oct;
     const bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     u32* cum = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_RANS_ENC_LDS_DW;
     u32* table = cum + 264;
     u8* stage = reinterpret_cast<u8*>(table + 256);
@@ -384,7 +385,7 @@ __global__ __launch_bounds__(256) void rcx_enc_rans_k(const u8* __restrict__ src
     if (j == 0) {
         sizes[blk] = overflow ? 0u : (u32)slot - ptr;
         starts[blk] = overflow ? 0u : ptr;
-        if (overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
     }
 }
 
@@ -411,17 +412,18 @@ __device__ __forceinline__ u32 rcx_load_le32(const u8* p) { return (u32)p[0] | (
 #define RCX_R8_RING_BYTES 256
 #define RCX_R8_LDS_BYTES (RCX_R8_FIRST_BYTES + 4 * RCX_R8_TABLE_DW + RCX_R8_RING_BYTES + 64)
 
-template <int WAVES>
+template <int WAVES, class G = RcxBlocks>
 __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets,
-                                                             u64 nblocks, u32 block, u64 n, u8* __restrict__ dst, u32* status)
+                                                             u64 nblocks, u32 block, u64 n, u8* __restrict__ dst, u32* status, const G g = G())
 {
     __shared__ __attribute__((aligned(16))) u8 lds_all[WAVES * RCX_RANS_BLOCKS * RCX_R8_LDS_BYTES];
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * WAVES + wave) * RCX_RANS_BLOCKS + oct;
     bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
+    u64 at = live ? blk * (u64)block : 0;
     u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     u8* mine = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_R8_LDS_BYTES;
     u8* first = mine;
     u32* table = reinterpret_cast<u32*>(mine + RCX_R8_FIRST_BYTES);
@@ -431,7 +433,8 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
     const u8* s = comp;
     u64 stream_len = 0;
     if (live) {
-        const u64 s0 = offsets[blk], s1 = offsets[blk + 1];
+        const u64 sidx = rcx_stream_of(g, blk);
+        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
         stream_len = s1 - s0;
         s = comp + s0;
         bool good = s1 >= s0 && s1 <= comp_size && stream_len >= RCX_RANS_HEADER + 32;
@@ -473,7 +476,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
             if (mine_count != 0 && rank == total) table[total] = table[total + 1] = table[total + 2] = last_entry;
         }
         if (!good) {
-            if (j == 0) rcx_flag(status, RCX_ST_CORRUPT, blk);
+            if (j == 0) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
             live = false;
             len = 0;
         }
@@ -638,7 +641,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
             out[8 * groups + j] = (u8)(e >> 24);
         }
         // a valid stream holds every word that was taken (cppans.h:479-481 reads on regardless)
-        if (j == 0 && (u64)(words - s) + (p - (u32)(words - origin)) > stream_len) rcx_flag(status, RCX_ST_CORRUPT, blk);
+        if (j == 0 && (u64)(words - s) + (p - (u32)(words - origin)) > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
     }
 }
 
@@ -654,16 +657,17 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
 // ===========================================================================
 #define RCX_RANS_MODEL_DW 776 /* per block in `models`: cum[257] (+ pad to 264) | 256 x {reciprocal, packed} for rcx_enc_rans1_k */
 
-template <u32 PROB_BITS>
-__global__ __launch_bounds__(256) void rcx_rans_model_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks, u32* __restrict__ models)
+template <u32 PROB_BITS, class G = RcxBlocks>
+__global__ __launch_bounds__(256) void rcx_rans_model_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks, u32* __restrict__ models, const G g = G())
 {
     __shared__ u32 lds_all[4 * RCX_RANS_BLOCKS * RCX_RANS_ENC_LDS_DW];
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * 4 + wave) * RCX_RANS_BLOCKS + oct;
     if (blk >= nblocks) return; // (an octet leaves together)
-    const u64 at = blk * (u64)block;
-    const u32 len = (u32)((n - at) < (u64)block ? (n - at) : (u64)block);
+    u64 at = blk * (u64)block;
+    u32 len = (u32)((n - at) < (u64)block ? (n - at) : (u64)block);
+    if constexpr (G::items) rcx_where(g, true, blk, at, len);
     u32* cum = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_RANS_ENC_LDS_DW;
     u32* table = cum + 264;
     const u8* in = src + at;
@@ -696,10 +700,11 @@ struct alignas(8) RcxRansSym {
 };
 // A workgroup is four independent waves (they land one on each SIMD of a CU; single-wave workgroups cluster).
 #define RCX_RANS1_ENC_WAVES 4
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(64 * RCX_RANS1_ENC_WAVES) void rcx_enc_rans1_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks,
                                                                            const u32* __restrict__ models, u8* __restrict__ slots, u64 slot,
                                                                            u32* __restrict__ sizes, u32* __restrict__ starts, u32* status,
-                                                                           u32 lanes_shift)
+                                                                           u32 lanes_shift, const G g = G())
 {
     extern __shared__ RcxRansSym rcx_rans1_lds[];
     const u32 lanes_used = 1u << lanes_shift;
@@ -707,8 +712,9 @@ __global__ __launch_bounds__(64 * RCX_RANS1_ENC_WAVES) void rcx_enc_rans1_k(cons
     const bool in_use = lane < lanes_used;
     const u64 blk = in_use ? ((u64)blockIdx.x * RCX_RANS1_ENC_WAVES + wave) * lanes_used + lane : nblocks;
     const bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     RcxRansSym* table = rcx_rans1_lds + wave * 256u * lanes_used + (in_use ? lane : 0u);
     if (live) {
         const RcxRansSym* m = reinterpret_cast<const RcxRansSym*>(models + blk * RCX_RANS_MODEL_DW + 264);
@@ -792,7 +798,7 @@ __global__ __launch_bounds__(64 * RCX_RANS1_ENC_WAVES) void rcx_enc_rans1_k(cons
         }
         sizes[blk] = overflow ? 0u : (u32)slot - ptr;
         starts[blk] = overflow ? 0u : ptr;
-        if (overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
     }
 #undef RCX_RANS1_PUT
 }
@@ -905,9 +911,10 @@ __device__ __forceinline__ void rcx_rans1w_pipeline(u32 wave, u32 lane, bool liv
     }
 }
 
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks, const u32* __restrict__ models,
                                                         u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes, u32* __restrict__ starts,
-                                                        u32* status)
+                                                        u32* status, const G g = G())
 {
     extern __shared__ __attribute__((aligned(16))) u8 rcx_r1w_lds[];
     RcxRansSym* table_all = reinterpret_cast<RcxRansSym*>(rcx_r1w_lds);
@@ -918,8 +925,9 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const u64 blk = (u64)blockIdx.x * 64u + lane;
     const bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     const u8* in = src + at;
     RcxRansSym* table = table_all + lane; // entry s at table[64 s]
     if (live) {
@@ -927,7 +935,7 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
         for (u32 sy = wave; sy < 256; sy += 2) table[sy * 64u] = m[sy];
     }
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
     const u32 nchunks = (maxlen + RCX_R1W_CHUNK - 1) / RCX_R1W_CHUNK;
     rcx_lds_barrier();
 
@@ -957,17 +965,17 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
         }
         sizes[blk] = overflow ? 0u : (u32)slot - ptr;
         starts[blk] = overflow ? 0u : ptr;
-        if (overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
     }
 }
 
 // Decode, 4 lanes per block.  LDS per wave: four table groups (rcx_oct.hpp: node n of the four blocks of a group in
 // the four quarters of a 256-byte row) | sixteen input rings.  Node n of a block = its cumulative bounds
 // cum[16n+1 .. 16n+16]; lane j keeps cum[16(4j+1)] .. cum[16(4j+4)] in registers.
-template <int WAVES>
+template <int WAVES, class G = RcxBlocks>
 __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets,
                                                                   u64 nblocks, u32 block, u64 n, u8* __restrict__ dst, u32* status,
-                                                                  u32 quads_used, u32* track)
+                                                                  u32 quads_used, u32* track, const G g = G())
 {
     __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_SQUAD_LDS_BYTES];
     const u32 lane = threadIdx.x & 63u;
@@ -977,8 +985,9 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
     const bool in_use = quad < quads_used; // see rcx_dec_quad_k: the other quads decode along and store nothing
     const u64 blk = ((u64)blockIdx.x * WAVES + wave_in_wg) * quads_used + (quad & (quads_used - 1u));
     bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
+    u64 at = live ? blk * (u64)block : 0;
     u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     const u32 group = 2u * (quad >> 3) + ((0x96u >> (quad & 7u)) & 1u), quarter = (quad & 7u) >> 1;
     u8* mine = lds + group * RCX_QUAD_GROUP_BYTES + quarter * 64;
     U4* leaves = reinterpret_cast<U4*>(mine) + j;
@@ -989,7 +998,8 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
     u64 stream_len = 0;
     u32 U1 = 1, U2 = 2, U3 = 3, U4_ = 16384;
     if (live) {
-        const u64 s0 = offsets[blk], s1 = offsets[blk + 1];
+        const u64 sidx = rcx_stream_of(g, blk);
+        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
         stream_len = s1 - s0;
         const u8* s = comp + s0;
         bool good = s1 >= s0 && s1 <= comp_size && stream_len >= RCX_RANS_HEADER + 4;
@@ -1018,7 +1028,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
             // 1032) is what it reads big-endian into `low`
             in.begin(s + RCX_RANS_HEADER - 4, comp + s1, block_ring, scratch + 3);
         } else {
-            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, blk);
+            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
             live = false;
             len = 0;
         }
@@ -1032,7 +1042,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
     }
     u32 x = live ? rcx_bswap(in.low) : (1u << 23); // cppans.h:303-310
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
     u8* out = dst + at;
     const bool leader = live && in_use && j == 0;
     const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(leaves);
@@ -1168,7 +1178,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
 #undef RCX_QP2
     // a valid stream holds every byte that was taken
     const u64 taken = RCX_RANS_HEADER - 4 + in.taken(); // QuadInput counts from 8 bytes into what it was given
-    if (leader && taken > stream_len) rcx_flag(status, RCX_ST_CORRUPT, blk);
+    if (leader && taken > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
     // the single-stream call wants what rANS::decode returns: the payload bytes consumed (cppans.h:562)
     if (track && leader && blk == 0) track[0] = (u32)(taken - RCX_RANS_HEADER);
 }

@@ -95,9 +95,10 @@ __device__ __forceinline__ u32 rcx_static_max_count(const StaticTable& tab)
 // ===========================================================================
 // Static encode, pass 1 (scan + scatter are shared with the adaptive coder)
 // ===========================================================================
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(64) void rcx_enc_static_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks,
                                                        u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes, u32* status,
-                                                       const u32* __restrict__ only)
+                                                       const u32* __restrict__ only, const G g = G())
 {
     __shared__ u32 lds[RCX_STATIC_LDS_DW];
     const u32 lane = threadIdx.x;
@@ -108,15 +109,16 @@ __global__ __launch_bounds__(64) void rcx_enc_static_k(const u8* __restrict__ sr
         live = live && only[blk] != 0;
         if (!__any(live)) return;
     }
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
 
     // ---- count(), cpprcoder.h:543-571 ----
     for (u32 i = 0; i <= 256; ++i) tab.set(i, 0);
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
     // A count can only be 0xFFFF before its increment once 65535 earlier symbols exist, so the squeeze
     // test is not needed for the first 65535 symbols of a block.
     const u32 easy = maxlen < 65535u ? maxlen : 65535u;
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(64) void rcx_enc_static_k(const u8* __restrict__ sr
         if (enc.low == 0xFFFFFFFFu) enc.acc += 1; // cpprcoder.h:439-443: bump the held byte, pending 0xFF -> 0x00
         const u32 bytes = enc.finish() + (RCX_STATIC_HEADER - 4);
         sizes[blk] = enc.overflow ? (u32)slot : bytes;
-        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
     }
 }
 
@@ -317,9 +319,10 @@ __device__ __forceinline__ void rcx_static3_pipeline(u32 wave, u32 lane, u32 len
     }
 }
 
+template <class G = RcxBlocks>
 __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks,
                                                                     u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes,
-                                                                    u32* status, u32* __restrict__ redo, u32 lanes_used)
+                                                                    u32* status, u32* __restrict__ redo, u32 lanes_used, const G g = G())
 {
     __shared__ __attribute__((aligned(16))) u32 lds[RCX_ST3_LDS_DW];
     const u32 lane = threadIdx.x & 63u;
@@ -327,8 +330,9 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     const bool in_use = lane < lanes_used; // see rcx_enc_mc5_k
     const u64 blk = in_use ? (u64)blockIdx.x * lanes_used + lane : nblocks;
     const bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
-    const u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    u64 at = live ? blk * (u64)block : 0;
+    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
     U4* ring = reinterpret_cast<U4*>(lds + RCX_STATIC_LDS_DW); // 16-byte aligned: RCX_STATIC_LDS_DW = 257 * 64 dwords
@@ -340,7 +344,7 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     u32* out_drained = out_pos + RCX_LANES;
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = __all(!in_use || (live && len == block)) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool full = !G::items && __all(!in_use || (live && len == block)) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
     const u32 nchunks = (maxlen + RCX_MC_CHUNK - 1) / RCX_MC_CHUNK;
 
     // ---- count(), cpprcoder.h:543-571 ----
@@ -444,7 +448,7 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
         if (enc.low == 0xFFFFFFFFu) enc.acc += 1; // cpprcoder.h:439-443
         const u32 bytes = enc.finish() + (RCX_STATIC_HEADER - 4);
         sizes[blk] = enc.overflow ? (u32)slot : bytes;
-        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, blk);
+        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
         redo[blk] = (wr.redo != 0 && !enc.overflow) ? 1u : 0u;
     } else if (wave == 1 && blk < nblocks) {
         redo[blk] = 0;
@@ -456,10 +460,10 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
 // ===========================================================================
 // STREAM = the single-stream entry point: one block whose symbol count n the host took from the header;
 // track[0] = first symbol whose renormalisation ran out of input (cpprcoder.h:506-509), or 0xFFFFFFFF.
-template <bool STREAM>
+template <bool STREAM, class G = RcxBlocks>
 __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets, u64 nblocks,
                                                        u32 block, u64 n, u8* __restrict__ dst, u32* status, u32* track,
-                                                       const u32* __restrict__ only)
+                                                       const u32* __restrict__ only, const G g = G())
 {
     __shared__ u32 lds[RCX_STATIC_LDS_DW + RCX_RING_DW * RCX_LANES];
     const u32 lane = threadIdx.x;
@@ -470,8 +474,9 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
         live = live && only[blk] != 0;
         if (!__any(live)) return;
     }
-    const u64 at = live ? blk * (u64)block : 0;
+    u64 at = live ? blk * (u64)block : 0;
     u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
     StaticTable tab{lds + lane};
     u32* ring_col = lds + RCX_STATIC_LDS_DW + lane;
 
@@ -480,7 +485,8 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     u32 total = 1;
     for (u32 i = 0; i <= 256; ++i) tab.set(i, 0);
     if (live) {
-        const u64 s0 = offsets[blk], s1 = offsets[blk + 1];
+        const u64 sidx = rcx_stream_of(g, blk);
+        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
         stream_len = s1 - s0;
         const u8* s = comp + s0;
         // cpprcoder.h:474-493: at least the header, one more byte, then 5 bytes for the lead-in and low
@@ -502,7 +508,7 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
             dec.low = ((u32)h[4] << 24) | ((u32)h[5] << 16) | ((u32)h[6] << 8) | (u32)h[7];
             dec.range = 0xFFFFFFFFu;
         } else {
-            if (!STREAM) rcx_flag(status, RCX_ST_CORRUPT, blk);
+            if (!STREAM) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
             live = false;
             len = 0;
         }
@@ -518,7 +524,7 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     for (u32 q = 0; q < 15; ++q) coarse[q] = tab.get(16 * (q + 1));
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = !G::items && !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
     u8* out = dst + at;
     bool bad = false;
     u32 short_at = 0xFFFFFFFFu;
@@ -587,7 +593,7 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     if (STREAM) {
         if (lane == 0) track[0] = live ? short_at : 0u;
     } else if (live && (bad || dec.taken() + (RCX_STATIC_HEADER - 3) > stream_len)) {
-        rcx_flag(status, RCX_ST_CORRUPT, blk);
+        rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
     }
 }
 
@@ -607,10 +613,10 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
 // `redo` and decoded by rcx_dec_static_k, which reports it the way the reference fails.
 // ===========================================================================
 #define RCX_SQUAD_LDS_BYTES (4 * RCX_QUAD_GROUP_BYTES + RCX_QUAD_BLOCKS * RCX_QUAD_RING_BYTES)
-template <int WAVES>
+template <int WAVES, class G = RcxBlocks>
 __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets,
                                                                     u64 nblocks, u32 block, u64 n, u8* __restrict__ dst,
-                                                                    u32* status, u32* __restrict__ redo, u32 quads_used)
+                                                                    u32* status, u32* __restrict__ redo, u32 quads_used, const G g = G())
 {
     __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_SQUAD_LDS_BYTES];
     const u32 lane = threadIdx.x & 63u;
@@ -620,8 +626,9 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
     const bool in_use = quad < quads_used; // see rcx_dec_quad_k: the other quads decode along and store nothing
     const u64 blk = ((u64)blockIdx.x * WAVES + wave_in_wg) * quads_used + (quad & (quads_used - 1u));
     bool live = blk < nblocks;
-    const u64 at = live ? blk * (u64)block : 0;
+    u64 at = live ? blk * (u64)block : 0;
     u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
+    if constexpr (G::items) rcx_where(g, live, blk, at, len);
 
     const u32 group = 2u * (quad >> 3) + ((0x96u >> (quad & 7u)) & 1u), quarter = (quad & 7u) >> 1; // see rcx_dec_quad_k
     u8* mine = lds + group * RCX_QUAD_GROUP_BYTES + quarter * 64;
@@ -633,7 +640,8 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
     u64 stream_len = 0;
     u32 U1 = 1, U2 = 2, U3 = 3, U4_ = 4, total = 4;
     if (live) {
-        const u64 s0 = offsets[blk], s1 = offsets[blk + 1];
+        const u64 sidx = rcx_stream_of(g, blk);
+        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
         stream_len = s1 - s0;
         const u8* s = comp + s0;
         // cpprcoder.h:474-493: at least the header, one more byte, then 5 bytes for the lead-in and low
@@ -666,7 +674,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
             in.begin(s + RCX_STATIC_HEADER - 3, comp + s1, block_ring, parked + 3);
             in.range = 0xFFFFFFFFu;
         } else {
-            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, blk);
+            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
             live = false;
             len = 0;
         }
@@ -687,7 +695,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
     const u64 kadd = k.add;
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
     u8* out = dst + at;
     const bool leader = live && in_use && j == 0;
     const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(leaves);
@@ -856,7 +864,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
     // the normalisation after the last symbol (it decides whether the input was long enough, cpprcoder.h:506-509)
     in.bp8 += rcx_clz(in.range) & 0x18u;
     const bool marked = live && (worst_node >= 16u || least_range == 0);
-    if (leader && !marked && in.taken() + (RCX_STATIC_HEADER - 3) > stream_len) rcx_flag(status, RCX_ST_CORRUPT, blk);
+    if (leader && !marked && in.taken() + (RCX_STATIC_HEADER - 3) > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
     if (leader) redo[blk] = marked ? 1u : 0u;
     else if (j == 0 && in_use && blk < nblocks) redo[blk] = 0;
 }

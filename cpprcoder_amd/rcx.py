@@ -34,7 +34,10 @@ EXPORTS = (
     "rcx_allgatherv_segments",
     "rcx_bwt_encode_bound", "rcx_bwt_decode_bound", "rcx_bwt_decoded_size", "rcx_bwt_reserve", "rcx_bwt_encode_device",
     "rcx_bwt_decode_device", "rcx_bwt_encode", "rcx_bwt_decode", "rcx_bwt_last_ties",
+    "rcx_encode_items_bound", "rcx_items_plan", "rcx_ctx_scratch_bytes", "rcx_encode_items_device", "rcx_decode_items_device",
+    "rcx_encode_items", "rcx_decode_items",
 )
+ITEM_SCRATCH_BYTES = 3168  # RCX_ITEM_SCRATCH_BYTES
 
 
 class RcxError(RuntimeError):
@@ -115,6 +118,17 @@ def lib() -> C.CDLL:
         for name in ("rcx_bwt_encode", "rcx_bwt_decode"):
             getattr(L, name).restype, getattr(L, name).argtypes = i32, [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.rcx_bwt_last_ties.restype, L.rcx_bwt_last_ties.argtypes = i32, [vp, C.POINTER(u64)]
+        L.rcx_encode_items_bound.restype, L.rcx_encode_items_bound.argtypes = u64, [i32, vp, u64]
+        L.rcx_items_plan.restype, L.rcx_items_plan.argtypes = i32, [i32, vp, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+        L.rcx_ctx_scratch_bytes.restype, L.rcx_ctx_scratch_bytes.argtypes = i32, [vp, C.POINTER(u64)]
+        L.rcx_encode_items_device.restype = i32
+        L.rcx_encode_items_device.argtypes = [vp, i32, vp, vp, u64, vp, u64, vp, vp]
+        L.rcx_decode_items_device.restype = i32
+        L.rcx_decode_items_device.argtypes = [vp, i32, vp, u64, vp, u64, vp, u64, vp, vp, vp]
+        L.rcx_encode_items.restype = i32
+        L.rcx_encode_items.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), vp]
+        L.rcx_decode_items.restype = i32
+        L.rcx_decode_items.argtypes = [vp, i32, vp, u64, vp, u64, vp, u64, vp, vp, u64]
         _lib = L
     return _lib
 
@@ -133,6 +147,29 @@ def block_bound(block: int, coder: int = CODER_ADAPTIVE) -> int:
 
 def encode_bound(n: int, block: int, coder: int = CODER_ADAPTIVE) -> int:
     return int(lib().rcx_encode_bound_for(coder, n, block))
+
+
+def item_offsets(lengths) -> np.ndarray:
+    """lengths -> the table of nitems+1 offsets of items stored back to back (uint64)."""
+    offs = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    np.cumsum(np.asarray(lengths, dtype=np.uint64), out=offs[1:])
+    return offs
+
+
+def encode_items_bound(offsets, coder: int = CODER_ADAPTIVE) -> int:
+    """rcx_encode_items_bound: a destination size that is always enough for these items."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    return int(lib().rcx_encode_items_bound(coder, offs.ctypes.data, len(offs) - 1))
+
+
+def items_plan(offsets, coder: int = CODER_ADAPTIVE):
+    """rcx_items_plan -> (work_order uint32[nwork], scratch_bytes, nclasses): what the host plans for an encode call."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    order = np.zeros(max(len(offs) - 1, 1), dtype=np.uint32)
+    nwork, scratch, ncls = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    _check(lib().rcx_items_plan(coder, offs.ctypes.data, len(offs) - 1, order.ctypes.data, C.byref(nwork), C.byref(scratch), C.byref(ncls)),
+           "rcx_items_plan")
+    return order[: nwork.value], int(scratch.value), int(ncls.value)
 
 
 def bwt_encode_bound(n: int) -> int:
@@ -255,6 +292,72 @@ class Context:
                                      out.ctypes.data, cap, C.byref(size))
         _check(st, "rcx_decode_blocks")
         return out[: size.value]
+
+    # ---- items: buffers of differing sizes, any subset back ------------------------
+    def scratch_bytes(self) -> int:
+        """rcx_ctx_scratch_bytes: device bytes of scratch the context holds now (divisor tables and host staging apart)."""
+        b = C.c_uint64()
+        _check(lib().rcx_ctx_scratch_bytes(self._h, C.byref(b)), "rcx_ctx_scratch_bytes")
+        return int(b.value)
+
+    def encode_items_device(self, src, src_offsets, dst, comp_offsets, coder: int = CODER_ADAPTIVE, stream=None, dst_cap: int | None = None) -> None:
+        """src, dst: uint8 cuda tensors; src_offsets: HOST table of nitems+1 offsets into src; comp_offsets: int64 cuda
+        tensor [nitems+1] (written).  Enqueues only."""
+        offs = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+        if comp_offsets.numel() < len(offs):
+            raise ValueError("comp_offsets needs nitems+1 entries")
+        st = lib().rcx_encode_items_device(self._h, coder, src.data_ptr(), offs.ctypes.data, len(offs) - 1, dst.data_ptr(),
+                                           dst.numel() if dst_cap is None else dst_cap, comp_offsets.data_ptr(), self._stream_handle(stream))
+        _check(st, "rcx_encode_items_device")
+
+    def decode_items_device(self, comp, comp_size: int, comp_offsets, dst_offsets, out, pick=None, coder: int = CODER_ADAPTIVE,
+                            stream=None) -> None:
+        """comp: uint8 cuda tensor, comp_offsets: int64 cuda tensor [nstreams+1]; stream pick[k] (k if pick is None) goes to
+        out[dst_offsets[k] : dst_offsets[k+1]]; pick and dst_offsets are HOST arrays.  Enqueues only."""
+        doffs = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        p = None if pick is None else np.ascontiguousarray(pick, dtype=np.uint64)
+        if p is not None and len(p) != len(doffs) - 1:
+            raise ValueError("dst_offsets needs npick+1 entries")
+        st = lib().rcx_decode_items_device(self._h, coder, comp.data_ptr(), comp_size, comp_offsets.data_ptr(), comp_offsets.numel() - 1,
+                                           None if p is None else p.ctypes.data, len(doffs) - 1, doffs.ctypes.data, out.data_ptr(),
+                                           self._stream_handle(stream))
+        _check(st, "rcx_decode_items_device")
+
+    def encode_items(self, items, lengths=None, coder: int = CODER_ADAPTIVE):
+        """items: a list of buffers, or one buffer with `lengths` cutting it -> (payload uint8[total], comp_offsets uint64[nitems+1])."""
+        if lengths is None:
+            parts = [_np_u8(x) for x in items]
+            lengths = [len(x) for x in parts]
+            src = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        else:
+            src = _np_u8(items)
+        offs = item_offsets(lengths)
+        if int(offs[-1]) != len(src):
+            raise ValueError("lengths do not add up to the buffer")
+        dst = np.empty(max(encode_items_bound(offs, coder), 1), dtype=np.uint8)
+        comp_offsets = np.zeros(len(offs), dtype=np.uint64)
+        size = C.c_uint64()
+        st = lib().rcx_encode_items(self._h, coder, src.ctypes.data, offs.ctypes.data, len(offs) - 1, dst.ctypes.data, len(dst), C.byref(size),
+                                    comp_offsets.ctypes.data)
+        _check(st, "rcx_encode_items")
+        return dst[: size.value], comp_offsets
+
+    def decode_items(self, payload, comp_offsets, lengths, pick=None, coder: int = CODER_ADAPTIVE) -> list:
+        """lengths: the decoded length of EVERY stream of the set; -> the list of the picked items' bytes (all, if pick is None)."""
+        comp = _np_u8(payload)
+        coffs = np.ascontiguousarray(comp_offsets, dtype=np.uint64)
+        lengths = np.asarray(lengths, dtype=np.uint64)
+        if len(lengths) != len(coffs) - 1:
+            raise ValueError("one length per stream")
+        p = None if pick is None else np.ascontiguousarray(pick, dtype=np.uint64)
+        if p is not None and len(p) and int(p.max()) >= len(lengths):
+            raise RcxError(E_ARG, "decode_items: pick")
+        doffs = item_offsets(lengths if p is None else lengths[p.astype(np.int64)])
+        out = np.empty(max(int(doffs[-1]), 1), dtype=np.uint8)
+        st = lib().rcx_decode_items(self._h, coder, comp.ctypes.data, len(comp), coffs.ctypes.data, len(coffs) - 1,
+                                    None if p is None else p.ctypes.data, len(doffs) - 1, doffs.ctypes.data, out.ctypes.data, int(doffs[-1]))
+        _check(st, "rcx_decode_items")
+        return [out[int(doffs[k]): int(doffs[k + 1])] for k in range(len(doffs) - 1)]
 
     # ---- block sort (blksort.h) ----------------------------------------------
     def bwt_encode(self, data) -> np.ndarray:

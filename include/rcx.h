@@ -165,6 +165,62 @@ int rcx_decode_blocks(rcx_ctx* ctx, int coder, const uint8_t* comp, uint64_t com
                       uint8_t* dst, uint64_t dst_cap, uint64_t* dst_size);
 
 /*
+ * Item calls: many independent buffers of differing sizes in one call, and any subset of their streams back.
+ * An ITEM is one buffer of 0 .. RCX_MAX_BLOCK bytes, coded by a fresh coder exactly as the reference codes a whole
+ * file of those bytes: item i's stream is byte for byte what rcx_encode_blocks* emits for it as a single block
+ * (initialize(len); encode(len, bytes), or rANS::encode / encode_simd).  An item of length 0 has NO stream: it takes
+ * 0 bytes of the compacted output (comp_offsets[i + 1] == comp_offsets[i]) and decodes to nothing; a pick of length 0
+ * is not looked at.  (The reference's "declares 0, yields one byte" belongs to the single-stream calls below.)
+ *
+ *   rcx_encode_items_device   item i = d_src[src_offsets[i] .. src_offsets[i + 1]); the streams go to d_dst back to back
+ *       in the caller's order, d_comp_offsets[0 .. nitems] (device, written) is their table.
+ *   rcx_decode_items_device   of a compacted set of nstreams streams (d_comp, comp_size, d_comp_offsets[nstreams + 1] on the
+ *       device), stream pick[k] -- k itself if pick is NULL -- is decoded to d_dst[dst_offsets[k] .. dst_offsets[k + 1])
+ *       for k < npick.  Picks may repeat and need not be ordered.
+ *   src_offsets, pick and dst_offsets are HOST arrays: the caller knows the lengths, and the library plans the call from
+ *   them without a synchronisation -- the divisor table for the longest item, the work order (entries sorted by length,
+ *   longest first, so that a wave carries entries of similar length), the layout of the scratch slots -- and sends its
+ *   tables to the device inside the call.  The item calls therefore cannot be captured in a graph.
+ *
+ * What is written and read, as for the block calls: encode writes exactly [d_dst, d_dst + comp_offsets[nitems]) and
+ * d_comp_offsets[0 .. nitems]; decode writes exactly the picked items' output ranges and reads at most 15 bytes past
+ * comp_size, inside the 16-byte aligned piece that holds a stream's last byte.  Pointers and offsets may have any alignment.
+ * The output ranges of one decode call do not overlap: dst_offsets is one non-decreasing table.
+ * RCX_E_ARG, before anything is enqueued: a table that decreases, a length above RCX_MAX_BLOCK, a pick >= nstreams.
+ * RCX_E_CAPACITY / RCX_E_CORRUPT are latched as for the block calls and read with rcx_ctx_sync_status(), whose index is the
+ * item (encode; nitems if only dst_cap was too small) or the pick position k (decode).  A stream whose header disagrees
+ * with its dst_offsets length is corrupt.  A damaged item decodes as if it were alone -- the rules stated above
+ * rcx_decode_blocks_device hold per item -- and every other item of the call is unaffected.
+ *
+ * Scratch.  Scratch slots are sized per length class (the power of two at or above an item's length), not for the
+ * longest item of the call: after an item call a fresh context holds at most
+ *     2 * rcx_encode_items_bound(coder, src_offsets, nitems) + RCX_ITEM_SCRATCH_BYTES * nitems
+ * device bytes, the divisor tables (which depend on the longest item only) and the staging buffers of the host-buffer
+ * calls apart; rcx_ctx_scratch_bytes() reports what a context holds now, counted that way.
+ *   rcx_encode_items_bound   pure: the sum of rcx_block_bound_for(coder, len_i) over the items with len_i > 0 -- a dst_cap that
+ *       is always enough (0 for a bad table)
+ *   rcx_items_plan   pure (diagnostic, tests): what the host plans for an encode call -- work_order[w] (nwork entries, may be
+ *       NULL) = the item of work entry w; *scratch_bytes = what a fresh context will hold; *nclasses = launches of pass 1.
+ *       RCX_ITEMS_ORDER=0 in the environment (diagnostic) keeps the caller's order.
+ * The host-buffer variants copy in, run the device call, synchronise and copy out; comp_offsets may be NULL for encode.
+ */
+#define RCX_ITEM_SCRATCH_BYTES 3168u /* sizes, redo, starts, work tables (36 B) and the one-state rANS model (3104 B) per item */
+uint64_t rcx_encode_items_bound(int coder, const uint64_t* src_offsets, uint64_t nitems);
+int rcx_items_plan(int coder, const uint64_t* src_offsets, uint64_t nitems, uint32_t* work_order, uint64_t* nwork,
+                   uint64_t* scratch_bytes, uint32_t* nclasses);
+int rcx_ctx_scratch_bytes(rcx_ctx* ctx, uint64_t* bytes);
+int rcx_encode_items_device(rcx_ctx* ctx, int coder, const void* d_src, const uint64_t* src_offsets, uint64_t nitems,
+                            void* d_dst, uint64_t dst_cap, uint64_t* d_comp_offsets, void* stream);
+int rcx_decode_items_device(rcx_ctx* ctx, int coder, const void* d_comp, uint64_t comp_size, const uint64_t* d_comp_offsets,
+                            uint64_t nstreams, const uint64_t* pick, uint64_t npick, const uint64_t* dst_offsets,
+                            void* d_dst, void* stream);
+int rcx_encode_items(rcx_ctx* ctx, int coder, const uint8_t* src, const uint64_t* src_offsets, uint64_t nitems,
+                     uint8_t* dst, uint64_t dst_cap, uint64_t* dst_size, uint64_t* comp_offsets);
+int rcx_decode_items(rcx_ctx* ctx, int coder, const uint8_t* comp, uint64_t comp_size, const uint64_t* comp_offsets,
+                     uint64_t nstreams, const uint64_t* pick, uint64_t npick, const uint64_t* dst_offsets,
+                     uint8_t* dst, uint64_t dst_cap);
+
+/*
  * Single-stream calls with the reference's exact stream semantics, used by the
  * C++ facade: one stream of any size 0 .. RCX_MAX_STREAM, coded by one GPU lane.
  *   rcx_stream_encode == initialize(sink, n); encode(n, src)  into a sink that holds

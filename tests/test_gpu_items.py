@@ -1,0 +1,393 @@
+"""The item calls on the GPU (include/rcx.h, "Item calls"): many buffers of differing sizes in one call, any subset
+of their streams back.  Expected bytes always come from the CPU oracle, item by item -- an item's stream is what the
+reference emits for a file of those bytes -- never from the code under test.  Nothing here reads /root/reference.
+"""
+import threading
+
+import numpy as np
+import pytest
+
+from cpprcoder_amd import container, rcx, workloads
+from test_gpu_parity import GUARD, Guarded  # noqa: F401  (the guarded buffers of the block tests)
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+CODERS = (rcx.CODER_ADAPTIVE, rcx.CODER_STATIC, rcx.CODER_RANS, rcx.CODER_RANS8)
+SPECIAL = (1, 2, 15, 16, 17, 63, 64, 65, 1000, 4095, 4096, 4097, 65536, 65537, 200_000)
+HEAD = {0: 5, 1: 516, 2: 1032, 3: 1032}  # bytes in front of the coded payload
+LOW = {0: (5, 9), 1: (516, 521)}          # the bytes the range decoders' first renormalisation shifts in
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    c = rcx.Context(0)
+    yield c
+    c.close()
+
+
+_POOLS = {}
+
+
+def pool(name, n):
+    """At least n bytes of a workload (made once, items are slices of it)."""
+    if name not in _POOLS or len(_POOLS[name]) < n:
+        _POOLS[name] = workloads.by_name(name, max(n, 1 << 22), 77)
+    return _POOLS[name]
+
+
+def make_items(lengths):
+    """Content rotates over zipf / uniform / canterbury; every item is its own slice of its workload."""
+    names = ("zipf", "uniform", "canterbury")
+    need = [0, 0, 0]
+    for i, n in enumerate(lengths):
+        need[i % 3] += int(n)
+    pools = [pool(names[k], need[k]) for k in range(3)]
+    at = [0, 0, 0]
+    items = []
+    for i, n in enumerate(lengths):
+        k = i % 3
+        items.append(pools[k][at[k]: at[k] + int(n)])
+        at[k] += int(n)
+    return items
+
+
+def oracle_streams(oracle, items, coder, threads=16):
+    """The reference's stream of every item on its own (None for an item of length 0, which has no stream)."""
+    out = [None] * len(items)
+
+    def work(first):
+        for i in range(first, len(items), threads):
+            if len(items[i]):
+                slots, sizes = oracle.encode_blocks(items[i], len(items[i]), coder=coder)
+                out[i] = slots[0, : int(sizes[0])].copy()
+
+    pool_ = [threading.Thread(target=work, args=(t,)) for t in range(threads)]
+    for t in pool_:
+        t.start()
+    for t in pool_:
+        t.join()
+    return out
+
+
+def compact(streams):
+    sizes = np.array([0 if s is None else len(s) for s in streams], np.uint64)
+    offs = np.zeros(len(streams) + 1, np.uint64)
+    np.cumsum(sizes, out=offs[1:])
+    parts = [s for s in streams if s is not None]
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), offs
+
+
+def encode_items(ctx, items, coder, src_offset=0, dst_offset=0, invert=False):
+    """Through the device call with every buffer guarded -> (payload, comp_offsets): the source is not written, the
+    destination only in [0, comp_offsets[nitems]), the table only in its nitems + 1 entries."""
+    lengths = [len(x) for x in items]
+    soffs = rcx.item_offsets(lengths)
+    data = np.concatenate(items) if items else np.zeros(0, np.uint8)
+    src = Guarded(len(data), src_offset, data, salt=1, invert=invert)
+    dst = Guarded(rcx.encode_items_bound(soffs, coder), dst_offset, salt=2, invert=invert)
+    offs = Guarded(8 * len(soffs), 0, salt=3, invert=invert)
+    ctx.encode_items_device(src.view, soffs, dst.view, offs.view.view(torch.int64), coder=coder)
+    ctx.sync_status()
+    table = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
+    src.check(0, "encode src")
+    offs.check(8 * len(soffs), "encode table")
+    dst.check(int(table[-1]), "encode dst")
+    return dst.view[: int(table[-1])].cpu().numpy(), table
+
+
+def decode_items(ctx, payload, comp_offsets, lengths, coder, pick=None, comp_offset=0, dst_offset=0, invert=False):
+    """Through the device call, guarded -> (list of the picked items' bytes, status, first bad index).  `lengths` are the
+    decoded lengths of the picks."""
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
+    table = np.ascontiguousarray(np.asarray(comp_offsets).astype(np.int64))
+    offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
+    doffs = rcx.item_offsets(lengths)
+    n = int(doffs[-1])
+    out = Guarded(n, dst_offset, salt=6, invert=invert)
+    ctx.decode_items_device(comp.view, len(payload), offs.view.view(torch.int64), doffs, out.view, pick=pick, coder=coder)
+    st, bad = ctx.sync_status(raise_on_error=False)
+    comp.check(0, "decode comp")
+    offs.check(0, "decode table")
+    out.check(n, "decode dst")
+    flat = out.view.cpu().numpy()
+    return [flat[int(doffs[k]): int(doffs[k + 1])] for k in range(len(lengths))], st, bad
+
+
+def ragged_lengths(seed, count=2200):
+    rs = np.random.RandomState(seed)
+    fill = np.exp(rs.uniform(0, np.log(60_000), count - 4 * len(SPECIAL) - 40)).astype(np.int64)
+    lengths = np.concatenate([np.repeat(SPECIAL, 4), np.zeros(40, np.int64), fill])
+    rs.shuffle(lengths)
+    return lengths
+
+
+_BATCH = {}
+
+
+def ragged_batch(oracle, coder):
+    """The seeded ragged batch and the oracle's streams for it (made once per coder)."""
+    if coder not in _BATCH:
+        items = make_items(ragged_lengths(2024))
+        _BATCH[coder] = (items, oracle_streams(oracle, items, coder))
+    return _BATCH[coder]
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_ragged_parity(ctx, oracle, coder):
+    """2200 items: every special length four times, 40 empty ones, log-uniform fill; comp_offsets and every stream equal
+    the oracle's, and the round trip returns the items."""
+    items, want = ragged_batch(oracle, coder)
+    assert len(items) >= 2000 and sum(1 for x in items if len(x) == 0) >= 40
+    payload, offs = encode_items(ctx, items, coder, src_offset=3, dst_offset=5)
+    want_payload, want_offs = compact(want)
+    assert np.array_equal(offs, want_offs), "comp_offsets differ from the oracle's sizes"
+    for i, s in enumerate(want):
+        got = payload[int(offs[i]): int(offs[i + 1])]
+        assert len(got) == (0 if s is None else len(s)) and (s is None or np.array_equal(got, s)), f"item {i} ({len(items[i])} bytes) differs"
+    back, st, _ = decode_items(ctx, payload, offs, [len(x) for x in items], coder, comp_offset=1, dst_offset=7)
+    assert st == rcx.OK
+    for i, x in enumerate(items):
+        assert np.array_equal(back[i], x), f"item {i} does not round-trip"
+    if coder in LOW:  # (the range coders' kernels keep the marks; nothing is marked on valid data)
+        assert ctx.last_redo(sum(1 for x in items if len(x))) == 0
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_picks(ctx, oracle, coder):
+    """A shuffled subset, a subset with repeats, a single item, the empty pick: each gives exactly those items' bytes --
+    decoded from the ORACLE's streams, so nothing of the encoder under test is involved."""
+    items, want = ragged_batch(oracle, coder)
+    payload, offs = compact(want)
+    rs = np.random.RandomState(9 + coder)
+    n = len(items)
+    longest = int(np.argmax([len(x) for x in items]))
+    for name, pick in (("shuffled subset", rs.permutation(n)[:700]), ("repeats", np.concatenate([rs.randint(0, n, 300), [longest, longest, 5, 5, 5]])),
+                       ("single", np.array([longest])), ("single short", np.array([int(np.argmin([len(x) or 1 << 30 for x in items]))])),
+                       ("empty", np.zeros(0, np.int64))):
+        got, st, _ = decode_items(ctx, payload, offs, [len(items[int(k)]) for k in pick], coder, pick=pick, dst_offset=int(rs.randint(0, 16)))
+        assert st == rcx.OK, name
+        assert len(got) == len(pick)
+        for k, i in enumerate(pick):
+            assert np.array_equal(got[k], items[int(i)]), (name, k, int(i))
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_bounds_at_every_alignment(ctx, oracle, coder):
+    """Every residue mod 16 of the source start, of the compressed start and of each output start; the buffers are
+    guarded (nothing is written outside the stated ranges) and the pattern around them is inverted for a second run,
+    whose results must be the same (nothing depends on the bytes behind the inputs)."""
+    lengths = [100 + 37 * i for i in range(48)] + [16, 1, 4097, 0, 65, 2000]
+    items = make_items(lengths)
+    want = oracle_streams(oracle, items, coder)
+    want_payload, want_offs = compact(want)
+    starts = set()
+    for r in range(16):
+        for invert in (False, True):
+            payload, offs = encode_items(ctx, items, coder, src_offset=r, dst_offset=(5 * r + 3) % 16, invert=invert)
+            assert np.array_equal(offs, want_offs) and np.array_equal(payload, want_payload), (r, invert)
+            back, st, _ = decode_items(ctx, want_payload, want_offs, lengths, coder, comp_offset=r, dst_offset=(7 * r + 1) % 16, invert=invert)
+            assert st == rcx.OK
+            for i, x in enumerate(items):
+                assert np.array_equal(back[i], x), (r, invert, i)
+        doffs = rcx.item_offsets(lengths)
+        starts |= {(GUARD + (7 * r + 1) % 16 + int(o)) % 16 for o in doffs[:-1]}
+    assert starts == set(range(16))  # (relative to the allocation, which the allocator aligns to 256 and more)
+    # a destination that is too small: RCX_E_CAPACITY, index nitems, and nothing written from d_dst + dst_cap on
+    soffs = rcx.item_offsets(lengths)
+    src = torch.from_numpy(np.concatenate(items)).cuda()
+    cap = int(want_offs[-1]) - 9
+    dst = Guarded(int(want_offs[-1]) + 64, 3, salt=8)
+    table = torch.zeros(len(soffs), dtype=torch.int64, device="cuda")
+    ctx.encode_items_device(src, soffs, dst.view, table, coder=coder, dst_cap=cap)
+    st, bad = ctx.sync_status(raise_on_error=False)
+    assert (st, bad) == (rcx.E_CAPACITY, len(lengths))
+    dst.check(cap, "encode dst beyond dst_cap")
+
+
+def decode_one(oracle, stream, length, coder):
+    """The oracle on one item's stream alone -> (ok, bytes)."""
+    slots = np.zeros((1, len(stream) + 64), np.uint8)
+    slots[0, : len(stream)] = stream
+    out, ok = oracle.decode_blocks(slots, np.array([len(stream)], np.uint32), max(length, 1), length, coder=coder)
+    return ok, out
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_damaged_items(oracle, coder):
+    """One item in the middle of a wave is damaged -- a payload byte, a target past the table (the range coders: the
+    quad kernels mark it and the one-lane kernel decodes it again), a truncation, a falsified header.  The status and the
+    first bad index (the PICK POSITION) follow the rule of the block calls, the damaged item the reference still decodes
+    gets the reference's bytes, and every other item is intact."""
+    rs = np.random.RandomState(100 + coder)
+    lengths = rs.randint(600, 1000, 3000)  # 3000 entries: several per wave of every decoder
+    items = make_items(lengths)
+    good = oracle_streams(oracle, items, coder)
+    pick = rs.permutation(len(items))  # the pick position of an item is not its stream index
+    where = {int(i): k for k, i in enumerate(pick)}
+    order = np.lexsort((np.arange(len(pick)), -lengths[pick]))  # the work order of the picks: by length, then position
+    victim = int(pick[order[len(order) // 2 + 5]])  # an entry in the middle of the work order, not at a wave's edge
+    c = rcx.Context(0)
+    try:
+        kinds = ["payload byte", "truncated", "header"] + (["past the table"] if coder in LOW else [])
+        for kind in kinds:
+            s = good[victim].copy()
+            pad = rs.randint(0, 256, 3 * len(items[victim])).astype(np.uint8)
+            if kind == "payload byte":
+                s[HEAD[coder] + 4 + (len(s) - HEAD[coder] - 4) // 2] ^= 0x5A
+                s = np.concatenate([s, pad])  # (so that the oracle does not run dry on it)
+            elif kind == "past the table":
+                s[LOW[coder][0]: LOW[coder][1]] = 0xFF
+                s = np.concatenate([s, pad])
+            elif kind == "truncated":
+                s = s[: len(s) - 40]
+            else:
+                s[:4] = np.frombuffer(np.uint32(len(items[victim]) + 1).tobytes(), np.uint8)
+            streams = list(good)
+            streams[victim] = s
+            payload, offs = compact(streams)
+            if kind == "header":
+                ok, ref = False, None  # a header that disagrees with dst_offsets is corrupt, whatever the reference makes of it
+            else:
+                ok, ref = decode_one(oracle, s, len(items[victim]), coder)
+            got, st, bad = decode_items(c, payload, offs, lengths[pick], coder, pick=pick, dst_offset=int(rs.randint(0, 16)))
+            if ok:
+                assert st == rcx.OK, (kind, st, bad)
+                assert np.array_equal(got[where[victim]], ref), f"{kind}: not the reference's bytes"
+            else:
+                assert (st, bad) == (rcx.E_CORRUPT, where[victim]), (kind, st, bad, where[victim])
+            if kind == "past the table" and ok:  # (the static coder's fall-through symbol 255 may have count 0: then it is corrupt)
+                assert c.last_redo(len(pick)) == 1, "the marked item goes through the one-lane kernel"
+            for k, i in enumerate(pick):
+                if int(i) != victim:
+                    assert np.array_equal(got[k], items[int(i)]), (kind, k)
+            st, _ = c.sync_status(raise_on_error=False)
+            assert st == rcx.OK  # (the status was cleared)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_items_cut_as_blocks_equal_the_block_calls(ctx, coder):
+    n = (2 << 20) + 777
+    data = workloads.zipf(n, 31)
+    src = torch.from_numpy(data).cuda()
+    for block in (65536, 1000):
+        nblocks = rcx.block_count(n, block)
+        dst = torch.zeros(rcx.encode_bound(n, block, coder), dtype=torch.uint8, device="cuda")
+        offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
+        ctx.encode_blocks_device(src, block, dst, offs, coder=coder)
+        ctx.sync_status()
+        soffs = np.minimum(np.arange(nblocks + 1, dtype=np.uint64) * np.uint64(block), np.uint64(n))
+        dst2 = torch.zeros(rcx.encode_items_bound(soffs, coder), dtype=torch.uint8, device="cuda")
+        offs2 = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
+        ctx.encode_items_device(src, soffs, dst2, offs2, coder=coder)
+        ctx.sync_status()
+        assert torch.equal(offs, offs2), (coder, block)
+        total = int(offs[-1])
+        assert torch.equal(dst[:total], dst2[:total]), (coder, block)
+        out = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        ctx.decode_items_device(dst2, total, offs2, soffs, out, coder=coder)
+        ctx.sync_status()
+        assert torch.equal(out, src)
+
+
+SKEW_SAMPLE_SEED, SKEW_SAMPLE = 4242, 1000
+
+
+@pytest.mark.parametrize("coder", CODERS)
+def test_skewed_batch(oracle, coder):
+    """One item of 4 MiB and 200 000 items of 64 bytes in one call (slots of one stride for all would be about 970 GB).
+    Parity with the oracle on the long item and on a sample of 1000 short ones fixed by seed (SKEW_SAMPLE_SEED: at most
+    199 000 short items are left out of the stream comparison; all of them are in the round trip), the round trip of the
+    whole batch, and the context's scratch within 2 x rcx_encode_items_bound + RCX_ITEM_SCRATCH_BYTES per item."""
+    nshort, long_at = 200_000, 123_456
+    lengths = np.full(nshort + 1, 64, dtype=np.uint64)
+    lengths[long_at] = 4 << 20
+    soffs = rcx.item_offsets(lengths)
+    data = workloads.zipf(int(soffs[-1]), 8)
+    c = rcx.Context(0)  # a fresh context: what it holds afterwards is what this call asked for
+    try:
+        src = torch.from_numpy(data).cuda()
+        bound = rcx.encode_items_bound(soffs, coder)
+        dst = torch.zeros(bound, dtype=torch.uint8, device="cuda")
+        offs = torch.zeros(len(soffs), dtype=torch.int64, device="cuda")
+        c.encode_items_device(src, soffs, dst, offs, coder=coder)
+        c.sync_status()
+        held = c.scratch_bytes()
+        assert 0 < held <= 2 * bound + rcx.ITEM_SCRATCH_BYTES * len(lengths), (held, bound)
+        assert held == rcx.items_plan(soffs, coder)[1]
+        table = offs.cpu().numpy().astype(np.uint64)
+        payload = dst[: int(table[-1])].cpu().numpy()
+        rs = np.random.RandomState(SKEW_SAMPLE_SEED)
+        sample = [long_at] + [int(i) for i in rs.choice(np.delete(np.arange(nshort + 1), long_at), SKEW_SAMPLE, replace=False)]
+        for i in sample:
+            item = data[int(soffs[i]): int(soffs[i + 1])]
+            slots, sizes = oracle.encode_blocks(item, len(item), coder=coder)
+            assert np.array_equal(payload[int(table[i]): int(table[i + 1])], slots[0, : int(sizes[0])]), f"item {i} differs from the oracle"
+        out = torch.zeros(len(data), dtype=torch.uint8, device="cuda")
+        c.decode_items_device(dst, int(table[-1]), offs, soffs, out, coder=coder)
+        c.sync_status()
+        assert torch.equal(out, src)
+        assert c.scratch_bytes() <= 2 * bound + rcx.ITEM_SCRATCH_BYTES * len(lengths)
+    finally:
+        c.close()
+
+
+def test_bad_arguments(ctx):
+    src = torch.zeros(4096, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
+    offs = torch.zeros(8, dtype=torch.int64, device="cuda")
+    for bad in (np.array([0, 100, 50], np.uint64), np.array([0, rcx.MAX_BLOCK + 1], np.uint64)):
+        with pytest.raises(rcx.RcxError) as e:
+            ctx.encode_items_device(src, bad, dst, offs)
+        assert e.value.status == rcx.E_ARG
+    soffs = rcx.item_offsets([100, 0, 200])
+    ctx.encode_items_device(src, soffs, dst, offs)
+    ctx.sync_status()
+    table = offs[:4]
+    for pick, doffs in (([3], [0, 100]), ([0, 1], [0, 100, 50]), ([0], [0, rcx.MAX_BLOCK + 1])):
+        with pytest.raises(rcx.RcxError) as e:
+            ctx.decode_items_device(dst, int(table[-1]), table, np.array(doffs, np.uint64), src, pick=np.array(pick, np.uint64))
+        assert e.value.status == rcx.E_ARG
+    st, _ = ctx.sync_status(raise_on_error=False)
+    assert st == rcx.OK  # nothing was enqueued
+    # no items, and only empty items: a table of zeros, no payload
+    offs.fill_(-1)
+    ctx.encode_items_device(src, rcx.item_offsets([0, 0, 0]), dst, offs)
+    ctx.sync_status()
+    assert offs[:4].tolist() == [0, 0, 0, 0] and int(offs[4]) == -1
+    payload, table = ctx.encode_items([b"", b"abc", b""])
+    assert table[0] == table[1] == 0 and table[2] == table[3] == len(payload) > 0
+    assert [bytes(x) for x in ctx.decode_items(payload, table, [0, 3, 0])] == [b"", b"abc", b""]
+
+
+def test_containers(ctx, oracle):
+    data = workloads.canterbury_concat()[:700_001]
+    for coder, block in ((0, 65536), (1, 4096), (2, 16384), (3, 65536)):
+        blob = container.pack(data, block, coder, ctx)
+        n = len(data)
+        for start, stop in ((0, 0), (0, 1), (0, block), (block, 2 * block), (block - 1, block + 1), (3 * block + 17, 5 * block + 3),
+                            (n - 1, n), (n - block - 5, n), (0, n), (2 * block, 2 * block)):
+            assert container.unpack_range(blob, start, stop, ctx) == data[start:stop].tobytes(), (coder, block, start, stop)
+        with pytest.raises(container.ContainerError):
+            container.unpack_range(blob, 5, n + 1, ctx)
+    with pytest.raises(container.ContainerError):
+        container.unpack_range(container.pack(data[:100_000], 65536, 0, ctx, blksort=True), 0, 10, ctx)
+    items = [bytes(x) for x in make_items([0, 5, 70_000, 1, 0, 4096, 33_333])]
+    for coder in CODERS:
+        blob = container.pack_items(items, coder, ctx)
+        c = container.parse_items(blob)
+        want = oracle_streams(oracle, [np.frombuffer(x, np.uint8) for x in items], coder)
+        for i, s in enumerate(want):
+            got = c["payload"][int(c["offsets"][i]): int(c["offsets"][i + 1])]
+            assert len(got) == (0 if s is None else len(s)) and (s is None or np.array_equal(got, s))
+        assert container.unpack_items(blob, ctx=ctx) == items
+        assert container.unpack_items(blob, pick=[6, 2, 2, 0, 3], ctx=ctx) == [items[6], items[2], items[2], items[0], items[3]]
+        assert container.unpack_items(blob, pick=[], ctx=ctx) == []
+        with pytest.raises(container.ContainerError):
+            container.unpack_items(blob, pick=[7], ctx=ctx)
+    assert container.unpack_items(container.pack_items([], 0, ctx), ctx=ctx) == []
