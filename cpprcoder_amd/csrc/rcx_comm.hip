@@ -13,7 +13,7 @@
 #include <new>
 #include <vector>
 
-#include "../../include/rcx.h"
+#include "rcx_buf.hpp"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -24,17 +24,13 @@ struct rcx_comm {
     int nranks = 1;
     int rank = 0;
     ncclComm_t nccl = nullptr;
-    u64* d_mine = nullptr;   // what this rank brings and has room for: RCX_COMM_WORDS words (rcx_pack_sizes_k)
-    u64* d_every = nullptr;  // the same of every rank
-    u64* h_every = nullptr;  // pinned copy
+    DevBuf<u64> d_mine;      // what this rank brings and has room for: RCX_COMM_WORDS words (rcx_pack_sizes_k)
+    DevBuf<u64> d_every;     // the same of every rank
+    PinBuf<u64> h_every;     // ... and the host's copy
 };
 
 namespace
 {
-#define HIP_TRY(expr)                           \
-    do {                                        \
-        if ((expr) != hipSuccess) return RCX_E_HIP; \
-    } while (0)
 #define NCCL_TRY(expr)                           \
     do {                                         \
         if ((expr) != ncclSuccess) return RCX_E_COMM; \
@@ -110,9 +106,8 @@ int rcx_comm_create(int device, const void* id, int nranks, int rank, rcx_comm**
         rcx_comm_destroy(c);
         return RCX_E_COMM;
     }
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_mine), RCX_COMM_WORDS * sizeof(u64)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_every), RCX_COMM_WORDS * sizeof(u64) * nranks) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->h_every), RCX_COMM_WORDS * sizeof(u64) * nranks, hipHostMallocDefault) != hipSuccess) {
+    if (c->d_mine.reserve(RCX_COMM_WORDS) != RCX_OK || c->d_every.reserve((u64)RCX_COMM_WORDS * nranks) != RCX_OK ||
+        c->h_every.reserve((u64)RCX_COMM_WORDS * nranks) != RCX_OK) {
         rcx_comm_destroy(c);
         return RCX_E_NOMEM;
     }
@@ -125,9 +120,6 @@ void rcx_comm_destroy(rcx_comm* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->nccl) (void)ncclCommDestroy(c->nccl);
-    if (c->d_mine) (void)hipFree(c->d_mine);
-    if (c->d_every) (void)hipFree(c->d_every);
-    if (c->h_every) (void)hipHostFree(c->h_every);
     delete c;
 }
 
@@ -140,7 +132,7 @@ int rcx_allgatherv_segments(rcx_comm* c, const void* d_segment, const uint64_t* 
 {
     if (!c || !d_offsets || !d_concat || (nblocks && !d_segment)) return RCX_E_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError(); // (what an earlier call of this thread left behind is not this call's: see rcx_enter_device in rcx_api.hip)
+    (void)hipGetLastError(); // (what an earlier call of this thread left behind is not this call's: see rcx_enter_device in rcx_ctx.hpp)
     HIP_TRY(hipSetDevice(c->device));
     const int n = c->nranks;
     // 1. what does every rank bring?  (the one host synchronisation of the exchange: send and receive counts are
@@ -194,7 +186,7 @@ int rcx_allgatherv_segments(rcx_comm* c, const void* d_segment, const uint64_t* 
         const bool closed = ncclGroupEnd() == ncclSuccess;
         if (!ok || !closed) return RCX_E_COMM;
     }
-    return hipGetLastError() == hipSuccess ? RCX_OK : RCX_E_HIP;
+    return LAUNCHED();
 }
 
 } // extern "C"

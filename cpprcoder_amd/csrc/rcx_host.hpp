@@ -1,11 +1,12 @@
-// rcx_host.hpp -- the host-buffer entry points of rcx.h as a pipeline (included by rcx_api.hip).
+// rcx_host.hpp -- the host-buffer entry points of rcx.h as a pipeline: what runs a call chunk by chunk (the calls
+// themselves say what a chunk is: rcx_api.hip, rcx_bwt_api.hpp).
 //
 // The reference is driven with host memory on both sides (test/main.cpp:321-350: a file in a malloc'd buffer in, a
 // MemoryStream out), so a drop-in caller of rcx_encode_blocks / rcx_decode_blocks / rcx_bwt_encode / rcx_bwt_decode
 // sees link + kernels, not kernels.  One call is cut into chunks of whole blocks and three things run at once:
 //   feeders   host threads that move chunk k+1 .. to the GPU, each on a copy stream of its own,
 //   the caller's thread, which launches chunk k's kernels on one of a few work streams as soon as its bytes are
-//             there (a chunk's launches are `packed`, rcx_api.hip: chunks share the machine, because a block is a
+//             there (a chunk's launches are `packed`, rcx_launch.hpp: chunks share the machine, because a block is a
 //             serial chain and a chunk's kernels take as long as a whole buffer's would),
 //   drainers  host threads that bring chunk k-1's result back, all on one copy-back stream.
 // The stages hand over on the HOST (a feeder waits for its own copy, the caller's thread for the feeders, a drainer
@@ -41,10 +42,7 @@
 #include <mutex>
 #include <thread>
 
-
-
-namespace
-{
+#include "rcx_ctx.hpp"
 
 enum { RCX_HOST_DIRECT = 0, RCX_HOST_STAGED = 1, RCX_HOST_REGISTER = 2 };
 #define RCX_HOST_WORK_STREAMS 3     /* default */
@@ -60,13 +58,14 @@ struct HostPipe {
     int out_mode_decode = RCX_HOST_DIRECT; // (the decoders' output: see the top of the file)
     int feeders = 1, drainers = 3; // host threads per direction
     u64 piece = 16ull << 20; // bytes per copy
-    u8* pin = nullptr;       // staged: two slots of `piece` bytes per feeder, then two per drainer
-    u64 pin_bytes = 0;
-    u64* words = nullptr;    // pinned: what the caller's thread needs back from a chunk (its offsets, a count)
-    u64 words_count = 0;
+    PinBuf<u8> pin;          // staged: two slots of `piece` bytes per feeder, then two per drainer
+    PinBuf<u64> words;       // what the caller's thread needs back from a chunk (its offsets, a count)
     u64 bwt_ties = 0;        // periodic blocks of the last host-buffer block sort (all chunks)
     bool bwt_ties_valid = false;
 };
+
+namespace
+{
 
 void host_pipe_destroy(HostPipe* p)
 {
@@ -76,8 +75,6 @@ void host_pipe_destroy(HostPipe* p)
     if (p->out_stream) (void)hipStreamDestroy(p->out_stream);
     for (auto& s : p->work)
         if (s) (void)hipStreamDestroy(s);
-    if (p->pin) (void)hipHostFree(p->pin);
-    if (p->words) (void)hipHostFree(p->words);
     delete p;
 }
 
@@ -132,28 +129,13 @@ int host_pipe_get(rcx_ctx* c, HostPipe** out)
     return RCX_OK;
 }
 
-int host_pipe_words(HostPipe* p, u64 count)
-{
-    if (p->words_count >= count) return RCX_OK;
-    if (p->words) (void)hipHostFree(p->words);
-    p->words = nullptr;
-    p->words_count = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&p->words), count * sizeof(u64), hipHostMallocDefault) != hipSuccess) return RCX_E_NOMEM;
-    p->words_count = count;
-    return RCX_OK;
-}
+int host_pipe_words(HostPipe* p, u64 count) { return p->words.reserve(count); }
 
 int host_pipe_pin(HostPipe* p)
 {
     const bool out_staged = p->out_mode == RCX_HOST_STAGED || p->out_mode_decode == RCX_HOST_STAGED;
     const u64 want = ((p->in_mode == RCX_HOST_STAGED ? 2ull * p->feeders : 0) + (out_staged ? 2ull * p->drainers : 0)) * p->piece;
-    if (p->pin_bytes >= want) return RCX_OK;
-    if (p->pin) (void)hipHostFree(p->pin);
-    p->pin = nullptr;
-    p->pin_bytes = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&p->pin), want, hipHostMallocDefault) != hipSuccess) return RCX_E_NOMEM;
-    p->pin_bytes = want;
-    return RCX_OK;
+    return p->pin.reserve(want);
 }
 
 // One piece of work for a mover: `bytes` from `from` to `to`, one of them the caller's memory.

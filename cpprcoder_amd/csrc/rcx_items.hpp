@@ -1,6 +1,6 @@
 // rcx_items.hpp -- the item calls of include/rcx.h: many independent buffers of differing sizes in one call, any
-// subset of their streams back.  Included by rcx_api.hip behind the launch templates (encode_launches / decode_launches),
-// which these calls instantiate with the item geometry (rcx_geom.hpp, RcxItems).
+// subset of their streams back.  These calls instantiate the launch templates (rcx_launch.hpp: encode_launches /
+// decode_launches) with the item geometry (rcx_geom.hpp, RcxItems).
 //
 // Everything that depends on the lengths is planned here, on the host, before anything is enqueued:
 //   work order   entries sorted by length, longest first: a wave runs as long as its longest entry, so it should carry
@@ -13,6 +13,8 @@
 #pragma once
 
 #include <algorithm>
+
+#include "rcx_launch.hpp"
 
 namespace
 {
@@ -97,19 +99,11 @@ u64 item_scratch_bytes(const ItemPlan& p, int coder, bool encode)
     return b;
 }
 
-int grow_u32(u32** p, u64* count, u64 want)
-{
-    u64 bytes = *count * sizeof(u32);
-    const int r = grow(reinterpret_cast<void**>(p), &bytes, want * sizeof(u32));
-    *count = r == RCX_OK ? bytes / sizeof(u32) : 0;
-    return r;
-}
-
 // The tables go to the device in one copy: at[nwork] | len | id | stream | inv[items], the u64 part first.
 int upload_items(rcx_ctx* c, const ItemPlan& p, hipStream_t s, RcxItems* g)
 {
     const u64 bytes = item_tables_bytes(p);
-    int r = grow(reinterpret_cast<void**>(&c->itab), &c->itab_bytes, bytes);
+    const int r = c->itab.reserve(bytes);
     if (r != RCX_OK) return r;
     c->itab_host.resize((bytes + 7) / 8);
     u8* h = reinterpret_cast<u8*>(c->itab_host.data());
@@ -180,7 +174,7 @@ int rcx_items_plan(int coder, const uint64_t* src_offsets, uint64_t nitems, uint
 int rcx_ctx_scratch_bytes(rcx_ctx* c, uint64_t* bytes)
 {
     if (!c || !bytes) return RCX_E_ARG;
-    *bytes = c->slots_bytes + (c->sizes_count + c->starts_count + c->redo_count) * sizeof(u32) + c->models_bytes + c->itab_bytes;
+    *bytes = c->slots.bytes() + c->sizes.bytes() + c->starts.bytes() + c->redo.bytes() + c->models.bytes() + c->itab.bytes();
     return RCX_OK;
 }
 
@@ -196,13 +190,7 @@ int rcx_encode_items_device(rcx_ctx* c, int coder, const void* d_src, const uint
     if (p.nwork == 0) return hipMemsetAsync(d_comp_offsets, 0, (nitems + 1) * sizeof(u64), s) == hipSuccess ? RCX_OK : RCX_E_HIP;
     if (!d_src || !d_dst) return RCX_E_ARG;
     // scratch: what the data asks for (at most twice its bound) and a fixed number of bytes per entry
-    if (!is_rans(coder) && (r = ensure_divtab(c, p.longest)) != RCX_OK) return r;
-    if ((r = grow(reinterpret_cast<void**>(&c->slots), &c->slots_bytes, p.slots_bytes + 256)) != RCX_OK) return r;
-    if ((r = grow_u32(&c->sizes, &c->sizes_count, p.nwork + 1)) != RCX_OK) return r;
-    if (is_rans(coder) && (r = grow_u32(&c->starts, &c->starts_count, p.nwork + 1)) != RCX_OK) return r;
-    if (coder == RCX_CODER_RANS && (r = grow(reinterpret_cast<void**>(&c->models), &c->models_bytes, p.nwork * RCX_RANS_MODEL_DW * sizeof(u32))) != RCX_OK)
-        return r;
-    if ((r = ensure_redo(c, p.nwork)) != RCX_OK) return r;
+    if ((r = reserve_scratch(c, coder, p.nwork, p.slots_bytes, p.longest)) != RCX_OK) return r;
     RcxItems g{};
     if ((r = upload_items(c, p, s, &g)) != RCX_OK) return r;
     // pass 1, a launch per class, the longest entries first; the launch shape follows the class's own count: a small
@@ -223,7 +211,7 @@ int rcx_encode_items_device(rcx_ctx* c, int coder, const void* d_src, const uint
                                d_comp_offsets, static_cast<u8*>(d_dst), dst_cap,
                                is_rans(coder) ? static_cast<const u32*>(c->starts + k.first) : static_cast<const u32*>(nullptr), items_from(g, k.first));
     }
-    return hipGetLastError() == hipSuccess ? RCX_OK : RCX_E_HIP;
+    return LAUNCHED();
 }
 
 int rcx_decode_items_device(rcx_ctx* c, int coder, const void* d_comp, uint64_t comp_size, const uint64_t* d_comp_offsets,
@@ -256,12 +244,7 @@ int rcx_encode_items(rcx_ctx* c, int coder, const uint8_t* src, const uint64_t* 
     const u64 base = nitems ? src_offsets[0] : 0, n = nitems ? src_offsets[nitems] - base : 0;
     if (n && (!src || !dst)) return RCX_E_ARG;
     const u64 bound = rcx_encode_items_bound(coder, src_offsets, nitems);
-    int r = grow(reinterpret_cast<void**>(&c->h_in), &c->h_in_bytes, n + 64);
-    if (r != RCX_OK) return r;
-    if ((r = grow(reinterpret_cast<void**>(&c->h_out), &c->h_out_bytes, bound + 64)) != RCX_OK) return r;
-    u64 off_bytes = c->h_off_count * sizeof(u64);
-    r = grow(reinterpret_cast<void**>(&c->h_off), &off_bytes, (nitems + 1) * sizeof(u64));
-    c->h_off_count = r == RCX_OK ? off_bytes / sizeof(u64) : 0;
+    int r = reserve_staging(c, n, bound, nitems + 1);
     if (r != RCX_OK) return r;
     std::vector<u64> rel(nitems + 1, 0); // the device copy begins at the first item
     for (u64 i = 0; i <= nitems && nitems; ++i) rel[i] = src_offsets[i] - base;
@@ -289,12 +272,7 @@ int rcx_decode_items(rcx_ctx* c, int coder, const uint8_t* comp, uint64_t comp_s
     const u64 base = dst_offsets[0], n = dst_offsets[npick] - base;
     if (n == 0) return RCX_OK;
     if (!comp || !dst) return RCX_E_ARG;
-    int r = grow(reinterpret_cast<void**>(&c->h_in), &c->h_in_bytes, comp_size + 64);
-    if (r != RCX_OK) return r;
-    if ((r = grow(reinterpret_cast<void**>(&c->h_out), &c->h_out_bytes, n + 64)) != RCX_OK) return r;
-    u64 off_bytes = c->h_off_count * sizeof(u64);
-    r = grow(reinterpret_cast<void**>(&c->h_off), &off_bytes, (nstreams + 1) * sizeof(u64));
-    c->h_off_count = r == RCX_OK ? off_bytes / sizeof(u64) : 0;
+    int r = reserve_staging(c, comp_size, n, nstreams + 1);
     if (r != RCX_OK) return r;
     std::vector<u64> rel(npick + 1);
     for (u64 k = 0; k <= npick; ++k) rel[k] = dst_offsets[k] - base;

@@ -52,7 +52,7 @@ def main():
                         enc_ms.append(t["encode"]["ms"] + t["scan"]["ms"] + t["scatter"]["ms"])
                         dec_ms.append(t["decode"]["ms"])
                 ok = bool(torch.equal(out, src))
-                # launch shape of the adaptive coder (rcx_api.hip: encode_lanes / decode_quads; SURVEY.md section 8(d) config 5
+                # launch shape of the adaptive coder (rcx_launch.hpp: encode_lanes / decode_quads; SURVEY.md section 8(d) config 5
                 # asks for waves per CU and LDS bytes per wave next to the rates)
                 shape = {}
                 if args.coder == 0:
