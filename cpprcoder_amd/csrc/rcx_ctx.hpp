@@ -51,7 +51,7 @@ struct rcx_ctx {
     DevBuf<u32> ties;        // block sort: [count, (block, period) ...] of the periodic blocks of the last forward call
     int bwt_atomic = -1;     // the block sort's counting passes rank with ds_add_rtn_u32 (1, checked on this device) or ballots (0); -1 = not asked yet
     // One allocation, two views: `div_entries` DivEntry, one per symbol of the largest block (divtab), and behind them the
-    // same divisors as the quad decoder reads them, RCX_QUAD_DIVQ_DW words per group of 16 (divq; rcx_oct.hpp).
+    // same divisors as the quad decoder reads them, RCX_QUAD_DIVQ_DW words per group of 16 (divq; rcx_quad.hpp).
     DevBuf<u8> divmem;
     u64 div_entries = 0;
     u32 divtab_block = 0;

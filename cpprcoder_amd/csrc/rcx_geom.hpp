@@ -25,15 +25,42 @@ struct RcxItems {
     const u32* inv;    // the size scan, which runs in the caller's order: item -> its work entry, 0xFFFFFFFF for an item of length 0
 };
 
-// The block geometry's two lines stay in the kernels as they were (at = blk * block, len = min(block, n - at)); the
-// item geometry replaces their result with the tables' (and leaves them without a use).  A lane without an entry has
-// length 0 and the position of the launch's first entry -- its longest: where a kernel lets such a lane read along with
-// the others, it reads bytes that are there.
+// Where entry `blk` lies.  A lane without an entry has length 0 and the position of the launch's first entry -- with
+// items its longest: where a kernel lets such a lane read along with the others, it reads bytes that are there.
 __device__ __forceinline__ void rcx_where(const RcxItems& g, bool live, u64 blk, u64& at, u32& len)
 {
     at = g.at[live ? blk : 0];
     len = live ? g.len[blk] : 0u;
 }
+
+// How every coding kernel opens.  RCX_ENTRY declares `live` (the lane has an entry), `at` and `len` for work entry BLK
+// of geometry GEOM: with blocks, position and length follow from the index (the last block of a buffer is the short
+// one); with items they are the tables' (and the block lines are left without a use).  RCX_ENTRY_ONLY is the same for a
+// kernel that can run as the second pass behind a many-lane kernel: ONLY != nullptr leaves just the entries that one
+// marked (ONLY[blk] != 0), and a wave none of whose lanes has an entry returns.
+// Macros, not functions: a function is optimised on its own before it is inlined into the kernel, and what arrives
+// there differs enough from these lines written in place that 18 of the 50 kernels came out with different
+// instructions, down into their symbol loops (tools/diag/kernel_diff.py).
+#define RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)                                                          \
+    u64 at = live ? (BLK) * (u64)(BLOCK) : 0;                                                         \
+    u32 len = live ? (u32)(((N) - at) < (u64)(BLOCK) ? ((N) - at) : (u64)(BLOCK)) : 0u;               \
+    if constexpr (decltype(GEOM)::items) rcx_where(GEOM, live, BLK, at, len)
+#define RCX_ENTRY(GEOM, BLK, NBLOCKS, N, BLOCK)                                                       \
+    bool live = (BLK) < (NBLOCKS);                                                                    \
+    RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)
+#define RCX_ENTRY_ONLY(GEOM, BLK, NBLOCKS, N, BLOCK, ONLY)                                            \
+    bool live = (BLK) < (NBLOCKS);                                                                    \
+    if (ONLY) {                                                                                       \
+        live = live && (ONLY)[BLK] != 0;                                                              \
+        if (!__any(live)) return;                                                                     \
+    }                                                                                                 \
+    RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)
+
+// The fast paths' condition (16 bytes at a go, no per-symbol length test), behind RCX_ENTRY: every lane of the wave has
+// a whole block, blocks are multiples of 16 bytes and P, the buffer the blocks lie in, is 16-byte aligned.  Never with
+// items, which begin where the one before ends.  (A macro for RCX_ENTRY's reason: as a function it changed three kernels.)
+#define RCX_ALL_FULL(GEOM, BLOCK, P)                                                                  \
+    (!decltype(GEOM)::items && __all(live && len == (BLOCK)) && ((BLOCK) % 16u == 0) && ((reinterpret_cast<uintptr_t>(P) & 15u) == 0))
 
 // the index a latched failure names
 __device__ __forceinline__ u64 rcx_id(const RcxBlocks&, u64 blk) { return blk; }
@@ -41,6 +68,15 @@ __device__ __forceinline__ u64 rcx_id(const RcxItems& g, u64 blk) { return g.id[
 // the entry's place in the table of compacted streams (decode)
 __device__ __forceinline__ u64 rcx_stream_of(const RcxBlocks&, u64 blk) { return blk; }
 __device__ __forceinline__ u64 rcx_stream_of(const RcxItems& g, u64 blk) { return g.stream[blk]; }
+
+// The entry's stream in the compacted set, for a decoder (behind RCX_ENTRY, for its reason macros): RCX_STREAM declares
+// s0, s1 -- where it begins and ends in the compressed buffer -- and sets stream_len; RCX_STREAM_OK: the two offsets are
+// in order, inside the buffer, and at least MIN bytes apart.  (An offset table that points past the buffer is not followed.)
+#define RCX_STREAM(GEOM, BLK, OFFSETS)                                                                \
+    const u64 sidx = rcx_stream_of(GEOM, BLK);                                                        \
+    const u64 s0 = (OFFSETS)[sidx], s1 = (OFFSETS)[sidx + 1];                                         \
+    stream_len = s1 - s0
+#define RCX_STREAM_OK(COMP_SIZE, MIN) (s1 >= s0 && s1 <= (COMP_SIZE) && stream_len >= (MIN))
 
 // stream size of entry b of the offsets table (the scan): sizes[] is in work order
 __device__ __forceinline__ u32 rcx_size_of(const RcxBlocks&, const u32* sizes, u64 b) { return sizes[b]; }

@@ -16,7 +16,7 @@
 // block (decode), see the second half of this file; a single stream (rcx_stream_encode) is coded by one octet whose
 // lanes all carry the state.
 //
-// Included at the end of rcx_kernels.hpp.
+// Included by rcx_kernels.hpp.
 #pragma once
 #include "rcx_divtab.hpp"
 
@@ -178,10 +178,7 @@ __global__ __launch_bounds__(256) void rcx_enc_rans_k(const u8* __restrict__ src
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * 4 + wave) * RCX_RANS_BLOCKS + oct;
-    const bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY(g, blk, nblocks, n, block);
     u32* cum = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_RANS_ENC_LDS_DW;
     u32* table = cum + 264;
     u8* stage = reinterpret_cast<u8*>(table + 256);
@@ -420,10 +417,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * WAVES + wave) * RCX_RANS_BLOCKS + oct;
-    bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY(g, blk, nblocks, n, block);
     u8* mine = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_R8_LDS_BYTES;
     u8* first = mine;
     u32* table = reinterpret_cast<u32*>(mine + RCX_R8_FIRST_BYTES);
@@ -433,11 +427,9 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
     const u8* s = comp;
     u64 stream_len = 0;
     if (live) {
-        const u64 sidx = rcx_stream_of(g, blk);
-        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
-        stream_len = s1 - s0;
+        RCX_STREAM(g, blk, offsets);
         s = comp + s0;
-        bool good = s1 >= s0 && s1 <= comp_size && stream_len >= RCX_RANS_HEADER + 32;
+        bool good = RCX_STREAM_OK(comp_size, RCX_RANS_HEADER + 32);
         if (good) good = rcx_load_le32(s) == len; // cppans.h:616-620: the declared size (the layout says len)
         // The table (cppans.h:621-626).  Lane j takes symbols 32j .. 32j+31: checks that their bounds form a scaled
         // cumulative table (the reference trusts it and would leave its arrays), counts the symbols that occur, and
@@ -650,7 +642,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans8_k(const u8* __restri
 // wastes seven lanes in eight on the coding loop; these kernels are what the block entry points run:
 //   rcx_rans_model_k     the model of every block (count / cumulative / normalize), by octets as above -> `models`
 //   rcx_enc_rans1_k      one lane per block: table lookups in LDS, bytes gathered into dwords, written backwards
-//   rcx_dec_rans1_quad_k 4 lanes per block with the range decoders' machinery (rcx_oct.hpp: table groups, input
+//   rcx_dec_rans1_quad_k 4 lanes per block with the range decoders' machinery (rcx_quad.hpp: table groups, input
 //                        ring): the symbol of a slot = the number of cumulative bounds at or below it, counted in
 //                        two rounds of 16; slot - start is the minimum of the wrapped differences and the frequency
 //                        is minimum - maximum, as in rcx_dec_static_quad_k -- no multiplication at all.
@@ -665,9 +657,7 @@ __global__ __launch_bounds__(256) void rcx_rans_model_k(const u8* __restrict__ s
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * 4 + wave) * RCX_RANS_BLOCKS + oct;
     if (blk >= nblocks) return; // (an octet leaves together)
-    u64 at = blk * (u64)block;
-    u32 len = (u32)((n - at) < (u64)block ? (n - at) : (u64)block);
-    if constexpr (G::items) rcx_where(g, true, blk, at, len);
+    RCX_ENTRY(g, blk, nblocks, n, block);
     u32* cum = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_RANS_ENC_LDS_DW;
     u32* table = cum + 264;
     const u8* in = src + at;
@@ -711,10 +701,7 @@ __global__ __launch_bounds__(64 * RCX_RANS1_ENC_WAVES) void rcx_enc_rans1_k(cons
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const bool in_use = lane < lanes_used;
     const u64 blk = in_use ? ((u64)blockIdx.x * RCX_RANS1_ENC_WAVES + wave) * lanes_used + lane : nblocks;
-    const bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY(g, blk, nblocks, n, block);
     RcxRansSym* table = rcx_rans1_lds + wave * 256u * lanes_used + (in_use ? lane : 0u);
     if (live) {
         const RcxRansSym* m = reinterpret_cast<const RcxRansSym*>(models + blk * RCX_RANS_MODEL_DW + 264);
@@ -924,10 +911,7 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
     const u32 lane = threadIdx.x & 63u;
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const u64 blk = (u64)blockIdx.x * 64u + lane;
-    const bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY(g, blk, nblocks, n, block);
     const u8* in = src + at;
     RcxRansSym* table = table_all + lane; // entry s at table[64 s]
     if (live) {
@@ -935,7 +919,7 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
         for (u32 sy = wave; sy < 256; sy += 2) table[sy * 64u] = m[sy];
     }
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool full = RCX_ALL_FULL(g, block, src);
     const u32 nchunks = (maxlen + RCX_R1W_CHUNK - 1) / RCX_R1W_CHUNK;
     rcx_lds_barrier();
 
@@ -969,7 +953,7 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
     }
 }
 
-// Decode, 4 lanes per block.  LDS per wave: four table groups (rcx_oct.hpp: node n of the four blocks of a group in
+// Decode, 4 lanes per block.  LDS per wave: four table groups (rcx_quad.hpp: node n of the four blocks of a group in
 // the four quarters of a 256-byte row) | sixteen input rings.  Node n of a block = its cumulative bounds
 // cum[16n+1 .. 16n+16]; lane j keeps cum[16(4j+1)] .. cum[16(4j+4)] in registers.
 template <int WAVES, class G = RcxBlocks>
@@ -977,77 +961,59 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
                                                                   u64 nblocks, u32 block, u64 n, u8* __restrict__ dst, u32* status,
                                                                   u32 quads_used, u32* track, const G g = G())
 {
-    __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_SQUAD_LDS_BYTES];
-    const u32 lane = threadIdx.x & 63u;
-    const u32 wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    u8* lds = lds_all + wave_in_wg * RCX_SQUAD_LDS_BYTES;
-    const u32 j = lane & 3u, quad = lane >> 2;
-    const bool in_use = quad < quads_used; // see rcx_dec_quad_k: the other quads decode along and store nothing
-    const u64 blk = ((u64)blockIdx.x * WAVES + wave_in_wg) * quads_used + (quad & (quads_used - 1u));
-    bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
-    const u32 group = 2u * (quad >> 3) + ((0x96u >> (quad & 7u)) & 1u), quarter = (quad & 7u) >> 1;
-    u8* mine = lds + group * RCX_QUAD_GROUP_BYTES + quarter * 64;
-    U4* leaves = reinterpret_cast<U4*>(mine) + j;
-    U4* scratch = reinterpret_cast<U4*>(mine + 16 * 256);
-    u32* block_ring = reinterpret_cast<u32*>(lds + 4 * RCX_QUAD_GROUP_BYTES + quad * RCX_QUAD_RING_BYTES);
+    __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_QUAD_LDS_BYTES];
+    RCX_QUAD_SEAT(seat, WAVES, quads_used, lds_all, g, nblocks, n, block); // (as rcx_dec_quad_k)
 
     QuadInput in;
     u64 stream_len = 0;
     u32 U1 = 1, U2 = 2, U3 = 3, U4_ = 16384;
     if (live) {
-        const u64 sidx = rcx_stream_of(g, blk);
-        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
-        stream_len = s1 - s0;
+        RCX_STREAM(g, seat.blk, offsets);
         const u8* s = comp + s0;
-        bool good = s1 >= s0 && s1 <= comp_size && stream_len >= RCX_RANS_HEADER + 4;
+        bool good = RCX_STREAM_OK(comp_size, RCX_RANS_HEADER + 4);
         if (good) good = rcx_load_le32(s) == len; // cppans.h:540-543: the declared size (the layout says len)
         u32 ok = 1;
         if (good) {
             // lane j takes cum[64j+1 .. 64j+64] = nodes 4j .. 4j+3; the table must be a scaled cumulative one (the
             // reference trusts it, cppans.h:544, and would leave its arrays)
-            u32 prev = rcx_load_le32(s + 4 + 4 * (64 * j));
-            if (j == 0 && prev != 0) ok = 0;
+            u32 prev = rcx_load_le32(s + 4 + 4 * (64 * seat.j));
+            if (seat.j == 0 && prev != 0) ok = 0;
             for (u32 i = 0; i < 64; ++i) {
-                const u32 v = rcx_load_le32(s + 4 + 4 * (64 * j + i + 1));
+                const u32 v = rcx_load_le32(s + 4 + 4 * (64 * seat.j + i + 1));
                 if (v < prev || v > 16384u) ok = 0;
-                reinterpret_cast<u32*>(mine + (4 * j + (i >> 4)) * 256)[i & 15u] = v;
+                reinterpret_cast<u32*>(seat.mine + (4 * seat.j + (i >> 4)) * 256)[i & 15u] = v;
                 if (i == 15) U1 = v;
                 if (i == 31) U2 = v;
                 if (i == 47) U3 = v;
                 if (i == 63) U4_ = v;
                 prev = v;
             }
-            if (j == 3 && prev != 16384u) ok = 0;
+            if (seat.j == 3 && prev != 16384u) ok = 0;
         }
         good = good && rcx_quad_or(ok ? 0u : 1u) == 0;
         if (good) {
             // QuadInput::begin wants 4 size bytes + 4 state bytes in front of the payload: the state (u32 LE at
             // 1032) is what it reads big-endian into `low`
-            in.begin(s + RCX_RANS_HEADER - 4, comp + s1, block_ring, scratch + 3);
+            in.begin(s + RCX_RANS_HEADER - 4, comp + s1, seat.ring, seat.parked + 3);
         } else {
-            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
-            live = false;
-            len = 0;
+            RCX_QUAD_FAIL(seat, g, status)
         }
     }
     if (!live) {
-        in.idle(comp, block_ring, scratch + 3);
+        in.idle(comp, seat.ring, seat.parked + 3);
         U1 = 1, U2 = 2, U3 = 3, U4_ = 16384;
         U4 v;
         v.x = v.y = v.z = v.w = 16384;
-        for (u32 q = 0; q < 16; ++q) leaves[q * 16] = v;
+        for (u32 q = 0; q < 16; ++q) seat.leaves[q * 16] = v;
     }
     u32 x = live ? rcx_bswap(in.low) : (1u << 23); // cppans.h:303-310
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = RCX_ALL_FULL(g, block, dst);
     u8* out = dst + at;
-    const bool leader = live && in_use && j == 0;
-    const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(leaves);
+    const bool leader = live && seat.in_use && seat.j == 0;
+    const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(seat.leaves);
 
-    const u32 ring_lds = (u32)reinterpret_cast<uintptr_t>(block_ring);
+    const u32 ring_lds = (u32)reinterpret_cast<uintptr_t>(seat.ring);
     // One symbol (cppans.h:556-561): get, the symbol of the slot, advance, renormalise by at most two bytes.
     // Written as instruction sequences like rcx_dec_quad_k / rcx_dec_static_quad_k (a lone wave: every compare result and
     // every DPP source at least two instructions old, nothing but the node index's own steps in front of the leaf read);
@@ -1056,8 +1022,6 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
     // needs is made by the NEXT symbol behind its leaf read (HP = 1: PWORD, PSHIFT are the earlier symbol's word and
     // bit position) or by RCX_RANS1_FINISH: the symbol's byte, the stream position and the read of the ring pair there.
     u32 p_nd_ = 0, p_nb_ = 0, p_r8_ = 0;
-#define RCX_QP1 "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define RCX_QP2 "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 #define RCX_R1_PREV_0
 #define RCX_R1_PREV_1 "\n\tv_lshl_add_u32 %[ps], %[pnd], 4, %[pnb]\n\t"                                             \
                       "v_lshl_or_b32 %[pword], %[ps], %[psh], %[pword]"
@@ -1100,31 +1064,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
             in.w1 = at_[1];                                                                                  \
         }                                                                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
-        u32 lo_, rg_, nb_, hi_, y1_, y2_, y3_, y4_;                                                          \
-        asm volatile("v_sub_co_u32_e64 %[y1], %[c1], %[sl], %[lx]\n\t"                                       \
-                     "v_sub_co_u32_e64 %[y2], %[c2], %[sl], %[ly]\n\t"                                       \
-                     "v_sub_co_u32_e64 %[y3], %[c3], %[sl], %[lz]\n\t"                                       \
-                     "v_sub_co_u32_e64 %[y4], %[c4], %[sl], %[lw]\n\t"                                       \
-                     "v_subb_co_u32_e64 %[nb], %[c1], 4, 0, %[c1]\n\t"                                       \
-                     "v_min3_u32 %[lo], %[y1], %[y2], %[y3]\n\t"                                             \
-                     "v_subb_co_u32_e64 %[nb], %[c2], %[nb], 0, %[c2]\n\t"                                   \
-                     "v_max3_u32 %[hi], %[y1], %[y2], %[y3]\n\t"                                             \
-                     "v_subb_co_u32_e64 %[nb], %[c3], %[nb], 0, %[c3]\n\t"                                   \
-                     "v_min3_u32 %[lo], %[lo], %[y4], %[rem]\n\t"                                            \
-                     "v_subb_co_u32_e64 %[nb], %[c4], %[nb], 0, %[c4]\n\t"                                   \
-                     "v_max_u32 %[hi], %[hi], %[y4]\n\t"                                                     \
-                     "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP1                                            \
-                     "v_add_u32_dpp %[nb], %[nb], %[nb] " RCX_QP1                                            \
-                     "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP1                                            \
-                     "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP2                                            \
-                     "v_add_u32_dpp %[nb], %[nb], %[nb] " RCX_QP2                                            \
-                     "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP2                                            \
-                     "v_sub_u32 %[rg], %[lo], %[hi]"                                                         \
-                     : [lo] "=&v"(lo_), [rg] "=&v"(rg_), [nb] "=&v"(nb_), [hi] "=&v"(hi_), [y1] "=&v"(y1_),   \
-                       [y2] "=&v"(y2_), [y3] "=&v"(y3_), [y4] "=&v"(y4_), [c1] "=&s"(c1_), [c2] "=&s"(c2_),  \
-                       [c3] "=&s"(c3_), [c4] "=&s"(c4_)                                                      \
-                     : [sl] "v"(slot_), [lx] "v"(l_.x), [ly] "v"(l_.y), [lz] "v"(l_.z), [lw] "v"(l_.w),      \
-                       [rem] "v"(rem_));                                                                     \
+        RCX_QUAD_ROUND2_CUM(slot_, l_.x, l_.y, l_.z, l_.w);                                                  \
         p_nd_ = node_;                                                                                       \
         p_nb_ = nb_;                                                                                         \
         x = rcx_mul24(rg_, xs_) + lo_; /* freq * (x >> 14) + slot - start (cppans.h:326) */                   \
@@ -1148,11 +1088,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
         for (u32 i0 = 0; i0 < maxlen; i0 += 16) {
             in.topup();
             u32 w0_ = 0, w1_ = 0, w2_ = 0, w3_ = 0;
-            RCX_RANS1_SYMBOL(0, w0_, 0) RCX_RANS1_SYMBOL(1, w0_, 0) RCX_RANS1_SYMBOL(1, w0_, 8) RCX_RANS1_SYMBOL(1, w0_, 16)
-            RCX_RANS1_SYMBOL(1, w0_, 24) RCX_RANS1_SYMBOL(1, w1_, 0) RCX_RANS1_SYMBOL(1, w1_, 8) RCX_RANS1_SYMBOL(1, w1_, 16)
-            RCX_RANS1_SYMBOL(1, w1_, 24) RCX_RANS1_SYMBOL(1, w2_, 0) RCX_RANS1_SYMBOL(1, w2_, 8) RCX_RANS1_SYMBOL(1, w2_, 16)
-            RCX_RANS1_SYMBOL(1, w2_, 24) RCX_RANS1_SYMBOL(1, w3_, 0) RCX_RANS1_SYMBOL(1, w3_, 8) RCX_RANS1_SYMBOL(1, w3_, 16)
-            RCX_RANS1_FINISH(w3_, 24)
+            RCX_QUAD_16_SYMBOLS(RCX_RANS1_SYMBOL, RCX_RANS1_FINISH)
             if (leader) {
                 U4 o;
                 o.x = w0_, o.y = w1_, o.z = w2_, o.w = w3_;
@@ -1160,26 +1096,16 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_rans1_quad_k(const u8* __r
             }
         }
     } else {
-        for (u32 i = 0; i < maxlen; ++i) {
-            if ((i & 15u) == 0) in.topup();
-            if (i < len) { // the 4 lanes of a quad agree
-                u32 sym = 0;
-                RCX_RANS1_SYMBOL(0, sym, 0);
-                RCX_RANS1_FINISH(sym, 0);
-                if (leader) out[i] = (u8)sym;
-            }
-        }
+        RCX_QUAD_TAIL(0u, , RCX_RANS1_SYMBOL, RCX_RANS1_FINISH, )
     }
 #undef RCX_RANS1_SYMBOL
 #undef RCX_RANS1_FINISH
 #undef RCX_R1_PREV_0
 #undef RCX_R1_PREV_1
-#undef RCX_QP1
-#undef RCX_QP2
     // a valid stream holds every byte that was taken
     const u64 taken = RCX_RANS_HEADER - 4 + in.taken(); // QuadInput counts from 8 bytes into what it was given
-    if (leader && taken > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
+    if (leader && taken > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, seat.blk));
     // the single-stream call wants what rANS::decode returns: the payload bytes consumed (cppans.h:562)
-    if (track && leader && blk == 0) track[0] = (u32)(taken - RCX_RANS_HEADER);
+    if (track && leader && seat.blk == 0) track[0] = (u32)(taken - RCX_RANS_HEADER);
 }
 

@@ -1,5 +1,5 @@
 // rcx_static.hpp -- the static (two-pass) range coder RangeEncoder<T> on gfx950: one lane per block
-// (rcx_enc_static_k, rcx_dec_static_k), and the many-wave / four-lane kernels built on rcx_oct.hpp's machinery
+// (rcx_enc_static_k, rcx_dec_static_k), and the many-wave / four-lane kernels built on rcx_mc.hpp's and rcx_quad.hpp's machinery
 // (rcx_enc_static3_k, rcx_dec_static_quad_k).
 //
 // Reference: cpprcoder.h:321-619.  Stream of one block:
@@ -14,7 +14,7 @@
 // The table of a block is 257 dwords in LDS, dword-interleaved over the 64 lanes of the wave
 // (entry i of lane l at (i*64 + l)*4), so any per-lane index is bank-conflict free.  The divisor
 // (total) is fixed per block but differs between lanes: its multiply-add magic is computed once per
-// block on the device.  Included at the end of rcx_kernels.hpp.
+// block on the device.  Included by rcx_kernels.hpp.
 #pragma once
 
 #define RCX_STATIC_HEADER 516u
@@ -103,22 +103,15 @@ __global__ __launch_bounds__(64) void rcx_enc_static_k(const u8* __restrict__ sr
     __shared__ u32 lds[RCX_STATIC_LDS_DW];
     const u32 lane = threadIdx.x;
     const u64 blk = (u64)blockIdx.x * RCX_LANES + lane;
-    bool live = blk < nblocks;
     // second pass behind rcx_enc_static3_k: only the blocks it marked (none, on ordinary data)
-    if (only) {
-        live = live && only[blk] != 0;
-        if (!__any(live)) return;
-    }
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY_ONLY(g, blk, nblocks, n, block, only);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
 
     // ---- count(), cpprcoder.h:543-571 ----
     for (u32 i = 0; i <= 256; ++i) tab.set(i, 0);
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool full = RCX_ALL_FULL(g, block, src);
     // A count can only be 0xFFFF before its increment once 65535 earlier symbols exist, so the squeeze
     // test is not needed for the first 65535 symbols of a block.
     const u32 easy = maxlen < 65535u ? maxlen : 65535u;
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(64) void rcx_enc_static_k(const u8* __restrict__ sr
 }
 
 // ===========================================================================
-// Static encode, pass 1, three waves per 64 blocks: the five-wave adaptive encoder (rcx_enc_mc5_k, rcx_oct.hpp)
+// Static encode, pass 1, three waves per 64 blocks: the five-wave adaptive encoder (rcx_enc_mc5_k, rcx_mc.hpp)
 // without its model waves -- the table does not change while coding.  wave 0 = arithmetic (EncLane::arith with
 // full 32-bit multiplies), wave 1 = writer (StagedWriter: words through LDS rings), wave 2 = table lookups for
 // the next chunk + the drain of the rings.  The histogram (cpprcoder.h:543-571) is counted by all three waves
@@ -247,36 +240,14 @@ __device__ __forceinline__ void rcx_static3_pipeline(u32 wave, u32 lane, u32 len
                 }
             }
         } else if (wave == 1) {
-            // ---- writer: chunk k-2 ----
-            if (k >= 2) {
-                const u32* rs2 = ring2 + ((k - 2) & 1u) * (RCX_MC_CHUNK * RCX_LANES) + lane;
-                u32 ra_next = rs2[0], rb_next = rs2[RCX_LANES];
-                wr.chunk_begins();
-#pragma unroll
-                for (u32 s = 0; s < RCX_MC_CHUNK; s += 2) {
-                    const u32 ra = ra_next, rb = rb_next;
-                    if (s + 2 < RCX_MC_CHUNK) ra_next = rs2[(s + 2) * RCX_LANES], rb_next = rs2[(s + 3) * RCX_LANES];
-                    wr.emit(ra);
-                    wr.emit(rb);
-                }
-                out_pos[lane] = wr.chunk_ends();
-            }
+            RCX_MC_WRITER_STAGE(k, ring2, wr, out_pos) // chunk k-2
         } else {
-            // ---- drain (see rcx_mc5_pipeline: the reads here, the stores between the wait for this chunk's input and the
-            // request for the next chunk's, no loop) ----
-            const u32 drain_p = out_pos[lane];
+            // ---- drain (rcx_mc.hpp: the reads here, the stores between the wait for this chunk's input and the request
+            // for the next chunk's) ----
+            u32 drain_p;
             RcxU4Unaligned drain_piece;
-            {
-                const u32* w = wr.ring_lane + ((drained >> 2) % RCX_OUT_RING_WORDS) * RCX_LANES; // (drained is a multiple of 16)
-                drain_piece.x = w[0];
-                drain_piece.y = w[RCX_LANES];
-                drain_piece.z = w[2 * RCX_LANES];
-                drain_piece.w = w[3 * RCX_LANES];
-            }
-            auto drain_store = [&]() {
-                const u32 limit = drain_p > RCX_OUT_MARGIN ? (drain_p - RCX_OUT_MARGIN) & ~15u : 0u;
-                drained = rcx_drain_piece(wr.ring_lane, payload, drained, limit < cap ? limit : cap, live, drain_piece);
-            };
+            RCX_MC_DRAIN_READ(drain_p, drain_piece, out_pos, wr, drained)
+            auto drain_store = [&]() { RCX_MC_DRAIN_STORE(drain_p, drain_piece, wr, payload, drained, cap, live) };
             if (k >= nchunks) drain_store();
             // ---- lookups: chunk k ----
             if (k < nchunks) {
@@ -329,21 +300,15 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool in_use = lane < lanes_used; // see rcx_enc_mc5_k
     const u64 blk = in_use ? (u64)blockIdx.x * lanes_used + lane : nblocks;
-    const bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY(g, blk, nblocks, n, block);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
     U4* ring = reinterpret_cast<U4*>(lds + RCX_STATIC_LDS_DW); // 16-byte aligned: RCX_STATIC_LDS_DW = 257 * 64 dwords
     u32* ring2 = reinterpret_cast<u32*>(ring + RCX_MC_RING_U4);
-    u32* final_low = ring2 + RCX_MC5_RING2_DW;
-    u32* out_ring = final_low + RCX_LANES;
-    u32* out_dummy = out_ring + RCX_OUT_RING_WORDS * RCX_LANES;
-    u32* out_pos = out_dummy + RCX_LANES;
-    u32* out_drained = out_pos + RCX_LANES;
+    RCX_MC_OUTPUT(oq, ring2 + RCX_MC5_RING2_DW);
 
     const u32 maxlen = rcx_wave_max(len);
+    // (RCX_ALL_FULL, but for the lanes that carry no block: they do not count)
     const bool full = !G::items && __all(!in_use || (live && len == block)) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
     const u32 nchunks = (maxlen + RCX_MC_CHUNK - 1) / RCX_MC_CHUNK;
 
@@ -407,7 +372,7 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     EncLane enc;
     enc.idle(wave_slots);
     StagedWriter wr;
-    wr.begin(out_ring, out_dummy, lane);
+    wr.begin(oq.ring, oq.dummy, lane);
     u32 drained = 0;
     if (wave == 1) {
         if (live) {
@@ -417,7 +382,7 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
             enc.off += RCX_STATIC_HEADER - 4;
             enc.cap -= RCX_STATIC_HEADER - 4;
         }
-        out_pos[lane] = 0;
+        oq.pos[lane] = 0;
     }
     rcx_lds_barrier();
     if (wave == 2) (void)tab.accumulate(); // cpprcoder.h:573-583; entry 256 = total
@@ -429,27 +394,16 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     u8* payload = wave_slots + (u64)lane * slot + RCX_STATIC_HEADER;
     const u32 cap = (((u32)slot - 4) & ~3u) - (RCX_STATIC_HEADER - 4);
     const bool narrow = __all(total >= 256u); // every wave sees the same table
-    if (full && narrow) rcx_static3_pipeline<true, false>(wave, lane, len, nchunks, in, tab, ring, ring2, enc, k, wr, out_pos, drained, payload, cap, live);
-    else if (full) rcx_static3_pipeline<true, true>(wave, lane, len, nchunks, in, tab, ring, ring2, enc, k, wr, out_pos, drained, payload, cap, live);
-    else rcx_static3_pipeline<false, true>(wave, lane, len, nchunks, in, tab, ring, ring2, enc, k, wr, out_pos, drained, payload, cap, live);
+    if (full && narrow) rcx_static3_pipeline<true, false>(wave, lane, len, nchunks, in, tab, ring, ring2, enc, k, wr, oq.pos, drained, payload, cap, live);
+    else if (full) rcx_static3_pipeline<true, true>(wave, lane, len, nchunks, in, tab, ring, ring2, enc, k, wr, oq.pos, drained, payload, cap, live);
+    else rcx_static3_pipeline<false, true>(wave, lane, len, nchunks, in, tab, ring, ring2, enc, k, wr, oq.pos, drained, payload, cap, live);
 
-    if (wave == 0) final_low[lane] = enc.low;
-    if (wave == 2) {
-        out_drained[lane] = drained;
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
-    }
-    rcx_lds_barrier();
+    RCX_MC_CLOSE_HANDOVER(wave, 2, oq, enc, drained);
     if (wave == 1 && live) {
-        u32 at2 = out_drained[lane];
-        const u32 flushed = wr.finish(enc);
-        const u32 end = flushed < cap ? flushed : cap;
-        for (; at2 < end; at2 += 4) *reinterpret_cast<u32*>(payload + at2) = wr.ring_lane[((at2 >> 2) % RCX_OUT_RING_WORDS) * RCX_LANES];
-        enc.low = final_low[lane];
+        RCX_MC_CLOSE_FLUSH(oq, wr, enc, payload, cap)
         if (enc.low == 0xFFFFFFFFu) enc.acc += 1; // cpprcoder.h:439-443
         const u32 bytes = enc.finish() + (RCX_STATIC_HEADER - 4);
-        sizes[blk] = enc.overflow ? (u32)slot : bytes;
-        if (enc.overflow) rcx_flag(status, RCX_ST_CAPACITY, rcx_id(g, blk));
-        redo[blk] = (wr.redo != 0 && !enc.overflow) ? 1u : 0u;
+        RCX_MC_CLOSE_REPORT(bytes, enc, wr, g, blk, slot, sizes, status, redo);
     } else if (wave == 1 && blk < nblocks) {
         redo[blk] = 0;
     }
@@ -468,15 +422,8 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     __shared__ u32 lds[RCX_STATIC_LDS_DW + RCX_RING_DW * RCX_LANES];
     const u32 lane = threadIdx.x;
     const u64 blk = (u64)blockIdx.x * RCX_LANES + lane;
-    bool live = blk < nblocks;
     // second pass behind rcx_dec_static_quad_k: only the blocks it marked (none, on valid input)
-    if (only) {
-        live = live && only[blk] != 0;
-        if (!__any(live)) return;
-    }
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
+    RCX_ENTRY_ONLY(g, blk, nblocks, n, block, only);
     StaticTable tab{lds + lane};
     u32* ring_col = lds + RCX_STATIC_LDS_DW + lane;
 
@@ -485,12 +432,10 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     u32 total = 1;
     for (u32 i = 0; i <= 256; ++i) tab.set(i, 0);
     if (live) {
-        const u64 sidx = rcx_stream_of(g, blk);
-        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
-        stream_len = s1 - s0;
-        const u8* s = comp + s0;
         // cpprcoder.h:474-493: at least the header, one more byte, then 5 bytes for the lead-in and low
-        bool good = s1 >= s0 && s1 <= comp_size && stream_len >= RCX_STATIC_HEADER + 5; // (an offset table that points past the buffer is not followed)
+        RCX_STREAM(g, blk, offsets);
+        const u8* s = comp + s0;
+        bool good = RCX_STREAM_OK(comp_size, RCX_STATIC_HEADER + 5);
         if (good) {
             const u32 declared = (u32)s[0] | ((u32)s[1] << 8) | ((u32)s[2] << 16) | ((u32)s[3] << 24);
             good = STREAM || declared == len;
@@ -524,7 +469,7 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     for (u32 q = 0; q < 15; ++q) coarse[q] = tab.get(16 * (q + 1));
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !G::items && !STREAM && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = !STREAM && RCX_ALL_FULL(g, block, dst);
     u8* out = dst + at;
     bool bad = false;
     u32 short_at = 0xFFFFFFFFu;
@@ -598,7 +543,7 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
 }
 
 // ===========================================================================
-// Static decode, 4 lanes per block: rcx_dec_quad_k's machinery (rcx_oct.hpp) with less to do per
+// Static decode, 4 lanes per block: rcx_dec_quad_k's machinery (rcx_quad.hpp) with less to do per
 // symbol -- the table never changes.  The block's 256 cumulative counts cum[1..256] (cpprcoder.h:573-583)
 // sit in LDS as 16 nodes of 16 entries in the same bank-conflict-free table groups; lane j keeps the
 // upper bounds of its four nodes, cum[16(4j+1)] .. cum[16(4j+4)], in registers for the whole block.
@@ -612,54 +557,36 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
 // A stream whose target runs past the table or that names a symbol of count 0 (damaged input) is marked in
 // `redo` and decoded by rcx_dec_static_k, which reports it the way the reference fails.
 // ===========================================================================
-#define RCX_SQUAD_LDS_BYTES (4 * RCX_QUAD_GROUP_BYTES + RCX_QUAD_BLOCKS * RCX_QUAD_RING_BYTES)
 template <int WAVES, class G = RcxBlocks>
 __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __restrict__ comp, u64 comp_size, const u64* __restrict__ offsets,
                                                                     u64 nblocks, u32 block, u64 n, u8* __restrict__ dst,
                                                                     u32* status, u32* __restrict__ redo, u32 quads_used, const G g = G())
 {
-    __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_SQUAD_LDS_BYTES];
-    const u32 lane = threadIdx.x & 63u;
-    const u32 wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    u8* lds = lds_all + wave_in_wg * RCX_SQUAD_LDS_BYTES;
-    const u32 j = lane & 3u, quad = lane >> 2;
-    const bool in_use = quad < quads_used; // see rcx_dec_quad_k: the other quads decode along and store nothing
-    const u64 blk = ((u64)blockIdx.x * WAVES + wave_in_wg) * quads_used + (quad & (quads_used - 1u));
-    bool live = blk < nblocks;
-    u64 at = live ? blk * (u64)block : 0;
-    u32 len = live ? (u32)((n - at) < (u64)block ? (n - at) : (u64)block) : 0u;
-    if constexpr (G::items) rcx_where(g, live, blk, at, len);
-
-    const u32 group = 2u * (quad >> 3) + ((0x96u >> (quad & 7u)) & 1u), quarter = (quad & 7u) >> 1; // see rcx_dec_quad_k
-    u8* mine = lds + group * RCX_QUAD_GROUP_BYTES + quarter * 64;
-    U4* leaves = reinterpret_cast<U4*>(mine) + j;
-    U4* parked = reinterpret_cast<U4*>(mine + 16 * 256);
-    u32* block_ring = reinterpret_cast<u32*>(lds + 4 * RCX_QUAD_GROUP_BYTES + quad * RCX_QUAD_RING_BYTES);
+    __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_QUAD_LDS_BYTES];
+    RCX_QUAD_SEAT(seat, WAVES, quads_used, lds_all, g, nblocks, n, block); // (as rcx_dec_quad_k)
 
     QuadInput in;
     u64 stream_len = 0;
     u32 U1 = 1, U2 = 2, U3 = 3, U4_ = 4, total = 4;
     if (live) {
-        const u64 sidx = rcx_stream_of(g, blk);
-        const u64 s0 = offsets[sidx], s1 = offsets[sidx + 1];
-        stream_len = s1 - s0;
-        const u8* s = comp + s0;
         // cpprcoder.h:474-493: at least the header, one more byte, then 5 bytes for the lead-in and low
-        bool good = s1 >= s0 && s1 <= comp_size && stream_len >= RCX_STATIC_HEADER + 5; // (an offset table that points past the buffer is not followed)
+        RCX_STREAM(g, seat.blk, offsets);
+        const u8* s = comp + s0;
+        bool good = RCX_STREAM_OK(comp_size, RCX_STATIC_HEADER + 5);
         if (good) {
             const u32 declared = (u32)s[0] | ((u32)s[1] << 8) | ((u32)s[2] << 16) | ((u32)s[3] << 24);
             good = declared == len;
         }
         if (good) {
             // cpprcoder.h:585-602 + :573-583: lane j takes the counts of symbols 64j .. 64j+63
-            const u8* cs = s + 4 + 128 * j;
+            const u8* cs = s + 4 + 128 * seat.j;
             u32 mysum = 0;
             for (u32 i = 0; i < 64; ++i) mysum += (u32)cs[2 * i] | ((u32)cs[2 * i + 1] << 8);
-            u32 run = rcx_quad_excl_scan(mysum, (j & 1u) ? ~0u : 0u, (j & 2u) ? ~0u : 0u);
+            u32 run = rcx_quad_excl_scan(mysum, (seat.j & 1u) ? ~0u : 0u, (seat.j & 2u) ? ~0u : 0u);
             for (u32 i = 0; i < 64; ++i) {
                 run += (u32)cs[2 * i] | ((u32)cs[2 * i + 1] << 8);
                 // entry e = 64j + i + 1 = cum[e] lives in node (e-1)/16 at position (e-1)%16
-                reinterpret_cast<u32*>(mine + (4 * j + (i >> 4)) * 256)[i & 15u] = run;
+                reinterpret_cast<u32*>(seat.mine + (4 * seat.j + (i >> 4)) * 256)[i & 15u] = run;
                 if (i == 15) U1 = run;
                 if (i == 31) U2 = run;
                 if (i == 47) U3 = run;
@@ -671,40 +598,36 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
         if (good) {
             // QuadInput::begin expects 4 size bytes + 4 bytes of low; the static stream has its lead-in byte in
             // between (low = bytes[1..4] after the header, cpprcoder.h:494-498): start it 3 bytes early
-            in.begin(s + RCX_STATIC_HEADER - 3, comp + s1, block_ring, parked + 3);
+            in.begin(s + RCX_STATIC_HEADER - 3, comp + s1, seat.ring, seat.parked + 3);
             in.range = 0xFFFFFFFFu;
         } else {
-            if (j == 0 && in_use) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
-            live = false;
-            len = 0;
+            RCX_QUAD_FAIL(seat, g, status)
         }
     }
     if (!live) {
-        in.idle(comp, block_ring, parked + 3);
+        in.idle(comp, seat.ring, seat.parked + 3);
         U1 = 1, U2 = 2, U3 = 3, U4_ = 4, total = 4;
         U4 v;
         v.x = v.y = v.z = v.w = 4;
-        for (u32 q = 0; q < 16; ++q) leaves[q * 16] = v;
+        for (u32 q = 0; q < 16; ++q) seat.leaves[q * 16] = v;
     }
     {
         U4 v; // the scratch row ("node 16", reached only by a target past the table)
         v.x = v.y = v.z = v.w = 0;
-        leaves[16 * 16] = v;
+        seat.leaves[16 * 16] = v;
     }
     const DivEntry k = rcx_make_div_entry(total);
     const u64 kadd = k.add;
 
     const u32 maxlen = rcx_wave_max(len);
-    const bool full = !G::items && __all(live && len == block) && (block % 16u == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+    const bool full = RCX_ALL_FULL(g, block, dst);
     u8* out = dst + at;
-    const bool leader = live && in_use && j == 0;
-    const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(leaves);
-    const u32 ring_lds = (u32)reinterpret_cast<uintptr_t>(block_ring);
+    const bool leader = live && seat.in_use && seat.j == 0;
+    const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(seat.leaves);
+    const u32 ring_lds = (u32)reinterpret_cast<uintptr_t>(seat.ring);
     u32 worst_node = 0;            // 16 = a target past the table
     u32 least_range = 0xFFFFFFFFu; // 0 = a symbol of count 0
 
-#define RCX_QP1 "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define RCX_QP2 "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
     // One symbol (instruction sequences as in rcx_dec_quad_k: no compare result or DPP source is used before two
     // other instructions have been issued).  Every lane of the quad ORs the symbol into WORD at bit SHIFT.
     // (as in rcx_dec_quad_k, what the coder state does not need -- the symbol's byte, the watch on the smallest range -- is
@@ -776,31 +699,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
                      : [w0] "v"(in.w0), [w1] "v"(in.w1), [bp] "v"(in.bp8), [swap] "s"(0x00010203u),        \
                        [pnd] "v"(p_nd_), [pnb] "v"(p_nb_), [prg] "v"(p_rg_), [psh] "n"(PSHIFT));           \
         const u32 q1_ = l_.x * t_, q2_ = l_.y * t_, q3_ = l_.z * t_, q4_ = l_.w * t_;                      \
-        u32 lo_, rg_, nb_, hi_, y1_, y2_, y3_, y4_;                                                        \
-        asm volatile("v_sub_co_u32_e64 %[y1], %[c1], %[low], %[q1]\n\t"                                    \
-                     "v_sub_co_u32_e64 %[y2], %[c2], %[low], %[q2]\n\t"                                    \
-                     "v_sub_co_u32_e64 %[y3], %[c3], %[low], %[q3]\n\t"                                    \
-                     "v_sub_co_u32_e64 %[y4], %[c4], %[low], %[q4]\n\t"                                    \
-                     "v_subb_co_u32_e64 %[nb], %[c1], 4, 0, %[c1]\n\t"                                     \
-                     "v_min3_u32 %[lo], %[y1], %[y2], %[y3]\n\t"                                           \
-                     "v_subb_co_u32_e64 %[nb], %[c2], %[nb], 0, %[c2]\n\t"                                 \
-                     "v_max3_u32 %[hi], %[y1], %[y2], %[y3]\n\t"                                           \
-                     "v_subb_co_u32_e64 %[nb], %[c3], %[nb], 0, %[c3]\n\t"                                 \
-                     "v_min3_u32 %[lo], %[lo], %[y4], %[rem]\n\t"                                          \
-                     "v_subb_co_u32_e64 %[nb], %[c4], %[nb], 0, %[c4]\n\t"                                 \
-                     "v_max_u32 %[hi], %[hi], %[y4]\n\t"                                                   \
-                     "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP1                                          \
-                     "v_add_u32_dpp %[nb], %[nb], %[nb] " RCX_QP1                                          \
-                     "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP1                                          \
-                     "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP2                                          \
-                     "v_add_u32_dpp %[nb], %[nb], %[nb] " RCX_QP2                                          \
-                     "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP2                                          \
-                     "v_sub_u32 %[rg], %[lo], %[hi]"                                                       \
-                     : [lo] "=&v"(lo_), [rg] "=&v"(rg_), [nb] "=&v"(nb_), [hi] "=&v"(hi_), [y1] "=&v"(y1_), \
-                       [y2] "=&v"(y2_), [y3] "=&v"(y3_), [y4] "=&v"(y4_), [c1] "=&s"(c1_), [c2] "=&s"(c2_),  \
-                       [c3] "=&s"(c3_), [c4] "=&s"(c4_)                                                    \
-                     : [low] "v"(in.low), [q1] "v"(q1_), [q2] "v"(q2_), [q3] "v"(q3_), [q4] "v"(q4_),      \
-                       [rem] "v"(rem_));                                                                   \
+        RCX_QUAD_ROUND2_CUM(in.low, q1_, q2_, q3_, q4_);                                                   \
         in.low = lo_;   /* :504 */                                                                         \
         in.range = rg_; /* :505 */                                                                         \
         p_nd_ = node_;  /* the symbol = node << 4 | nb, in all four lanes */                                \
@@ -809,62 +708,31 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_static_quad_k(const u8* __
     }
 
     if (full) {
-        U4 o_last;
+        U4 o_last; // (RCX_QUAD_PARKED_*, rcx_quad.hpp)
         o_last.x = o_last.y = o_last.z = o_last.w = 0;
         for (u32 i0 = 0; i0 < maxlen; i0 += 16) {
             in.topup();
-            const u32 g = (i0 >> 4) & 3u;
-            if (g == 0 && i0 != 0 && leader) { // see rcx_dec_quad_k: the stores follow the top-up
-                U4* o4 = reinterpret_cast<U4*>(out + (i0 - 64));
-                const U4 p0 = parked[0], p1 = parked[1], p2 = parked[2];
-                o4[0] = p0;
-                o4[1] = p1;
-                o4[2] = p2;
-                o4[3] = o_last;
-            }
+            RCX_QUAD_PARKED_FLUSH(i0, seat.parked, o_last, G::items)
             u32 w0_ = 0, w1_ = 0, w2_ = 0, w3_ = 0;
-            RCX_SQUAD_SYMBOL(0, w0_, 0) RCX_SQUAD_SYMBOL(1, w0_, 0) RCX_SQUAD_SYMBOL(1, w0_, 8) RCX_SQUAD_SYMBOL(1, w0_, 16)
-            RCX_SQUAD_SYMBOL(1, w0_, 24) RCX_SQUAD_SYMBOL(1, w1_, 0) RCX_SQUAD_SYMBOL(1, w1_, 8) RCX_SQUAD_SYMBOL(1, w1_, 16)
-            RCX_SQUAD_SYMBOL(1, w1_, 24) RCX_SQUAD_SYMBOL(1, w2_, 0) RCX_SQUAD_SYMBOL(1, w2_, 8) RCX_SQUAD_SYMBOL(1, w2_, 16)
-            RCX_SQUAD_SYMBOL(1, w2_, 24) RCX_SQUAD_SYMBOL(1, w3_, 0) RCX_SQUAD_SYMBOL(1, w3_, 8) RCX_SQUAD_SYMBOL(1, w3_, 16)
-            RCX_SQUAD_FINISH(w3_, 24)
+            RCX_QUAD_16_SYMBOLS(RCX_SQUAD_SYMBOL, RCX_SQUAD_FINISH)
             U4 o;
             o.x = w0_;
             o.y = w1_;
             o.z = w2_;
             o.w = w3_;
-            if (g == 3) o_last = o;
-            else parked[g] = o;
+            RCX_QUAD_PARKED_PUT(o, seat.parked, o_last);
         }
-        if (leader && maxlen != 0) {
-            const u32 groups = ((maxlen - 1) >> 4 & 3u) + 1;
-            U4* o4 = reinterpret_cast<U4*>(out + ((maxlen - 1) & ~63u));
-            o4[0] = parked[0];
-            if (groups > 1) o4[1] = parked[1];
-            if (groups > 2) o4[2] = parked[2];
-            if (groups > 3) o4[3] = o_last;
-        }
+        RCX_QUAD_PARKED_END(maxlen, seat.parked, o_last, G::items)
     } else {
-        for (u32 i = 0; i < maxlen; ++i) {
-            if ((i & 15u) == 0) in.topup();
-            if (i < len) { // the 4 lanes of a quad agree
-                u32 sym = 0;
-                RCX_SQUAD_SYMBOL(0, sym, 0);
-                RCX_SQUAD_FINISH(sym, 0);
-                if (leader) out[i] = (u8)sym;
-            }
-        }
+        RCX_QUAD_TAIL(0u, , RCX_SQUAD_SYMBOL, RCX_SQUAD_FINISH, )
     }
 #undef RCX_SQUAD_SYMBOL
 #undef RCX_SQUAD_FINISH
 #undef RCX_SQ_PREV_0
 #undef RCX_SQ_PREV_1
-#undef RCX_QP1
-#undef RCX_QP2
     // the normalisation after the last symbol (it decides whether the input was long enough, cpprcoder.h:506-509)
     in.bp8 += rcx_clz(in.range) & 0x18u;
     const bool marked = live && (worst_node >= 16u || least_range == 0);
-    if (leader && !marked && in.taken() + (RCX_STATIC_HEADER - 3) > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, blk));
-    if (leader) redo[blk] = marked ? 1u : 0u;
-    else if (j == 0 && in_use && blk < nblocks) redo[blk] = 0;
+    if (leader && !marked && in.taken() + (RCX_STATIC_HEADER - 3) > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, seat.blk));
+    RCX_QUAD_MARK_REDO(seat, redo, nblocks, marked);
 }

@@ -1,6 +1,6 @@
 // rcx_variants.hpp -- superseded kernels, kept selectable (RCX_ENC_VARIANT=1/2, RCX_LANES_PER_BLOCK=8) so that
 // tests/test_gpu_parity.py::test_every_kernel_variant_is_bit_identical and the sweeps can compare them with the
-// defaults in rcx_oct.hpp.  Included after rcx_oct.hpp by rcx_kernels.hpp.
+// defaults in rcx_quad.hpp and rcx_mc.hpp.  Included after them by rcx_kernels.hpp.
 //
 // rcx_enc_oct_k / rcx_dec_oct_k -- why 8 lanes per block.  A block is one serial chain per symbol, so 1 GiB of 64 KiB blocks
 // offers only 16384 chains.  With one lane per block that is 256 waves -- one per CU, three

@@ -1,4 +1,4 @@
-"""The quad decoder's divisors (rcx_oct.hpp, RCX_QUAD_DIVQ_DW): multiplier and increment per symbol from global memory,
+"""The quad decoder's divisors (rcx_quad.hpp, RCX_QUAD_DIVQ_DW): multiplier and increment per symbol from global memory,
 the shift per group of 16 symbols.
 
 Round trips through the device entry points at the places that arrangement depends on: block lengths around the totals

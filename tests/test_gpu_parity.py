@@ -291,7 +291,7 @@ def test_carry_through_long_runs_of_ff(ctx, oracle):
 
 def test_carries_at_many_output_positions(ctx, oracle):
     """The multi-wave encoder's writer mirrors a window of the newest eight bytes into a 256-byte ring and lets a carry that
-    runs through more than four bytes go on in the ring (csrc/rcx_oct.hpp StagedWriter): runs of 4 .. 40 held 0xFF bytes
+    runs through more than four bytes go on in the ring (csrc/rcx_mc.hpp StagedWriter): runs of 4 .. 40 held 0xFF bytes
     that begin at many places of a block -- whatever their position relative to the ring's wrap, a word boundary, a chunk
     of 16 symbols -- must give the reference's stream."""
     import carry_runs

@@ -2,7 +2,12 @@
 """Is the device code of two builds the same?  Compares two gfx950 assembly files (hipcc --save-temps:
 rcx_api-hip-amdgcn-amd-amdhsa-gfx950.s) kernel by kernel: the set of kernels, each one's instruction text and its
 .amdhsa_* descriptor.  The order in which the kernels were emitted may differ; local labels (.LBB<function>_<n>) are
-compared without the function's number.  For a change that is meant to touch the host side only.
+compared without the function's number.  For a change that is meant to leave the device code alone: host-side work, or
+device source that only moves.  Every kernel is put into a class:
+    same    descriptor and instruction text identical
+    moved   descriptor identical, the same number of basic blocks, and each basic block holds the same multiset of
+            instructions once register numbers are masked (the compiler scheduled or numbered a stretch differently)
+    differs anything else; the exit status is non-zero if there is one, or if the sets of kernels differ
 
     python tools/diag/kernel_diff.py before/rcx_api-hip-amdgcn-amd-amdhsa-gfx950.s after/rcx_api-hip-amdgcn-amd-amdhsa-gfx950.s
 """
@@ -24,15 +29,43 @@ def kernels(path):
     return out
 
 
+def blocks(text):
+    """The basic blocks of a kernel, in order: a label begins one, a branch or s_endpgm ends one.  Each as the sorted
+    list of its instructions with register numbers masked (v12 -> v#, s[4:5] -> s[#], vcc / exec / m0 stay)."""
+    out, cur = [], []
+    for line in text.split("\n"):
+        ins = re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", line.strip())
+        if ins.endswith(":") and cur:
+            out.append(sorted(cur))
+            cur = []
+        cur.append(ins)
+        if re.match(r"s_c?branch|s_endpgm|s_setpc", ins):
+            out.append(sorted(cur))
+            cur = []
+    return out + ([sorted(cur)] if cur else [])
+
+
+def classify(a, b):
+    if a[0] is None or b[0] is None or a[1] != b[1]:
+        return "differs"
+    if a[0] == b[0]:
+        return "same"
+    return "moved" if blocks(a[0]) == blocks(b[0]) else "differs"
+
+
 def main():
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-    differ = [k for k in sorted(set(a) & set(b)) if a[k] != b[k] or a[k][0] is None]
-    print(f"{len(a)} kernels before, {len(b)} after; only before {len(only_a)}, only after {len(only_b)}, "
-          f"instruction text or descriptor differs {len(differ)}")
-    for what, names in (("only before", only_a), ("only after", only_b), ("differs", differ)):
+    cls = {k: classify(a[k], b[k]) for k in sorted(set(a) & set(b))}
+    moved, differ = [k for k in cls if cls[k] == "moved"], [k for k in cls if cls[k] == "differs"]
+    print(f"{len(a)} kernels before, {len(b)} after; only before {len(only_a)}, only after {len(only_b)}; "
+          f"same {len(cls) - len(moved) - len(differ)}, moved {len(moved)}, differs {len(differ)}")
+    for what, names in (("only before", only_a), ("only after", only_b), ("moved", moved), ("differs", differ)):
         for k in names:
             print(f"  {what}: {k}")
+    if "-v" in sys.argv[3:]:
+        for k in cls:
+            print(f"  {cls[k]:8s}{k}")
     raise SystemExit(1 if only_a or only_b or differ else 0)
 
 
