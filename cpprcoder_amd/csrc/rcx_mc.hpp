@@ -1,7 +1,7 @@
 // rcx_mc.hpp -- the multi-wave range encoders' machinery, and the adaptive one itself:
 //   the rings between the waves, rcx_lds_barrier, StagedWriter (the byte writer whose words leave through LDS), the
 //   drain of its rings, the output-ring layout (McOutput), the writer and drain stages and the closing stage
-//   rcx_enc_mc5_k    adaptive encode, five waves per 64 blocks (model x3 / arithmetic / writer) + the drain wave
+//   rcx_enc_mc5_k    adaptive encode, seven waves per 64 blocks (model x4 / arithmetic / writer / drain)
 // rcx_enc_static3_k (rcx_static.hpp) is built on the same machinery.
 #pragma once
 // included by rcx_kernels.hpp behind rcx_quad.hpp (uses rcx_flag, rcx_wave_max, rcx_byte_of; RcxV4, RcxLdsU32 from rcx_quad.hpp)
@@ -45,22 +45,17 @@ struct alignas(16) DivQ {
 // The drain keeps the newest RCX_OUT_MARGIN bytes back, so that a carry that runs through more than the newest four
 // bytes (cpprcoder.h:767-781) is resolved in LDS; a run of 0xFF bytes longer than that margin cannot be,
 // and such a block is marked in `redo` and encoded again by rcx_enc_adaptive_k.
-// Level 3 of the model (one group per block) lives in registers of the levels-3+2 wave, the other levels in LDS.
+// Level 3 of the model (one group per block) lives in registers of a wave of its own, the other levels in LDS.
 // ===========================================================================
-// Which wave drains the output rings: 5 = a sixth wave that does nothing else (default), 4 = the level-1 model wave (shares
-// its SIMD with the arithmetic wave), 3 = the leaf wave.  The kernel's wave ROLES are numbered 0 arithmetic, 1 writer,
-// 2 model levels 3+2, 3 model leaf level, 4 model level 1, 5 drain; with six waves the hardware's waves 1 and 3 swap roles,
-// so that (a workgroup's wave i runs on SIMD i mod 4) the drain shares a SIMD with the leaf wave, which has the most room.
-#if !defined(RCX_DRAIN_WAVE)
+// The kernel's wave ROLES are numbered 0 arithmetic, 1 writer, 2 model level 2, 3 model leaf level, 4 model level 1,
+// 5 drain (a wave that does nothing else), 6 model level 3.  A workgroup's wave i runs on SIMD i mod 4, and a wave that
+// is alone on its SIMD pays 4 cycles for every wait and scalar instruction and 12-28 for every LDS instruction, which a
+// second wave hides.  The hardware's waves 1 and 3 swap roles, so that the pairs are arithmetic + level 1, leaf + drain
+// and level 2 + level 3; the writer is alone.
 #define RCX_DRAIN_WAVE 5
-#endif
-#if RCX_DRAIN_WAVE == 5
-#define RCX_MC5_THREADS 384
-#define RCX_MC5_ROLE(HW) ((HW) == 1u ? 3u : (HW) == 3u ? 1u : (HW))
-#else
-#define RCX_MC5_THREADS 320
-#define RCX_MC5_ROLE(HW) (HW)
-#endif
+#define RCX_L3_WAVE 6
+#define RCX_MC5_THREADS 448
+#define RCX_MC5_ROLE(HW) ((0x6541230u >> (4u * (HW))) & 15u) /* one hex digit per hardware wave, wave 0 lowest */
 // The ring between the model waves and the arithmetic wave: four dwords per symbol and lane.  Kept as 16 contiguous
 // bytes per lane (one ds_read_b128 for the arithmetic wave; the model waves' 4-byte stores hit each bank four times)
 // or, RCX_RING_PLANAR=1, as four dword planes (conflict-free stores, two ds_read2st64_b32).
@@ -84,7 +79,10 @@ struct alignas(16) DivQ {
 #define RCX_OUT_RING_WORDS 64 /* per block: 256 bytes of output waiting in LDS */
 #define RCX_OUT_MARGIN 32     /* bytes kept back from the drain */
 #define RCX_MC5_OUT_DW (RCX_OUT_RING_WORDS * RCX_LANES + 3 * RCX_LANES)
-#define RCX_MC5_LDS_U4 (RCX_MC_LDS_U4 + RCX_MC5_RING2_DW / 4 + RCX_LANES / 4 + RCX_MC5_OUT_DW / 4)
+// The level-3 wave's sums: a fifth value per symbol and lane, in a dword plane of its own beside the ring (the ring's record
+// stays the 16 bytes per lane that the arithmetic wave reads at once), double-buffered like it, behind the output rings.
+#define RCX_MC5_RING3_DW (2 * RCX_MC_CHUNK * RCX_LANES)
+#define RCX_MC5_LDS_U4 (RCX_MC_LDS_U4 + RCX_MC5_RING2_DW / 4 + RCX_LANES / 4 + RCX_MC5_OUT_DW / 4 + RCX_MC5_RING3_DW / 4)
 
 struct __attribute__((packed, aligned(4))) RcxU4Unaligned {
     u32 x, y, z, w;
@@ -228,8 +226,11 @@ struct StagedWriter {
         u32 at = (u32)reinterpret_cast<uintptr_t>(ring_lane + (((pos8 - 40u) >> 5) % RCX_OUT_RING_WORDS) * RCX_LANES);
         asm volatile("" : "+v"(sh8), "+v"(at));
         acc = ((u64)((u32)(acc >> 32) + (far ? 1u : 0u)) << 32) | lo1;
-        if (rcx_any(far)) redo |= rcx_stage_far_carry(ring_lane, acc, pos8, safe_from, far ? 1u : 0u);
+        // (the far carry is looked at BEHIND the words' write: a branch on VCC directly behind the add that sets it held the
+        // wave for 24 cycles a symbol.  rcx_stage_far_carry writes the two newest words itself, so the order does not matter
+        // to what the ring holds afterwards.)
         mirror_at(sh8, at);
+        if (rcx_any(far)) redo |= rcx_stage_far_carry(ring_lane, acc, pos8, safe_from, far ? 1u : 0u);
         const u32 k8 = rec & 0x18u;
         acc = (acc << k8) | __builtin_amdgcn_ubfe(rec, 32u - k8, k8); // the k8 / 8 bytes that leave through the top of low
         pos8 += k8;
@@ -337,18 +338,23 @@ struct McOutput {
 template <bool FULL>
 __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u32 nchunks, const u8* in,
                                                  const DivEntry* __restrict__ divtab, const Tree& tree, DivEntry* stage,
-                                                 u32* ring, u32* ring2, EncLane& enc, DivEntry& ahead, StagedWriter& wr,
+                                                 u32* ring, u32* ring2, u32* ring3, EncLane& enc, DivEntry& ahead, StagedWriter& wr,
                                                  u32* out_pos, u32& drained, u8* payload, u32 cap, bool live)
 {
-    // wave roles: 0 arithmetic, 1 writer, 2 model levels 3+2, 3 model leaf level, 4 model level 1 + drain
+    // wave roles: 0 arithmetic, 1 writer, 2 model level 2, 3 model leaf level, 4 model level 1, 5 drain, 6 model level 3
 #if defined(RCX_STAMP)
     unsigned long long stamp_wait_ = 0;
     const unsigned long long stamp_begin_ = __builtin_amdgcn_s_memtime();
 #endif
+    // Two waves of a SIMD share its issue slots by priority, then age.  The level-1 wave is the younger one beside the
+    // arithmetic wave and was the kernel's pole (busy 174 of 177 cycles a symbol); the arithmetic wave has 45 to give.
+    // (Measured on full 64 KiB blocks, 64 to a workgroup; set for the guarded pipeline and single streams as well, where
+    // its effect is not measured.  It changes the order in which instructions issue, never a result.)
+    if (wave == 4) __builtin_amdgcn_s_setprio(1);
     U4 piece_ahead;
     piece_ahead.x = piece_ahead.y = piece_ahead.z = piece_ahead.w = 0;
-    if (FULL && wave >= 2 && wave <= 4 && nchunks > 0) piece_ahead = *reinterpret_cast<const U4*>(in);
-    u32 l3a = 64, l3b = 128, l3c = 192; // wave 2: the level-3 sums (cpprcoder.h:1094-1132: every count 1)
+    if (FULL && wave >= 2 && wave != RCX_DRAIN_WAVE && nchunks > 0) piece_ahead = *reinterpret_cast<const U4*>(in);
+    u32 l3a = 64, l3b = 128, l3c = 192; // level-3 wave: its sums (cpprcoder.h:1094-1132: every count 1)
     for (u32 k = 0; k <= nchunks + 1; ++k) {
         if (wave == 0) {
             // ---- arithmetic: chunk k-1, records into ring2[(k-1)&1] ----
@@ -365,6 +371,7 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                 }
                 // the model waves' answers: field f of symbol s of lane l at dword RCX_RING_AT(s, f) + RCX_RING_LANE * l
                 const u32* rs = ring + ((k - 1) & 1u) * (4 * RCX_MC_CHUNK * RCX_LANES) + RCX_RING_LANE * lane;
+                const u32* rs3 = ring3 + ((k - 1) & 1u) * (RCX_MC_CHUNK * RCX_LANES) + lane; // (level 3: two symbols per ds_read2st64_b32)
                 u32* ws2 = ring2 + ((k - 1) & 1u) * (RCX_MC_CHUNK * RCX_LANES) + lane;
                 // the chunk's divisors through one vector base register and immediate offsets (a wave-uniform
                 // address would be rebuilt in a scalar register and moved over for every read)
@@ -372,12 +379,14 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                 asm volatile("" : "+v"(st_lds));
                 const RcxLdsDivQ* st = reinterpret_cast<const RcxLdsDivQ*>(st_lds);
                 U4 eq[RCX_MC_CHUNK];
+                u32 c3q[RCX_MC_CHUNK];
                 RcxDivQv kq[RCX_MC_CHUNK];
                 u32 rec_even = 0;
 #define RCX_A_ISSUE(T)                                                                                              \
     {                                                                                                               \
         eq[T].x = rs[RCX_RING_AT((T), 0)], eq[T].y = rs[RCX_RING_AT((T), 1)], eq[T].z = rs[RCX_RING_AT((T), 2)];    \
         eq[T].w = rs[RCX_RING_AT((T), 3)];                                                                          \
+        if (((T)&1u) == 0) c3q[T] = rs3[(T)*RCX_LANES], c3q[(T) + 1] = rs3[((T) + 1) * RCX_LANES];                   \
         kq[T] = st[T];                                                                                              \
     }
 #pragma unroll
@@ -388,7 +397,7 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                     const U4 e = eq[s];
                     const RcxDivQv kk = kq[s];
                     u32 rec = 0; // past the end of a short block: a record that does nothing
-                    if (FULL || i0 + s < len) rec = enc.arith_q(e.x + e.y + e.z, e.w, kk.x, kk.y, ((u64)kk.w << 32) | kk.z);
+                    if (FULL || i0 + s < len) rec = enc.arith_q(e.x + e.y + e.z + c3q[s], e.w, kk.x, kk.y, ((u64)kk.w << 32) | kk.z);
                     // two symbols' records leave as one ds_write2st64_b32 (consecutive symbols are 64 dwords apart): an LDS
                     // instruction costs a lone wave 12-16 cycles of issue whatever it carries (tools/diag/ubench.hip k_t_*)
                     if ((s & 1u) == 0) rec_even = rec;
@@ -401,29 +410,19 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
             }
         } else if (wave == 1) {
             RCX_MC_WRITER_STAGE(k, ring2, wr, out_pos) // chunk k-2
-        } else {
-          // ---- drain: asked for here, stored behind the chunk's model work ----
-          u32 drain_p = 0;
-          RcxU4Unaligned drain_piece;
-          drain_piece.x = drain_piece.y = drain_piece.z = drain_piece.w = 0;
-          if (wave == RCX_DRAIN_WAVE) RCX_MC_DRAIN_READ(drain_p, drain_piece, out_pos, wr, drained)
-          auto drain_store = [&]() { RCX_MC_DRAIN_STORE(drain_p, drain_piece, wr, payload, drained, cap, live) };
-          if ((k >= nchunks || RCX_DRAIN_WAVE == 5) && wave == RCX_DRAIN_WAVE) drain_store(); // (a wave that only drains: nothing to wait for)
-          if (k < nchunks && wave <= 4) {
+        } else if (wave == RCX_DRAIN_WAVE) {
+            // ---- drain: what the writer had a barrier ago ----
+            u32 drain_p;
+            RcxU4Unaligned drain_piece;
+            RCX_MC_DRAIN_READ(drain_p, drain_piece, out_pos, wr, drained)
+            RCX_MC_DRAIN_STORE(drain_p, drain_piece, wr, payload, drained, cap, live)
+        } else if (k < nchunks) {
             // ---- model: chunk k ----
             const u32 i0 = k * RCX_MC_CHUNK;
             u32* ws = ring + (k & 1u) * (4 * RCX_MC_CHUNK * RCX_LANES) + RCX_RING_LANE * lane;
             U4 piece;
-            if (FULL) piece = piece_ahead;
-            if (RCX_DRAIN_WAVE != 5 && wave == RCX_DRAIN_WAVE) {
-                // The stores go out between the wait for this chunk's input (asked for a chunk ago: it is there) and the
-                // request for the next chunk's: memory operations complete in order as far as s_waitcnt vmcnt can tell, so
-                // a wait for input behind a store just issued would wait for that store (that was 28 cycles a symbol on
-                // the SIMD this wave shares with the arithmetic wave).
-                if (FULL) asm volatile("" ::"v"(piece.x), "v"(piece.y), "v"(piece.z), "v"(piece.w));
-                drain_store();
-            }
             if (FULL) {
+                piece = piece_ahead;
                 if (k + 1 < nchunks) piece_ahead = *reinterpret_cast<const U4*>(in + i0 + RCX_MC_CHUNK);
             } else if (i0 + RCX_MC_CHUNK <= len && (reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
                 piece = *reinterpret_cast<const U4*>(in + i0); // a whole, aligned chunk of a ragged block (or of a single stream)
@@ -456,29 +455,7 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                 for (u32 s = 0; s < RCX_MC_CHUNK; ++s) {
                     if (s + RCX_MODEL_AHEAD < RCX_MC_CHUNK) RCX_M2_ISSUE(s + RCX_MODEL_AHEAD);
                     const u32 cc = rcx_byte_of(piece, s);
-                    // Level 3 -- one group per block -- lives in registers as three prefix sums (symbols below 64, 128,
-                    // 192 so far): three compares serve both the select and the update (an LDS read, a ds_add and the
-                    // masked sum cost this wave, the kernel's busiest, 20 cycles a symbol more).
-                    u32 cum3;
-                    if (FULL) {
-                        u64 m1_, m2_, m3_, cz_;
-                        asm volatile("v_cmp_gt_u32_e64 %[m3], %[k192], %[c]\n\t" /* (no literals in this encoding: 192, 128 from registers) */
-                                     "v_cmp_gt_u32_e64 %[m2], %[k128], %[c]\n\t"
-                                     "v_cmp_gt_u32_e64 %[m1], 64, %[c]\n\t"
-                                     "v_cndmask_b32_e64 %[x], %[pc], %[pb], %[m3]\n\t"
-                                     "v_cndmask_b32_e64 %[x], %[x], %[pa], %[m2]\n\t"
-                                     "v_cndmask_b32_e64 %[x], %[x], 0, %[m1]\n\t"
-                                     "v_addc_co_u32_e64 %[pc], %[cz], %[pc], 0, %[m3]\n\t"
-                                     "v_addc_co_u32_e64 %[pb], %[cz], %[pb], 0, %[m2]\n\t"
-                                     "v_addc_co_u32_e64 %[pa], %[cz], %[pa], 0, %[m1]"
-                                     : [x] "=&v"(cum3), [pa] "+v"(l3a), [pb] "+v"(l3b), [pc] "+v"(l3c), [m1] "=&s"(m1_), [m2] "=&s"(m2_),
-                                       [m3] "=&s"(m3_), [cz] "=&s"(cz_)
-                                     : [c] "v"(cc), [k192] "s"(192u), [k128] "s"(128u));
-                    } else {
-                        cum3 = cc < 64u ? 0u : (cc < 128u ? l3a : (cc < 192u ? l3b : l3c));
-                        if (i0 + s < len) l3a += cc < 64u ? 1u : 0u, l3b += cc < 128u ? 1u : 0u, l3c += cc < 192u ? 1u : 0u;
-                    }
-                    const u32 sum32 = cum3 + rcx_pre4(gb[s], (cc >> 4) & 3);
+                    const u32 sum32 = rcx_pre4(gb[s], (cc >> 4) & 3);
                     if (FULL) { // (pairs: one ds_write2st64_b32)
                         if ((s & 1u) == 0) held = sum32;
                         else ws[RCX_RING_AT(s - 1, 0)] = held, ws[RCX_RING_AT(s, 0)] = sum32;
@@ -505,6 +482,31 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                     } else if (i0 + s < len) ws[RCX_RING_AT(s, 1)] = sum1;
                 }
 #undef RCX_M1_ISSUE
+            } else if (wave == RCX_L3_WAVE) {
+                // Level 3 -- one group per block -- lives in registers as three prefix sums (symbols below 64, 128, 192 so
+                // far): three compares serve both the select and the update.  No LDS access but the hand-over, and no test
+                // for the end of a short block: what follows a block's last symbol is never read.
+                u32* ws3 = ring3 + (k & 1u) * (RCX_MC_CHUNK * RCX_LANES) + lane;
+#pragma unroll
+                for (u32 s = 0; s < RCX_MC_CHUNK; ++s) {
+                    const u32 cc = rcx_byte_of(piece, s);
+                    u32 cum3;
+                    u64 m1_, m2_, m3_, cz_;
+                    asm volatile("v_cmp_gt_u32_e64 %[m3], %[k192], %[c]\n\t" /* (no literals in this encoding: 192, 128 from registers) */
+                                 "v_cmp_gt_u32_e64 %[m2], %[k128], %[c]\n\t"
+                                 "v_cmp_gt_u32_e64 %[m1], 64, %[c]\n\t"
+                                 "v_cndmask_b32_e64 %[x], %[pc], %[pb], %[m3]\n\t"
+                                 "v_cndmask_b32_e64 %[x], %[x], %[pa], %[m2]\n\t"
+                                 "v_cndmask_b32_e64 %[x], %[x], 0, %[m1]\n\t"
+                                 "v_addc_co_u32_e64 %[pc], %[cz], %[pc], 0, %[m3]\n\t"
+                                 "v_addc_co_u32_e64 %[pb], %[cz], %[pb], 0, %[m2]\n\t"
+                                 "v_addc_co_u32_e64 %[pa], %[cz], %[pa], 0, %[m1]"
+                                 : [x] "=&v"(cum3), [pa] "+v"(l3a), [pb] "+v"(l3b), [pc] "+v"(l3c), [m1] "=&s"(m1_), [m2] "=&s"(m2_),
+                                   [m3] "=&s"(m3_), [cz] "=&s"(cz_)
+                                 : [c] "v"(cc), [k192] "s"(192u), [k128] "s"(128u));
+                    if ((s & 1u) == 0) held = cum3; // (pairs: one ds_write2st64_b32)
+                    else ws3[(s - 1) * RCX_LANES] = held, ws3[s * RCX_LANES] = cum3;
+                }
             } else {
 #define RCX_M0_ISSUE(T)                                                       \
     {                                                                         \
@@ -532,7 +534,6 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                 }
 #undef RCX_M0_ISSUE
             }
-          }
         }
 #if defined(RCX_STAMP)
         const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
@@ -558,7 +559,7 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
 {
     __shared__ U4 lds[RCX_MC5_LDS_U4];
     const u32 lane = threadIdx.x & 63u;
-    const u32 wave = RCX_MC5_ROLE(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); // the wave's ROLE (see RCX_DRAIN_WAVE)
+    const u32 wave = RCX_MC5_ROLE(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); // the wave's ROLE (see RCX_MC5_ROLE)
     // lanes_used (1..64) of the 64 lanes carry a block; the others idle along (rcx_api.hip picks it from the
     // block count so that every CU has a workgroup before any workgroup carries 64 blocks)
     const bool in_use = lane < lanes_used;
@@ -570,6 +571,7 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     u32* ring = reinterpret_cast<u32*>(lds + RCX_LDS_U4);
     u32* ring2 = reinterpret_cast<u32*>(lds + RCX_MC_LDS_U4);
     RCX_MC_OUTPUT(oq, ring2 + RCX_MC5_RING2_DW);
+    u32* ring3 = oq.drained + RCX_LANES;
 
     const u32 maxlen = rcx_wave_max(len);
     bool full;
@@ -600,7 +602,7 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     } else if (wave == 1) {
         if (live) enc.begin(wave_slots, lane * (u32)slot, (u32)slot, len);
         oq.pos[lane] = 0;
-    } else if (wave == 2) { // cpprcoder.h:1094-1132: every count 1
+    } else if (wave == 2) { // cpprcoder.h:1094-1132: every count 1 (level 3: registers of rcx_mc5_pipeline)
         v.x = v.y = v.z = v.w = 16;
         for (u32 g = RCX_G_L2; g < RCX_G_L1; ++g) tree.store(g, v);
     } else if (wave == 4) {
@@ -614,8 +616,8 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
 
     u8* payload = wave_slots + (u64)lane * slot + 4;
     const u32 cap = ((u32)slot - 4) & ~3u; // as EncLane::begin
-    if (full) rcx_mc5_pipeline<true>(wave, lane, len, nchunks, in, divtab, tree, stage, ring, ring2, enc, ahead, wr, oq.pos, drained, payload, cap, live);
-    else rcx_mc5_pipeline<false>(wave, lane, len, nchunks, in, divtab, tree, stage, ring, ring2, enc, ahead, wr, oq.pos, drained, payload, cap, live);
+    if (full) rcx_mc5_pipeline<true>(wave, lane, len, nchunks, in, divtab, tree, stage, ring, ring2, ring3, enc, ahead, wr, oq.pos, drained, payload, cap, live);
+    else rcx_mc5_pipeline<false>(wave, lane, len, nchunks, in, divtab, tree, stage, ring, ring2, ring3, enc, ahead, wr, oq.pos, drained, payload, cap, live);
 
     RCX_MC_CLOSE_HANDOVER(wave, RCX_DRAIN_WAVE, oq, enc, drained);
     if (wave == 1 && live) {
