@@ -7,15 +7,25 @@ for that block, so a reader with only the reference can decode a container block
 
 Layout (little-endian):
     0   4  magic  b"RCXB"
-    4   1  version (1)
+    4   1  version (1; 2 with checksums)
     5   1  coder   (0 adaptive, 1 static, 2 rANS one state, 3 rANS eight states: include/rcx.h RCX_CODER_*)
     6   2  flags: bit 0 = the data went through the reference's block sort first (blksort.h: BlkSort::encode, 2 bytes
-           more per whole 32 KiB, as test/main.cpp:961-970 does in front of zlib / zstd); other bits 0
+           more per whole 32 KiB, as test/main.cpp:961-970 does in front of zlib / zstd); bit 1 = checksums (version 2,
+           and only there); other bits 0
     8   4  block size in bytes
     12  8  n, the original size
     20  8  nblocks = ceil(m / block), m = the bytes the coder saw: n, or with bit 0 n + 2 * (n // 32768)
     28  8 * (nblocks + 1)  offsets of the block streams in the payload (offsets[0] = 0, offsets[nblocks] = payload size)
+    ..  version 2: 4 * nblocks  the CRC-32 (zlib's crc32, u32 LE) of each block of the bytes the coder saw -- with bit 0 the
+        block-sorted text -- so that a block can be checked on its own, by unpack_range() too
     ..  payload: the block streams back to back
+
+Checksums are opt-in (pack(..., checksum=True)): without them a container is byte for byte what it always was, version
+1.  The decoders cannot tell that a damaged payload came back wrong (include/rcx.h, "Damaged streams": it still decodes to
+some bytes); with checksums unpack(), unpack_range() and unpack_items() compare what they decoded, on the GPU, before
+they hand it back, and raise ChecksumError naming the first bad block or item (verify=False skips that).  The checked
+paths upload once and use the device calls (encode + CRC, decode + verify): they give up the overlap of copies and
+kernels that the host-buffer calls have.
 
 The header functions are plain Python; pack()/unpack() go through the HIP library (there is no CPU coder
 here: without librcx.so and a GPU they raise).
@@ -28,12 +38,13 @@ The item container holds independent buffers of differing sizes (include/rcx.h, 
 reference codes a file of those bytes; an item of length 0 has no stream.  Its own magic, so that parse() keeps
 rejecting what it does not know:
     0   4  magic  b"RCXI"
-    4   1  version (1)
+    4   1  version (1; 2 with checksums)
     5   1  coder
-    6   2  flags (0)
+    6   2  flags (0; version 2: bit 1 = checksums)
     8   8  nitems
     16  8 * nitems        the items' lengths
     ..  8 * (nitems + 1)  offsets of the item streams in the payload
+    ..  version 2: 4 * nitems  the CRC-32 of each item (u32 LE; 0 for an empty one)
     ..  payload: the item streams back to back
 """
 import struct
@@ -42,7 +53,9 @@ import numpy as np
 
 MAGIC = b"RCXB"
 VERSION = 1
+VERSION_CRC = 2  # the same layout + the CRC table; always with FLAG_CRC32
 FLAG_BLKSORT = 1
+FLAG_CRC32 = 2
 _FIXED = struct.Struct("<4sBBHIQQ")
 ITEM_MAGIC = b"RCXI"
 ITEM_VERSION = 1
@@ -59,36 +72,147 @@ class ContainerError(ValueError):
     pass
 
 
-def header_bytes(coder: int, block: int, n: int, offsets, flags: int = 0) -> bytes:
+class ChecksumError(ContainerError):
+    """Decoded bytes whose CRC-32 differs from the container's: `index` is the first such block (RCXB) or item (RCXI),
+    counted as the container counts them."""
+
+    def __init__(self, kind: str, index: int):
+        self.kind, self.index = kind, int(index)
+        super().__init__(f"checksum mismatch in {kind} {self.index}")
+
+
+def _version_and_flags(flags: int, crcs, count: int):
+    """A header's version byte, flags and CRC table: version 1 as it always was, version 2 = the CRC bit + the table."""
+    if crcs is None:
+        if flags & FLAG_CRC32:
+            raise ContainerError("the checksum flag needs the checksums")
+        return VERSION, flags, b""
+    crcs = np.ascontiguousarray(crcs, dtype="<u4")
+    if len(crcs) != count:
+        raise ContainerError("one checksum per block or item")
+    return VERSION_CRC, flags | FLAG_CRC32, crcs.tobytes()
+
+
+def _check_version(version: int, flags: int, known: int) -> bool:
+    """-> whether a CRC table follows.  Version 1: exactly the flags it always had; version 2: only with the CRC bit."""
+    if version == VERSION and not flags & ~known:
+        return False
+    if version == VERSION_CRC and flags & FLAG_CRC32 and not flags & ~(known | FLAG_CRC32):
+        return True
+    raise ContainerError("unsupported container version, coder or flags")
+
+
+def header_bytes(coder: int, block: int, n: int, offsets, flags: int = 0, crcs=None) -> bytes:
     offsets = np.ascontiguousarray(offsets, dtype="<u8")
     nblocks = len(offsets) - 1
     if nblocks != (coded_size(n, flags) + block - 1) // block:
         raise ContainerError("offsets do not match n and the block size")
-    return _FIXED.pack(MAGIC, VERSION, coder, flags, block, n, nblocks) + offsets.tobytes()
+    version, flags, table = _version_and_flags(flags, crcs, nblocks)
+    return _FIXED.pack(MAGIC, version, coder, flags, block, n, nblocks) + offsets.tobytes() + table
 
 
 def parse(blob):
-    """-> dict(coder, flags, block, n, nblocks, offsets uint64[nblocks+1], payload uint8 view)"""
+    """-> dict(coder, flags, block, n, nblocks, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, payload uint8 view)"""
     buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
     if len(buf) < _FIXED.size:
         raise ContainerError("shorter than a header")
     magic, version, coder, flags, block, n, nblocks = _FIXED.unpack(bytes(buf[: _FIXED.size]))
     if magic != MAGIC:
         raise ContainerError("not an RCXB container")
-    if version != VERSION or coder not in (0, 1, 2, 3) or flags & ~FLAG_BLKSORT:
+    if coder not in (0, 1, 2, 3):
         raise ContainerError("unsupported container version, coder or flags")
+    checked = _check_version(version, flags, FLAG_BLKSORT)
     if block < 16 or block > (1 << 24) - 256 or nblocks != (coded_size(n, flags) + block - 1) // block:
         raise ContainerError("inconsistent header")
     end = _FIXED.size + 8 * (nblocks + 1)
     if len(buf) < end:
         raise ContainerError("truncated offset table")
     offsets = np.frombuffer(bytes(buf[_FIXED.size:end]), dtype="<u8").astype(np.uint64)
+    crcs = None
+    if checked:
+        if nblocks > len(buf) or len(buf) < end + 4 * nblocks:
+            raise ContainerError("truncated checksum table")
+        crcs = np.frombuffer(bytes(buf[end: end + 4 * nblocks]), dtype="<u4").astype(np.uint32)
+        end += 4 * nblocks
     if offsets[0] != 0 or np.any(np.diff(offsets.astype(np.int64)) < 0) or end + int(offsets[-1]) != len(buf):
         raise ContainerError("offset table does not match the payload")
-    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "offsets": offsets, "payload": buf[end:]}
+    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "offsets": offsets, "crcs": crcs, "payload": buf[end:]}
 
 
-def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = False) -> bytes:
+# ---- the checked paths: one upload, the device calls, one download ------------------------------------------------
+def _cuda(a, dtype=None):
+    import torch
+    a = np.array(a, dtype=dtype)  # (a writable copy: a container's arrays are views of the caller's bytes)
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
+
+
+def _crcs_of(t) -> np.ndarray:
+    return t.cpu().numpy().view(np.uint32).copy()
+
+
+def _pack_checked(ctx, src: np.ndarray, block: int, coder: int, blksort: bool):
+    """-> (payload, offsets, crcs): block sort (if asked for), encode and CRC-32 of the coder's input, all on the device."""
+    import torch
+    from . import rcx
+    d_src = _cuda(src)
+    if blksort:
+        d_sorted = torch.empty(rcx.bwt_encode_bound(len(src)), dtype=torch.uint8, device="cuda")
+        ctx.bwt_encode_device(d_src, d_sorted)
+        d_src = d_sorted[: coded_size(len(src), FLAG_BLKSORT)]
+    m = d_src.numel()
+    nblocks = rcx.block_count(m, block)
+    d_dst = torch.empty(rcx.encode_bound(m, block, coder), dtype=torch.uint8, device="cuda")
+    d_offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
+    d_crc = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
+    ctx.encode_blocks_device(d_src, block, d_dst, d_offs, coder=coder)
+    ctx.crc32_blocks_device(d_src, block, d_crc)
+    ctx.sync_status()
+    offsets = d_offs.cpu().numpy().astype(np.uint64)
+    return d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc)
+
+
+def _sync_checked(ctx, kind: str, name=lambda k: k):
+    """The latch behind a verify call: a mismatch becomes ChecksumError with the container's index."""
+    from . import rcx
+    st, bad = ctx.sync_status(raise_on_error=False)
+    if st == rcx.E_CORRUPT:
+        raise ChecksumError(kind, name(int(bad)))
+    if st != rcx.OK:
+        raise rcx.RcxError(st, f"{kind} {bad}")
+
+
+def _unpack_checked(ctx, c) -> bytes:
+    import torch
+    m = coded_size(c["n"], c["flags"])
+    d_out = torch.empty(m, dtype=torch.uint8, device="cuda")
+    ctx.decode_blocks_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), m, c["block"], d_out, coder=c["coder"])
+    ctx.sync_status()  # (the decoder's own failures first: a stream that runs dry is an RcxError, as without checksums)
+    ctx.verify_blocks_device(d_out, c["block"], _cuda(c["crcs"]))
+    _sync_checked(ctx, "block")
+    if c["flags"] & FLAG_BLKSORT:
+        d_text = torch.empty(max(c["n"], 1), dtype=torch.uint8, device="cuda")
+        ctx.bwt_decode_device(d_out, m, d_text)
+        ctx.sync_status()
+        d_out = d_text[: c["n"]]
+    return d_out.cpu().numpy().tobytes()
+
+
+def _decode_picked_checked(ctx, c, lengths, pick, kind: str) -> list:
+    """Streams pick[k] of a checked container, decoded back to back and verified -> their bytes."""
+    import torch
+    from . import rcx
+    pick = np.asarray(pick, dtype=np.uint64)
+    doffs = rcx.item_offsets(np.asarray(lengths, dtype=np.uint64)[pick.astype(np.int64)])
+    d_out = torch.empty(max(int(doffs[-1]), 1), dtype=torch.uint8, device="cuda")
+    ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), doffs, d_out, pick=pick, coder=c["coder"])
+    ctx.sync_status()
+    ctx.verify_items_device(d_out, doffs, _cuda(c["crcs"][pick.astype(np.int64)]))
+    _sync_checked(ctx, kind, lambda k: int(pick[k]))
+    out = d_out.cpu().numpy()
+    return [out[int(doffs[k]): int(doffs[k + 1])] for k in range(len(pick))]
+
+
+def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = False, checksum: bool = False) -> bytes:
     from . import rcx
     own = ctx is None
     ctx = ctx or rcx.Context(0)
@@ -96,7 +220,10 @@ def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = Fal
         src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
         flags = FLAG_BLKSORT if blksort else 0
         if len(src) == 0:
-            return header_bytes(coder, block, 0, np.zeros(1, np.uint64), flags)
+            return header_bytes(coder, block, 0, np.zeros(1, np.uint64), flags, np.zeros(0, np.uint32) if checksum else None)
+        if checksum:
+            payload, offsets, crcs = _pack_checked(ctx, src, block, coder, blksort)
+            return header_bytes(coder, block, len(src), offsets, flags, crcs) + payload.tobytes()
         payload, offsets = ctx.encode_blocks(ctx.bwt_encode(src) if blksort else src, block, coder=coder)
         return header_bytes(coder, block, len(src), offsets, flags) + payload.tobytes()
     finally:
@@ -104,7 +231,7 @@ def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = Fal
             ctx.close()
 
 
-def unpack(blob, ctx=None) -> bytes:
+def unpack(blob, ctx=None, verify: bool = True) -> bytes:
     from . import rcx
     c = parse(blob)
     if c["n"] == 0:
@@ -112,6 +239,8 @@ def unpack(blob, ctx=None) -> bytes:
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
+        if verify and c["crcs"] is not None:
+            return _unpack_checked(ctx, c)
         m = coded_size(c["n"], c["flags"])
         out = ctx.decode_blocks(c["payload"], c["offsets"], c["block"], capacity=m, coder=c["coder"])
         if len(out) != m:
@@ -124,8 +253,9 @@ def unpack(blob, ctx=None) -> bytes:
             ctx.close()
 
 
-def unpack_range(blob, start: int, stop: int, ctx=None) -> bytes:
-    """The bytes [start, stop) of the original, decoding only the blocks that cover them."""
+def unpack_range(blob, start: int, stop: int, ctx=None, verify: bool = True) -> bytes:
+    """The bytes [start, stop) of the original, decoding -- and, in a container with checksums, verifying -- only the
+    blocks that cover them."""
     from . import rcx
     c = parse(blob)
     if c["flags"] & FLAG_BLKSORT:
@@ -142,7 +272,10 @@ def unpack_range(blob, start: int, stop: int, ctx=None) -> bytes:
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
-        parts = ctx.decode_items(c["payload"], c["offsets"], lengths, pick=pick, coder=c["coder"])
+        if verify and c["crcs"] is not None:
+            parts = _decode_picked_checked(ctx, c, lengths, pick, "block")
+        else:
+            parts = ctx.decode_items(c["payload"], c["offsets"], lengths, pick=pick, coder=c["coder"])
     finally:
         if own:
             ctx.close()
@@ -150,32 +283,40 @@ def unpack_range(blob, start: int, stop: int, ctx=None) -> bytes:
     return out[start - first * block: stop - first * block].tobytes()
 
 
-def item_header_bytes(coder: int, lengths, offsets) -> bytes:
+def item_header_bytes(coder: int, lengths, offsets, crcs=None) -> bytes:
     lengths = np.ascontiguousarray(lengths, dtype="<u8")
     offsets = np.ascontiguousarray(offsets, dtype="<u8")
     if len(offsets) != len(lengths) + 1:
         raise ContainerError("offsets do not match the number of items")
     if len(lengths) and int(lengths.max()) > MAX_ITEM:
         raise ContainerError("an item is longer than the coder takes")
-    return _ITEM_FIXED.pack(ITEM_MAGIC, ITEM_VERSION, coder, 0, len(lengths)) + lengths.tobytes() + offsets.tobytes()
+    version, flags, table = _version_and_flags(0, crcs, len(lengths))
+    return _ITEM_FIXED.pack(ITEM_MAGIC, version, coder, flags, len(lengths)) + lengths.tobytes() + offsets.tobytes() + table
 
 
 def parse_items(blob):
-    """-> dict(coder, nitems, lengths uint64[nitems], offsets uint64[nitems+1], payload uint8 view)"""
+    """-> dict(coder, nitems, lengths uint64[nitems], offsets uint64[nitems+1], crcs uint32[nitems] or None, payload uint8 view)"""
     buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
     if len(buf) < _ITEM_FIXED.size:
         raise ContainerError("shorter than a header")
     magic, version, coder, flags, nitems = _ITEM_FIXED.unpack(bytes(buf[: _ITEM_FIXED.size]))
     if magic != ITEM_MAGIC:
         raise ContainerError("not an RCXI container")
-    if version != ITEM_VERSION or coder not in (0, 1, 2, 3) or flags:
+    if coder not in (0, 1, 2, 3):
         raise ContainerError("unsupported container version, coder or flags")
+    checked = _check_version(version, flags, 0)
     mid = _ITEM_FIXED.size + 8 * nitems
     end = mid + 8 * (nitems + 1)
     if nitems > len(buf) or len(buf) < end:
         raise ContainerError("truncated tables")
     lengths = np.frombuffer(bytes(buf[_ITEM_FIXED.size:mid]), dtype="<u8").astype(np.uint64)
     offsets = np.frombuffer(bytes(buf[mid:end]), dtype="<u8").astype(np.uint64)
+    crcs = None
+    if checked:
+        if len(buf) < end + 4 * nitems:
+            raise ContainerError("truncated checksum table")
+        crcs = np.frombuffer(bytes(buf[end: end + 4 * nitems]), dtype="<u4").astype(np.uint32)
+        end += 4 * nitems
     if nitems and int(lengths.max()) > MAX_ITEM:
         raise ContainerError("an item is longer than the coder takes")
     sizes = np.diff(offsets.astype(np.int64))
@@ -183,16 +324,28 @@ def parse_items(blob):
         raise ContainerError("offset table does not match the payload")
     if np.any((lengths == 0) != (sizes == 0)):
         raise ContainerError("an item of length 0 has no stream, and only such an item")
-    return {"coder": coder, "nitems": nitems, "lengths": lengths, "offsets": offsets, "payload": buf[end:]}
+    return {"coder": coder, "nitems": nitems, "lengths": lengths, "offsets": offsets, "crcs": crcs, "payload": buf[end:]}
 
 
-def pack_items(items, coder: int = 0, ctx=None) -> bytes:
+def pack_items(items, coder: int = 0, ctx=None, checksum: bool = False) -> bytes:
     """items: a list of buffers -> an RCXI container."""
     from . import rcx
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
         parts = [np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if not isinstance(x, np.ndarray) else x, dtype=np.uint8) for x in items]
+        if checksum:
+            import torch
+            soffs = rcx.item_offsets([len(x) for x in parts])
+            d_src = _cuda(np.concatenate(parts) if parts else np.zeros(0, np.uint8))
+            d_dst = torch.empty(max(rcx.encode_items_bound(soffs, coder), 1), dtype=torch.uint8, device="cuda")
+            d_offs = torch.zeros(len(soffs), dtype=torch.int64, device="cuda")
+            d_crc = torch.zeros(len(parts), dtype=torch.int32, device="cuda")
+            ctx.encode_items_device(d_src, soffs, d_dst, d_offs, coder=coder)
+            ctx.crc32_items_device(d_src, soffs, d_crc)
+            ctx.sync_status()
+            offsets = d_offs.cpu().numpy().astype(np.uint64)
+            return item_header_bytes(coder, [len(x) for x in parts], offsets, _crcs_of(d_crc)) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
         payload, offsets = ctx.encode_items(parts, coder=coder)
         return item_header_bytes(coder, [len(x) for x in parts], offsets) + payload.tobytes()
     finally:
@@ -200,8 +353,9 @@ def pack_items(items, coder: int = 0, ctx=None) -> bytes:
             ctx.close()
 
 
-def unpack_items(blob, pick=None, ctx=None) -> list:
-    """-> the list of the picked items' bytes (all of them, in order, if pick is None); picks may repeat."""
+def unpack_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
+    """-> the list of the picked items' bytes (all of them, in order, if pick is None); picks may repeat.  In a container
+    with checksums the picked items, and only they, are verified."""
     from . import rcx
     c = parse_items(blob)
     if pick is not None and any(not 0 <= int(k) < c["nitems"] for k in pick):
@@ -211,6 +365,9 @@ def unpack_items(blob, pick=None, ctx=None) -> list:
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
+        if verify and c["crcs"] is not None:
+            picked = np.arange(c["nitems"], dtype=np.uint64) if pick is None else pick
+            return [x.tobytes() for x in _decode_picked_checked(ctx, c, c["lengths"], picked, "item")]
         return [x.tobytes() for x in ctx.decode_items(c["payload"], c["offsets"], c["lengths"], pick=pick, coder=c["coder"])]
     finally:
         if own:

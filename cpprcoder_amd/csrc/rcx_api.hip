@@ -11,6 +11,7 @@
 #include "rcx_items.hpp"    // the item calls
 #include "rcx_streams.hpp"  // single streams, whole and resumable
 #include "rcx_bwt_api.hpp"  // the block sort
+#include "rcx_crc_api.hpp"  // CRC-32 per block or item
 
 extern "C" {
 

@@ -237,4 +237,22 @@ int decode_range(rcx_ctx* c, int coder, const void* d_comp, u64 comp_size, const
     return decode_launches(c, coder, d_comp, comp_size, d_offsets, nblocks, block, n, d_dst, s, redo, rg.packed, RcxBlocks{});
 }
 
+// The CRC-32 launch for `nblocks` work entries of geometry G (rcx_crc.hpp): d_expected == nullptr stores d_crc[id], else
+// the entries are compared and a mismatch is latched.  One wave per entry, four to a workgroup; a workgroup copies 5 KiB
+// of tables into LDS when it starts, so there are at most 8 per CU (32 waves, what a CU holds) and they loop over the entries.
+template <class G>
+int crc_launch(rcx_ctx* c, const void* d_src, u64 n, u32 block, u64 nblocks, u32* d_crc, const u32* d_expected, hipStream_t s, G g)
+{
+    const u8* const src = static_cast<const u8*>(d_src);
+    const u64 want = (nblocks + RCX_CRC_WAVES - 1) / RCX_CRC_WAVES, most = 8ull * (u64)c->cus;
+    const u32 grid = (u32)(want < most ? want : most);
+    if (d_expected)
+        hipLaunchKernelGGL((rcx_crc32_k<true, G>), dim3(grid), dim3(64 * RCX_CRC_WAVES), 0, s, src, n, block, nblocks, static_cast<u32*>(nullptr),
+                           d_expected, c->status, g);
+    else
+        hipLaunchKernelGGL((rcx_crc32_k<false, G>), dim3(grid), dim3(64 * RCX_CRC_WAVES), 0, s, src, n, block, nblocks, d_crc,
+                           static_cast<const u32*>(nullptr), c->status, g);
+    return LAUNCHED();
+}
+
 } // namespace

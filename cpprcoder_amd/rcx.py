@@ -36,6 +36,8 @@ EXPORTS = (
     "rcx_bwt_decode_device", "rcx_bwt_encode", "rcx_bwt_decode", "rcx_bwt_last_ties",
     "rcx_encode_items_bound", "rcx_items_plan", "rcx_ctx_scratch_bytes", "rcx_encode_items_device", "rcx_decode_items_device",
     "rcx_encode_items", "rcx_decode_items",
+    "rcx_crc32_blocks_device", "rcx_crc32_items_device", "rcx_crc32_verify_blocks_device", "rcx_crc32_verify_items_device",
+    "rcx_crc32_blocks", "rcx_crc32_items",
 )
 ITEM_SCRATCH_BYTES = 3168  # RCX_ITEM_SCRATCH_BYTES
 
@@ -129,6 +131,12 @@ def lib() -> C.CDLL:
         L.rcx_encode_items.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), vp]
         L.rcx_decode_items.restype = i32
         L.rcx_decode_items.argtypes = [vp, i32, vp, u64, vp, u64, vp, u64, vp, vp, u64]
+        for name in ("rcx_crc32_blocks_device", "rcx_crc32_verify_blocks_device"):
+            getattr(L, name).restype, getattr(L, name).argtypes = i32, [vp, vp, u64, u32, vp, vp]
+        for name in ("rcx_crc32_items_device", "rcx_crc32_verify_items_device"):
+            getattr(L, name).restype, getattr(L, name).argtypes = i32, [vp, vp, vp, u64, vp, vp]
+        L.rcx_crc32_blocks.restype, L.rcx_crc32_blocks.argtypes = i32, [vp, vp, u64, u32, vp]
+        L.rcx_crc32_items.restype, L.rcx_crc32_items.argtypes = i32, [vp, vp, vp, u64, vp]
         _lib = L
     return _lib
 
@@ -358,6 +366,61 @@ class Context:
                                     None if p is None else p.ctypes.data, len(doffs) - 1, doffs.ctypes.data, out.ctypes.data, int(doffs[-1]))
         _check(st, "rcx_decode_items")
         return [out[int(doffs[k]): int(doffs[k + 1])] for k in range(len(doffs) - 1)]
+
+    # ---- CRC-32 per block or item (zlib's crc32) ------------------------------------
+    def crc32_blocks_device(self, src, block: int, crc, stream=None) -> None:
+        """src: uint8 cuda tensor; crc: int32 / uint32 cuda tensor [>= nblocks] (written: crc[b] = block b's CRC-32).  Enqueues only."""
+        n = src.numel()
+        if MIN_BLOCK <= block <= MAX_BLOCK and crc.numel() < block_count(n, block):
+            raise ValueError("crc needs nblocks entries")
+        _check(lib().rcx_crc32_blocks_device(self._h, src.data_ptr(), n, block, crc.data_ptr(), self._stream_handle(stream)), "rcx_crc32_blocks_device")
+
+    def crc32_items_device(self, src, src_offsets, crc, stream=None) -> None:
+        """Item i = src[src_offsets[i] : src_offsets[i+1]] (HOST table); crc: 4-byte cuda tensor [>= nitems] (written).  Enqueues only."""
+        offs = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+        if crc.numel() < len(offs) - 1:
+            raise ValueError("crc needs nitems entries")
+        _check(lib().rcx_crc32_items_device(self._h, src.data_ptr(), offs.ctypes.data, len(offs) - 1, crc.data_ptr(), self._stream_handle(stream)),
+               "rcx_crc32_items_device")
+
+    def verify_blocks_device(self, src, block: int, expected, stream=None) -> None:
+        """Compare every block's CRC-32 with expected[b] (4-byte cuda tensor); a mismatch is E_CORRUPT from sync_status(),
+        with the lowest such block.  Writes nothing else; enqueues only."""
+        n = src.numel()
+        if MIN_BLOCK <= block <= MAX_BLOCK and expected.numel() < block_count(n, block):
+            raise ValueError("expected needs nblocks entries")
+        _check(lib().rcx_crc32_verify_blocks_device(self._h, src.data_ptr(), n, block, expected.data_ptr(), self._stream_handle(stream)),
+               "rcx_crc32_verify_blocks_device")
+
+    def verify_items_device(self, src, src_offsets, expected, stream=None) -> None:
+        """The same per item; sync_status() names the lowest mismatching item."""
+        offs = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+        if expected.numel() < len(offs) - 1:
+            raise ValueError("expected needs nitems entries")
+        _check(lib().rcx_crc32_verify_items_device(self._h, src.data_ptr(), offs.ctypes.data, len(offs) - 1, expected.data_ptr(),
+                                                   self._stream_handle(stream)), "rcx_crc32_verify_items_device")
+
+    def crc32_blocks(self, data, block: int) -> np.ndarray:
+        """Host buffer -> uint32[nblocks]."""
+        src = _np_u8(data)
+        crc = np.zeros(block_count(len(src), block) if MIN_BLOCK <= block <= MAX_BLOCK else 0, dtype=np.uint32)
+        _check(lib().rcx_crc32_blocks(self._h, src.ctypes.data, len(src), block, crc.ctypes.data), "rcx_crc32_blocks")
+        return crc
+
+    def crc32_items(self, items, lengths=None) -> np.ndarray:
+        """items: a list of buffers, or one buffer with `lengths` cutting it -> uint32[nitems]."""
+        if lengths is None:
+            parts = [_np_u8(x) for x in items]
+            lengths = [len(x) for x in parts]
+            src = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        else:
+            src = _np_u8(items)
+        offs = item_offsets(lengths)
+        if int(offs[-1]) != len(src):
+            raise ValueError("lengths do not add up to the buffer")
+        crc = np.zeros(len(offs) - 1, dtype=np.uint32)
+        _check(lib().rcx_crc32_items(self._h, src.ctypes.data, offs.ctypes.data, len(offs) - 1, crc.ctypes.data), "rcx_crc32_items")
+        return crc
 
     # ---- block sort (blksort.h) ----------------------------------------------
     def bwt_encode(self, data) -> np.ndarray:

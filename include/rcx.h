@@ -48,7 +48,7 @@ enum {
     RCX_ERROR = -1,      /* Status_Error */
     RCX_E_ARG = -2,      /* bad argument (null pointer, block size out of range ...) */
     RCX_E_CAPACITY = -3, /* destination too small / a block outgrew its scratch slot */
-    RCX_E_CORRUPT = -4,  /* a block's stream is truncated or its header disagrees with the layout */
+    RCX_E_CORRUPT = -4,  /* a block's stream is truncated or its header disagrees with the layout; a CRC-32 mismatch (rcx_crc32_verify_*) */
     RCX_E_HIP = -5,      /* HIP runtime error, or no usable MI355X */
     RCX_E_NOMEM = -6,    /* device or host allocation failed */
     RCX_E_COMM = -7      /* RCCL error */
@@ -219,6 +219,36 @@ int rcx_encode_items(rcx_ctx* ctx, int coder, const uint8_t* src, const uint64_t
 int rcx_decode_items(rcx_ctx* ctx, int coder, const uint8_t* comp, uint64_t comp_size, const uint64_t* comp_offsets,
                      uint64_t nstreams, const uint64_t* pick, uint64_t npick, const uint64_t* dst_offsets,
                      uint8_t* dst, uint64_t dst_cap);
+
+/*
+ * CRC-32 per block or per item, on the GPU (new; the reference has no checksum).  The decoders above cannot tell that
+ * a damaged payload came back wrong -- it "still decodes to some bytes", with RCX_OK -- so a caller that wants to know
+ * keeps one CRC-32 per block (or item) of what it encoded and has the decoded bytes compared where they lie, in HBM.
+ * The checksum is zlib's crc32(): polynomial 0xEDB88320 (reflected), init and final XOR 0xFFFFFFFF, so "123456789"
+ * gives 0xCBF43926 and no bytes give 0.
+ *   rcx_crc32_blocks_device          d_crc[b] = the CRC-32 of block b of [d_src, d_src + n), blocks as in the data model above
+ *   rcx_crc32_items_device           d_crc[i] = the CRC-32 of item i = d_src[src_offsets[i] .. src_offsets[i + 1]) (0 .. RCX_MAX_BLOCK
+ *                                    bytes; an item of length 0 has CRC 0); src_offsets is a HOST table of nitems + 1
+ *   rcx_crc32_verify_blocks_device   compare instead of store: block b against d_expected[b]
+ *   rcx_crc32_verify_items_device    the same, item i against d_expected[i]
+ * The device calls only enqueue.  They read exactly [d_src, d_src + n), or the items' ranges, and d_expected[0 .. count);
+ * pointers and offsets may have any alignment.  The store calls write exactly d_crc[0 .. count), count = rcx_block_count(n,
+ * block) or nitems; the verify calls write nothing but the latch: a mismatch is RCX_E_CORRUPT from rcx_ctx_sync_status(),
+ * whose index is the lowest mismatching block or item -- the same latch, with the same meaning, as a decode call's on that
+ * context, so decode + verify enqueued on one stream are read with one rcx_ctx_sync_status().
+ * The block calls allocate nothing, need no rcx_ctx_reserve and can be enqueued on any stream, also under graph capture.
+ * The item calls send their table to the device inside the call, as the coder item calls do, and cannot be captured.
+ * RCX_E_ARG, before anything is enqueued: a null pointer with a non-zero count, a block size outside RCX_MIN_BLOCK ..
+ * RCX_MAX_BLOCK, a table that decreases or an item above RCX_MAX_BLOCK.  n = 0 or nitems = 0 is RCX_OK and does nothing.
+ * The host-buffer variants copy in, run the kernel, synchronise and copy 4 bytes per block or item out.
+ */
+int rcx_crc32_blocks_device(rcx_ctx* ctx, const void* d_src, uint64_t n, uint32_t block, uint32_t* d_crc, void* stream);
+int rcx_crc32_items_device(rcx_ctx* ctx, const void* d_src, const uint64_t* src_offsets, uint64_t nitems, uint32_t* d_crc, void* stream);
+int rcx_crc32_verify_blocks_device(rcx_ctx* ctx, const void* d_src, uint64_t n, uint32_t block, const uint32_t* d_expected, void* stream);
+int rcx_crc32_verify_items_device(rcx_ctx* ctx, const void* d_src, const uint64_t* src_offsets, uint64_t nitems,
+                                  const uint32_t* d_expected, void* stream);
+int rcx_crc32_blocks(rcx_ctx* ctx, const uint8_t* src, uint64_t n, uint32_t block, uint32_t* crc);
+int rcx_crc32_items(rcx_ctx* ctx, const uint8_t* src, const uint64_t* src_offsets, uint64_t nitems, uint32_t* crc);
 
 /*
  * Single-stream calls with the reference's exact stream semantics, used by the
