@@ -45,13 +45,19 @@ __device__ __forceinline__ u32 rcx_oct_excl_scan(u32 x, u32 m1, u32 m2, u32 m4)
 // Model (cpprcoder.h:1094-1243): the alphabet is split 16 nodes x 16 symbols.  Lane j of the
 // block's quad keeps in REGISTERS U1..U4 = the counts of all symbols below node 4j+1, ..., 4j+4
 // (absolute cumulative sums: the upper bounds of its four nodes; U4 of the last lane is the
-// total); the 256 counts live in LDS, node n as 64 contiguous bytes of which lane j reads counts
-// 4j..4j+3 (one ds_read_b128).
+// total) -- negated, nU_k = -U_k, see below; the 256 counts live in LDS, node n as 64 contiguous
+// bytes of which lane j reads counts 4j..4j+3 (one ds_read_b128).
 //
 // find() (cpprcoder.h:1220-1242) in the scaled domain (see DecLane), without selects:
 //   x_k = low - U_k*t wraps past zero exactly for the bounds above low, so
 //     * the number of bounds that do NOT borrow, summed over the quad, is the node index,
 //     * the unsigned minimum of low and all x_k over the quad is low - cum(node)*t;
+//   round 1 takes both from one v_mad_i64_i32 per bound, {low, 0} + nU_k*t: x_k is its low word, the borrow -- 0 or
+//   -1 -- its high word h_k, and the model update (+1 on every bound above the symbol's node) is nU_k += h_k.
+//   h_k is 0 or -1 on ANY input: t = floor(r / (256 + i)) for whatever 32-bit r the renormalised range is (the divisor
+//   entries are exact, rcx_divtab.hpp; a wrapped r + inc gives t = 0), and U_k <= 256 + i as long as every h so far was
+//   0 or -1, so U_k*t <= r < 2^32 and low - U_k*t > -2^32: by induction the node index is 0 .. 16 and a symbol raises a
+//   bound by at most one, however damaged the stream;
 //   round 2 is the same over the node's 16 counts, and the unsigned maximum of the x over the
 //   quad is the (wrapped) distance to the smallest bound above, so the new range count*t is
 //   min - max (mod 2^32): cum(c+1)*t - cum(c)*t, no multiply, no select of the count.
@@ -399,7 +405,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #pragma unroll
         for (u32 q = 0; q < 17; ++q) seat.leaves[q * 16] = v; // 16 nodes + the scratch row
     }
-    u32 U1 = 64u * seat.j + 16, U2 = U1 + 16, U3 = U1 + 32, U4_ = U1 + 48;
+    u32 nU1 = 0u - (64u * seat.j + 16), nU2 = nU1 - 16, nU3 = nU1 - 32, nU4 = nU1 - 48; // the bounds, negated
     const u32 T0 = 4u * seat.j;
     const u32 m1 = (seat.j & 1u) ? ~0u : 0u, m2 = (seat.j & 2u) ? ~0u : 0u;
 
@@ -442,7 +448,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     //
     // The three arithmetic cores are written out as instruction sequences: a lone wave pays 4 cycles
     // for every s_nop the compiler has to put between a compare and the use of its mask, or between
-    // a vector write and a DPP read of it (2 wait states each on gfx950), so compares go to four
+    // a vector write and a DPP read of it (2 wait states each on gfx950), so round 2's compares go to
     // different mask registers before any is used, and every DPP step has two independent
     // instructions in front of it.  Only register-to-register vector instructions are in there;
     // LDS and global accesses stay with the compiler (and its s_waitcnt placement).
@@ -483,33 +489,38 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
            range is count x t <= (total - 255) x t, or shifted left by 8 or more), so range + inc does not wrap (only a block \
            that has already decoded "node 16" can break that, and it is marked and decoded again) */          \
         const u32 t_ = __umulhi((in.range << k8_) + (INC), (MUL)) >> (SH);                                 \
-        /* round 1: which of the 16 nodes.  node = bounds at or below low, rem = low - the largest */      \
-        const u32 a1_ = rcx_mul24(U1, t_), a2_ = rcx_mul24(U2, t_), a3_ = rcx_mul24(U3, t_);               \
-        const u32 a4_ = rcx_mul24(U4_, t_);                                                                \
-        u32 node_, rem_, ro_, la_, x1_, x2_, x3_, x4_, pown_, pad_, pye_;                                  \
-        u64 c1_, c2_, c3_, c4_, cz_;                                                                       \
-        asm volatile("v_sub_co_u32_e64 %[x1], %[c1], %[low], %[a1]\n\t"                                    \
-                     "v_sub_co_u32_e64 %[x2], %[c2], %[low], %[a2]\n\t"                                    \
-                     "v_sub_co_u32_e64 %[x3], %[c3], %[low], %[a3]\n\t"                                    \
-                     "v_sub_co_u32_e64 %[x4], %[c4], %[low], %[a4]\n\t"                                    \
-                     "v_subb_co_u32_e64 %[nd], %[cz], 4, 0, %[c1]\n\t" /* (the borrows stay: the update below) */ \
-                     "v_subb_co_u32_e64 %[nd], %[cz], %[nd], 0, %[c2]\n\t"                                 \
-                     "v_subb_co_u32_e64 %[nd], %[cz], %[nd], 0, %[c3]\n\t"                                 \
-                     "v_subb_co_u32_e64 %[nd], %[cz], %[nd], 0, %[c4]\n\t"                                 \
+        /* round 1: which of the 16 nodes.  node = bounds at or below low, rem = low - the largest.  One 64-bit           \
+           multiply-add per bound: {low, 0} - U_k * t has low - U_k * t in its low word and the borrow, 0 or -1, in   \
+           its high word (its carry-out goes to a mask register nothing reads) */                          \
+        const u64 lowp_ = in.low;                                                                          \
+        u32 node_, rem_, ro_, la_, pown_, pad_, pye_;                                                      \
+        u64 X1_, X2_, X3_, X4_, c1_, c2_, c3_, cz_;                                                        \
+        asm volatile("v_mad_i64_i32 %[X1], %[cz], %[n1], %[t], %[lp]\n\t"                                  \
+                     "v_mad_i64_i32 %[X2], %[cz], %[n2], %[t], %[lp]\n\t"                                  \
+                     "v_mad_i64_i32 %[X3], %[cz], %[n3], %[t], %[lp]\n\t"                                  \
+                     "v_mad_i64_i32 %[X4], %[cz], %[n4], %[t], %[lp]"                                      \
+                     : [X1] "=&v"(X1_), [X2] "=&v"(X2_), [X3] "=&v"(X3_), [X4] "=&v"(X4_), [cz] "=&s"(cz_)  \
+                     : [n1] "v"(nU1), [n2] "v"(nU2), [n3] "v"(nU3), [n4] "v"(nU4), [t] "v"(t_), [lp] "v"(lowp_)); \
+        /* (a statement that reads the words of the pairs cannot come right behind the one that wrote them without an   \
+           s_nop from the compiler: the stream position moves on in between) */                            \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        in.bp8 += k8_;                                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        const u32 x1_ = (u32)X1_, x2_ = (u32)X2_, x3_ = (u32)X3_, x4_ = (u32)X4_;                          \
+        const u32 h1_ = (u32)(X1_ >> 32), h2_ = (u32)(X2_ >> 32), h3_ = (u32)(X3_ >> 32), h4_ = (u32)(X4_ >> 32); \
+        asm volatile("v_add3_u32 %[nd], %[h1], %[h2], %[h3]\n\t"                                           \
+                     "v_add3_u32 %[nd], %[nd], %[h4], 4\n\t" /* 4 - the lane's borrows (they stay: the update below) */ \
                      RCX_QD_PREV_A_##HP                                                                    \
-                     : [nd] "=&v"(node_), [x1] "=&v"(x1_), [x2] "=&v"(x2_), [x3] "=&v"(x3_), [x4] "=&v"(x4_), \
-                       [c1] "=&s"(c1_), [c2] "=&s"(c2_), [c3] "=&s"(c3_), [c4] "=&s"(c4_), [cz] "=&s"(cz_), \
-                       [pown] "=&v"(pown_), [pad] "=&v"(pad_)                                              \
-                     : [low] "v"(in.low), [a1] "v"(a1_), [a2] "v"(a2_), [a3] "v"(a3_), [a4] "v"(a4_),      \
+                     : [nd] "=&v"(node_), [pown] "=&v"(pown_), [pad] "=&v"(pad_)                            \
+                     : [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_),                         \
                        [pc] "s"(p_own_), [psym] "v"(p_sym_), [pla] "v"(p_la_));                            \
         if (HP) (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), pown_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916, the earlier symbol's */ \
         asm volatile("v_add_u32_dpp %[nd], %[nd], %[nd] " RCX_QP1                                          \
-                     "v_add_u32 %[bp], %[bp], %[k8]\n\t" /* the stream position moves on */                \
                      "v_bfe_u32 %[ro], %[bp], 5, 5\n\t"  /* ring slot of the next pair ... */               \
                      "v_lshl_add_u32 %[ro], %[ro], 2, %[rb]" /* ... and its LDS address (formed here: a vector instruction right \
                                                                behind the sequence that reads a register of it costs an s_nop) */ \
-                     : [nd] "+v"(node_), [ro] "=&v"(ro_), [bp] "+v"(in.bp8)                                 \
-                     : [k8] "v"(k8_), [rb] "v"(ring_lds));                                                 \
+                     : [nd] "+v"(node_), [ro] "=&v"(ro_)                                                    \
+                     : [bp] "v"(in.bp8), [rb] "v"(ring_lds));                                              \
         {                                                                                                  \
             const RcxLdsU32* at_ = reinterpret_cast<const RcxLdsU32*>(ro_); /* the stream bytes of the next symbol */ \
             in.w0 = at_[0];                                                                                \
@@ -526,24 +537,24 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
         __builtin_amdgcn_sched_barrier(0);                                                                 \
         /* behind the read: the remainder (round 1's other result) across the quad; cpprcoder.h:1134-1177, +1 on every \
            cumulative sum above the node -- the bounds whose subtraction borrowed in round 1 (bound above low <=> its \
-           node number above the symbol's node; a target past the total seat.leaves no borrow and raises none, as find()'s \
-           fall-through needs it); the earlier symbol's byte; the next symbol's stream bytes */            \
+           node number above the symbol's node; a target past the total leaves no borrow and raises none, as find()'s \
+           fall-through needs it): the negated bound takes its high word, 0 or -1; the earlier symbol's byte */ \
         u32 sb_;                                                                                           \
         asm volatile("v_min3_u32 %[rm], %[x1], %[x2], %[x3]\n\t"                                           \
                      "v_min3_u32 %[rm], %[rm], %[x4], %[low]\n\t"                                          \
-                     "v_addc_co_u32_e64 %[u1], %[c1], 0, %[u1], %[c1]\n\t"                                 \
-                     "v_addc_co_u32_e64 %[u2], %[c2], 0, %[u2], %[c2]\n\t"                                 \
+                     "v_add_u32 %[u1], %[u1], %[h1]\n\t"                                                   \
+                     "v_add_u32 %[u2], %[u2], %[h2]\n\t"                                                   \
                      "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP1                                          \
-                     "v_addc_co_u32_e64 %[u3], %[c3], 0, %[u3], %[c3]\n\t"                                 \
-                     "v_addc_co_u32_e64 %[u4], %[c4], 0, %[u4], %[c4]\n\t"                                 \
+                     "v_add_u32 %[u3], %[u3], %[h3]\n\t"                                                   \
+                     "v_add_u32 %[u4], %[u4], %[h4]\n\t"                                                   \
                      "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP2                                          \
                      "v_lshl_add_u32 %[sb], %[n], 4, %[t0p3]" /* symbol, if none of the lane's bounds is above */ \
                      RCX_QD_PREV_S_##HP                                                                    \
-                     : [u1] "+v"(U1), [u2] "+v"(U2), [u3] "+v"(U3), [u4] "+v"(U4_), [rm] "=&v"(rem_),       \
-                       [sb] "=&v"(sb_), [c1] "+s"(c1_), [c2] "+s"(c2_), [c3] "+s"(c3_), [c4] "+s"(c4_),    \
-                       [pye] "=&v"(pye_), [pword] "+v"(PWORD)                                              \
+                     : [u1] "+v"(nU1), [u2] "+v"(nU2), [u3] "+v"(nU3), [u4] "+v"(nU4), [rm] "=&v"(rem_),    \
+                       [sb] "=&v"(sb_), [pye] "=&v"(pye_), [pword] "+v"(PWORD)                              \
                      : [n] "v"(node_), [t0p3] "v"(T0p3), [low] "v"(in.low), [x1] "v"(x1_), [x2] "v"(x2_),  \
-                       [x3] "v"(x3_), [x4] "v"(x4_), [pc] "s"(p_own_), [psym] "v"(p_sym_), [psh] "n"(PSHIFT)); \
+                       [x3] "v"(x3_), [x4] "v"(x4_), [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_), \
+                       [pc] "s"(p_own_), [psym] "v"(p_sym_), [psh] "n"(PSHIFT));                           \
         u32 lo_, rg_, qa_, qb_, qc_, qe_, tot_, pre_, o2_, d2_, ya_, yb_, yc_, ye_, hi_;                   \
         asm volatile("v_mul_u32_u24 %[qa], %[lx], %[t]\n\t"      /* the lane's four inclusive sums, scaled: every */ \
                      "v_mad_u32_u24 %[qb], %[ly], %[t], %[qa]\n\t" /* sum is below total x t <= range < 2^32 */      \
@@ -706,7 +717,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     // A symbol past the table ("node 16") is the only one that raises none of the cumulative sums: the last
     // lane's U4 -- the total, 256 + the symbols decoded (cpprcoder.h:1096, :1138) -- then falls short.
     // A marked block is judged (truncated or not) by the kernel that decodes it again.
-    const bool marked = live && rcx_quad_or(seat.j == 3 && U4_ != 256u + len ? 1u : 0u) != 0;
+    const bool marked = live && rcx_quad_or(seat.j == 3 && 0u - nU4 != 256u + len ? 1u : 0u) != 0;
     if (leader && !marked && in.taken() > stream_len) rcx_flag(status, RCX_ST_CORRUPT, rcx_id(g, seat.blk));
     RCX_QUAD_MARK_REDO(seat, redo, nblocks, marked);
 }

@@ -39,6 +39,13 @@ BENCH_KERNEL(k_add_indep, "", "v_add_u32 %[a], %[b], %[c]\n\tv_add_u32 %[d], %[b
 BENCH_KERNEL(k_mul24, "", "v_mul_u32_u24 %[a], %[a], %[b]")
 BENCH_KERNEL(k_mad64, "v_mov_b32 v40, 1\n\tv_mov_b32 v41, 0", "v_mad_u64_u32 v[40:41], s[20:21], %[a], %[b], v[40:41]")
 BENCH_KERNEL(k_mulhi, "", "v_mul_hi_u32 %[a], %[a], %[b]")
+// the signed form, as the quad decoder's round 1 uses it ({low, 0} - U * t: remainder in the low word, borrow in the high one):
+// a dependent chain, and four independent ones back to back with the four VOP2 adds that take their high words
+BENCH_KERNEL(k_madi64, "v_mov_b32 v40, 1\n\tv_mov_b32 v41, 0", "v_mad_i64_i32 v[40:41], s[20:21], %[a], %[b], v[40:41]")
+BENCH_KERNEL(k_madi64_x4, "v_mov_b32 v50, 1\n\tv_mov_b32 v51, 0",
+             "v_mad_i64_i32 v[40:41], s[20:21], %[a], %[b], v[50:51]\n\tv_mad_i64_i32 v[42:43], s[20:21], %[c], %[b], v[50:51]\n\t"
+             "v_mad_i64_i32 v[44:45], s[20:21], %[d], %[b], v[50:51]\n\tv_mad_i64_i32 v[46:47], s[20:21], %[a], %[b], v[50:51]\n\t"
+             "v_add_u32 %[a], %[a], v41\n\tv_add_u32 %[c], %[c], v43\n\tv_add_u32 %[d], %[d], v45\n\tv_add_u32 %[a], %[a], v47")
 BENCH_KERNEL(k_mullo, "", "v_mul_lo_u32 %[a], %[a], %[b]")
 BENCH_KERNEL(k_lshl64, "v_mov_b32 v40, 1\n\tv_mov_b32 v41, 0", "v_lshlrev_b64 v[40:41], %[b], v[40:41]")
 BENCH_KERNEL(k_add_nop0, "", "v_add_u32 %[a], %[a], %[b]\n\ts_nop 0")
@@ -196,6 +203,29 @@ SYM_KERNEL(k_sym_gap0_b64, "", LEAF64, ATOM)
     "v_bfe_u32 v47, v46, 5, 5\n\t"                                                \
     "v_add_u32_dpp v44, v44, v44" QP2                                             \
     "v_lshl_add_u32 %[a], v44, 8, v45\n\t"
+// BLOCK_A with the four multiplies in front of it that the kernel had there (round 1 as it was: 21 instructions) ...
+#define BLOCK_A_MUL                                                               \
+    "v_mul_u32_u24 v48, v49, %[b]\n\t"                                            \
+    "v_mul_u32_u24 v50, v49, %[c]\n\t"                                            \
+    "v_mul_u32_u24 v51, v49, %[d]\n\t"                                            \
+    "v_mul_u32_u24 v52, v49, %[b]\n\t" BLOCK_A
+// ... and with the borrows as high words of 64-bit multiply-adds (15)
+#define BLOCK_A2                                                                  \
+    "v_mad_i64_i32 v[40:41], s[20:21], %[b], v49, v[58:59]\n\t"                   \
+    "v_mad_i64_i32 v[42:43], s[20:21], %[c], v49, v[58:59]\n\t"                   \
+    "v_mad_i64_i32 v[50:51], s[20:21], %[d], v49, v[58:59]\n\t"                   \
+    "v_mad_i64_i32 v[52:53], s[20:21], %[b], v49, v[58:59]\n\t"                   \
+    "v_add3_u32 v44, v41, v43, v51\n\t"                                           \
+    "v_add3_u32 v44, v44, v53, 4\n\t"                                             \
+    "v_min3_u32 v45, v40, v42, v50\n\t"                                           \
+    "v_min3_u32 v45, v45, v52, %[a]\n\t"                                          \
+    "v_min_u32_dpp v45, v45, v45" QP1                                             \
+    "v_add_u32 v46, v46, %[b]\n\t"                                                \
+    "v_add_u32_dpp v44, v44, v44" QP1                                             \
+    "v_min_u32_dpp v45, v45, v45" QP2                                             \
+    "v_bfe_u32 v47, v46, 5, 5\n\t"                                                \
+    "v_add_u32_dpp v44, v44, v44" QP2                                             \
+    "v_lshl_add_u32 %[a], v44, 8, v45\n\t"
 #define BLOCK_U                                                                   \
     "v_cmp_lt_u32_e64 s[20:21], %[a], %[b]\n\t"                                   \
     "v_cmp_lt_u32_e64 s[22:23], %[a], %[c]\n\t"                                   \
@@ -260,6 +290,8 @@ SYM_KERNEL(k_sym_gap0_b64, "", LEAF64, ATOM)
         sink[threadIdx.x & 4095] = v0 + v1 + v2 + v3;                                             \
     }
 BK(k_blk_a, BLOCK_A, 0)
+BK(k_blk_a_mul, BLOCK_A_MUL, 0)
+BK(k_blk_a2, BLOCK_A2, 0)
 BK(k_blk_u, BLOCK_U, 0)
 BK(k_blk_c, BLOCK_C, 0)
 BK(k_blk_auc, BLOCK_A BLOCK_U BLOCK_C, 0)
@@ -319,7 +351,7 @@ int main(int argc, char** argv)
     hipMalloc(&sink, (4 << 20) + 4096 * 4);
     const char* only = argc > 3 ? argv[3] : nullptr;
 #define C(k, per) {#k, k, per}
-    std::vector<Case> cases = {C(k_add_dep, 1), C(k_add_indep, 2), C(k_mul24, 1), C(k_mad64, 1), C(k_mulhi, 1), C(k_mullo, 1),
+    std::vector<Case> cases = {C(k_add_dep, 1), C(k_add_indep, 2), C(k_mul24, 1), C(k_mad64, 1), C(k_madi64, 1), C(k_madi64_x4, 8), C(k_mulhi, 1), C(k_mullo, 1),
                                C(k_lshl64, 1), C(k_add_nop0, 2), C(k_add_nop1, 2), C(k_add_nop3, 2), C(k_dpp_dep, 2), C(k_dpp_fill, 3),
                                C(k_cmp_addc, 3), C(k_cmp5_addc5, 10), C(k_min3, 1), C(k_perm, 1), C(k_alignbit, 1), C(k_lds_b32, 1),
                                C(k_lds_b64, 1), C(k_lds_b128, 2), C(k_lds_b128_same, 2), C(k_lds_read2, 2), C(k_lds_add, 1), C(k_lds_add_read, 3),
@@ -329,7 +361,7 @@ int main(int argc, char** argv)
                                C(k_t_wr_b64, 9), C(k_t_wr_b128, 9), C(k_t_add, 9), C(k_t_add_rd128, 10), C(k_t_wr128_rd128, 10), C(k_t_waitcnt, 9), C(k_t_sdwa, 9), C(k_v_ld_scatter, 9), C(k_v_ld_contig, 9), C(k_v_st_scatter, 9), C(k_v_st_contig, 9), C(k_v_st4_scatter, 9),
                                C(k_sym_gap0, 65), C(k_sym_gap4, 69), C(k_sym_gap8, 73), C(k_sym_gap12, 77), C(k_sym_gap16, 81), C(k_sym_gap24, 89),
                                C(k_sym_gap32, 97), C(k_sym_gap12_noatom, 76), C(k_sym_gap12_b64, 77), C(k_sym_gap0_b64, 65),
-                               C(k_blk_a, 17), C(k_blk_u, 9), C(k_blk_c, 36), C(k_blk_auc, 62), C(k_loop_auc, 62), C(k_loop_add62, 62), C(k_loop_min3_62, 62),
+                               C(k_blk_a, 17), C(k_blk_a_mul, 21), C(k_blk_a2, 15), C(k_blk_u, 9), C(k_blk_c, 36), C(k_blk_auc, 62), C(k_loop_auc, 62), C(k_loop_add62, 62), C(k_loop_min3_62, 62),
                                C(k_pat_84, 62), C(k_pat_884, 62), C(k_pat_844, 62), C(k_pat_8884, 62), C(k_pat_D62, 62),
                                C(k_bank_same3, 62), C(k_bank_diff3, 62), C(k_bank_same2, 62), C(k_mad64_same, 62), C(k_subco_chain, 62)};
     printf("waves/workgroup %d, workgroups %d, %d copies per measurement\n", waves, wgs, REPS);
