@@ -9,7 +9,6 @@ only ever read the JSON.
 
     python tests/golden/make_golden.py
 """
-import hashlib
 import json
 import os
 import sys
@@ -21,12 +20,10 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import golden_cases  # noqa: E402
 import oracle_lib  # noqa: E402
 from cpprcoder_amd import workloads  # noqa: E402
-
-
-def sha(b) -> str:
-    return hashlib.sha256(bytes(b)).hexdigest()
+from oracle_lib import sha  # noqa: E402
 
 
 def main() -> None:
@@ -47,16 +44,9 @@ def main() -> None:
                     "static_ok": ok, "static_size": ssize, "static_sha256": sha(sout), "static_tail_hex": sout[516:].hex()})
 
     # ---- generated inputs, sizes + hashes ---------------------------------
-    gen = {
-        "A*65535": b"A" * 65535, "A*65536": b"A" * 65536, "A*65537": b"A" * 65537,
-        "ff*70000": b"\xff" * 70000,
-        "uniform(65536,12345)": workloads.uniform(65536, 12345).tobytes(),
-        "uniform(100000,7)": workloads.uniform(100000, 7).tobytes(),
-        "zipf(65536,12345)": workloads.zipf(65536, 12345).tobytes(),
-        "runs(200000,7)": workloads.runs(200000, 7).tobytes(),
-    }
     big = {}
-    for name, v in gen.items():
+    for name, make in golden_cases.GENERATED.items():
+        v = make()
         (st, rq), out, size = ref.adaptive_encode(v)
         ok, sout, ssize = ref.static_encode(v)
         big[name] = {"n": len(v), "input_sha256": sha(v), "adaptive_size": size, "adaptive_sha256": sha(out),

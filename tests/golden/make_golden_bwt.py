@@ -9,7 +9,6 @@ stored behind each block.  The reference publishes no block-sort numbers, so the
 
     python tests/golden/make_golden_bwt.py
 """
-import hashlib
 import json
 import os
 import sys
@@ -24,10 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bwt_cases  # noqa: E402
 import oracle_lib  # noqa: E402
 from cpprcoder_amd import workloads  # noqa: E402
-
-
-def sha(b) -> str:
-    return hashlib.sha256(bytes(b)).hexdigest()
+from oracle_lib import sha  # noqa: E402
 
 
 def main() -> None:

@@ -7,7 +7,6 @@ how to regenerate each input, and the size / hashes of the reference's output.
 
     python tests/golden/make_golden_long.py
 """
-import hashlib
 import json
 import os
 import sys
@@ -19,31 +18,10 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import golden_cases  # noqa: E402
 import oracle_lib  # noqa: E402
 from cpprcoder_amd import workloads  # noqa: E402
-
-NO_HALVING = (1 << 24) - 256  # RCX_MAX_BLOCK: the longest stream whose table is never halved
-
-
-def sha(b) -> str:
-    return hashlib.sha256(bytes(b)).hexdigest()
-
-
-def inputs():
-    """label -> bytes; tests regenerate the inputs from these recipes."""
-    return {
-        "uniform(2MiB+77,3)": workloads.uniform((2 << 20) + 77, 3),
-        "zipf(NO_HALVING,4)": workloads.zipf(NO_HALVING, 4),
-        "uniform(NO_HALVING+5000,11)": workloads.uniform(NO_HALVING + 5000, 11),
-        "min(zipf(2^24+70000,5),3)": np.minimum(workloads.zipf((1 << 24) + 70000, 5), 3).astype(np.uint8),
-    }
-
-
-def static_inputs():
-    return {
-        "zipf(2^24+1000,6)": workloads.zipf((1 << 24) + 1000, 6),
-        "runs(3MiB,2)": workloads.runs(3 << 20, 2),
-    }
+from oracle_lib import sha  # noqa: E402
 
 
 def main() -> None:
@@ -54,13 +32,15 @@ def main() -> None:
     fnv = oracle_lib.fnv1a64
     out = {"generator": "tests/golden/make_golden_long.py", "source": "oracle/_ref/libcpprcoder_ref.so (unmodified /root/reference/cpprcoder.h)",
            "adaptive": {}, "static": {}, "blocks": []}
-    for label, v in inputs().items():
+    for label, make in golden_cases.LONG_ADAPTIVE.items():
+        v = make()
         (st, rq), comp, size = ref.adaptive_encode(v)
         (dst, drq), back, dsize = ref.adaptive_decode(comp, len(v))
         assert (st, rq, dst, drq) == (0, 0, 0, 0) and back == v.tobytes(), label
         out["adaptive"][label] = {"n": len(v), "input_sha256": sha(v), "size": size, "sha256": sha(comp), "fnv1a64": "%016x" % fnv(comp)}
         print(label, len(v), size, flush=True)
-    for label, v in static_inputs().items():
+    for label, make in golden_cases.LONG_STATIC.items():
+        v = make()
         ok, comp, size = ref.static_encode(v)
         dok, back, dsize = ref.static_decode(comp, len(v))
         assert ok and dok and back == v.tobytes(), label

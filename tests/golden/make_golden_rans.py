@@ -8,7 +8,6 @@ states, 12-bit, 16-bit words).  The reference publishes no rANS numbers, so thes
 
     python tests/golden/make_golden_rans.py
 """
-import hashlib
 import json
 import os
 import sys
@@ -20,26 +19,14 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import golden_cases  # noqa: E402
 import oracle_lib  # noqa: E402
 from cpprcoder_amd import workloads  # noqa: E402
-
-
-def sha(b) -> str:
-    return hashlib.sha256(bytes(b)).hexdigest()
+from oracle_lib import sha  # noqa: E402
 
 
 SMALL = [b"\x00", b"\xff", b"ab", b"abcabcabcabc", b"hello world", b"\xff" * 16, b"\x00" * 17, bytes(range(256)),
          b"\x00\xff" * 40, b"The quick brown fox jumps over the lazy dog", bytes(range(7)) * 3]
-
-GENERATED = {
-    "A*65536": lambda: np.full(65536, 65, np.uint8),          # one symbol: encode_simd spends a word per symbol (cppans.h:357 wraps)
-    "uniform(65536,12345)": lambda: workloads.uniform(65536, 12345),
-    "uniform(100003,7)": lambda: workloads.uniform(100003, 7),
-    "zipf(65536,12345)": lambda: workloads.zipf(65536, 12345),
-    "runs(200000,7)": lambda: workloads.runs(200000, 7),
-    "two symbols 1:70000": lambda: np.concatenate([np.zeros(70000, np.uint8), np.ones(1, np.uint8)]),  # the steal loop of normalize()
-    "rare tail": lambda: np.concatenate([workloads.zipf(300000, 3), np.arange(256, dtype=np.uint8)]),
-}
 
 
 def main() -> None:
@@ -56,7 +43,7 @@ def main() -> None:
             assert ok and back == v
         kat.append({"input_hex": v.hex(), "rans_hex": a.hex(), "rans8_hex": b.hex()})
     big = {}
-    for name, make in GENERATED.items():
+    for name, make in golden_cases.RANS_GENERATED.items():
         v = make()
         a, b = ref.rans_encode(v, False), ref.rans_encode(v, True)
         big[name] = {"n": len(v), "input_sha256": sha(v), "rans_size": len(a), "rans_sha256": sha(a), "rans8_size": len(b), "rans8_sha256": sha(b)}

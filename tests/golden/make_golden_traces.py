@@ -5,7 +5,6 @@ caller that looks at its sink between calls sees.  Runs only in the build contai
 
     python tests/golden/make_golden_traces.py
 """
-import hashlib
 import json
 import os
 import sys
@@ -17,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle_lib  # noqa: E402
 import trace_cases  # noqa: E402
+from oracle_lib import sha  # noqa: E402
 
 
 def main() -> None:
@@ -27,8 +27,8 @@ def main() -> None:
     out = {"cases": []}
     for name, data, piece, cap in trace_cases.cases():
         (st, rq), sink, sizes = ref.adaptive_encode_trace(data, piece, cap)
-        out["cases"].append({"name": name, "n": len(data), "input_sha256": hashlib.sha256(bytes(data)).hexdigest(), "piece": piece,
-                             "sink_capacity": cap, "status": [st, rq], "sink_sizes": sizes, "sink_sha256": hashlib.sha256(sink).hexdigest()})
+        out["cases"].append({"name": name, "n": len(data), "input_sha256": sha(data), "piece": piece,
+                             "sink_capacity": cap, "status": [st, rq], "sink_sizes": sizes, "sink_sha256": sha(sink)})
         print(name, piece, cap, (st, rq), sizes[:6], "...", sizes[-1], flush=True)
     with open(os.path.join(HERE, "encode_traces.json"), "w") as f:
         json.dump(out, f, indent=1)

@@ -1,0 +1,447 @@
+"""What the GPU tests share: the launch-shape knobs and contexts made under them, the `ctx` fixture, guarded buffers and
+the device calls wrapped in them, the comparisons with the oracle that most tests make, and damaged streams.
+
+A test file imports what it needs from here (the fixture by name: `from gpu_support import ctx  # noqa: F401`, one
+context per importing module), never from another test file.  tests/test_support_cpu.py holds Guarded, knobs, chunk_blocks
+and the two comparisons to their contracts on CPU tensors.  Nothing here reads /root/reference.
+"""
+import contextlib
+import os
+import threading
+
+import numpy as np
+import pytest
+
+import oracle_lib
+from cpprcoder_amd import rcx, workloads
+
+torch = pytest.importorskip("torch")
+
+CODERS = (rcx.CODER_ADAPTIVE, rcx.CODER_STATIC, rcx.CODER_RANS, rcx.CODER_RANS8)
+HEAD = {0: 5, 1: 516, 2: 1032, 3: 1032}  # bytes in front of the coded payload: header (+ the adaptive coder's 0x00 / table)
+LOW = {0: (5, 9), 1: (516, 521)}          # the bytes the first renormalisation shifts in (the static coder skips 516)
+# the launch-shape variables, read when a context is created (rcx_api.hip rcx_ctx_create)
+KNOBS = ("RCX_DEC_QUADS", "RCX_WIDE_WG", "RCX_LANES_PER_BLOCK", "RCX_ENC_VARIANT", "RCX_ENC_LANES")
+
+
+# ---- the environment and contexts ------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def knobs(env, clear=()):
+    """The environment without the variables in `clear` and with those of `env`; what was there before is back on exit,
+    also on an exception."""
+    saved = {k: os.environ.get(k) for k in (*clear, *env)}
+    try:
+        for k in clear:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        yield
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def context(env=None):
+    """A context of the launch shape `env` asks for and no other (the knobs are read at creation)."""
+    with knobs(env or {}, clear=KNOBS):
+        return rcx.Context(0)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    c = rcx.Context(0)
+    yield c
+    c.close()
+
+
+# ---- guarded buffers ---------------------------------------------------------------------------------------------------
+GUARD = 256  # bytes of guard pattern on each side of every buffer a device call is handed
+
+
+class Guarded:
+    """A buffer handed to a kernel, as a view into a larger tensor: GUARD bytes, `offset` more, the buffer, GUARD
+    bytes.  Everything that is not buffer content holds a position-dependent pattern (nonzero; its complement with
+    `invert`), and a copy of the whole tensor is kept, so that a check after the call sees any byte written outside
+    the range the call may write, and any byte of an input that the call changed."""
+
+    def __init__(self, size, offset=0, content=None, salt=0, invert=False, device="cuda"):
+        self.at = GUARD + offset
+        self.size = size
+        i = np.arange(self.at + size + GUARD, dtype=np.int64)
+        image = ((i * 37 + salt * 101 + 11) % 251 + 1).astype(np.uint8)
+        if invert:
+            image = ~image
+        if content is not None:
+            image[self.at: self.at + len(content)] = np.frombuffer(np.ascontiguousarray(content).tobytes(), np.uint8)
+        self.tensor = torch.from_numpy(image).to(device)
+        self.before = self.tensor.clone()
+        self.view = self.tensor[self.at: self.at + size]
+
+    def check(self, written=0, what="buffer"):
+        """Nothing changed but the first `written` bytes of the buffer."""
+        hi = self.at + written
+        for lo_, hi_ in ((0, self.at), (hi, self.tensor.numel())):
+            if not torch.equal(self.tensor[lo_:hi_], self.before[lo_:hi_]):
+                first = lo_ + int(torch.nonzero(self.tensor[lo_:hi_] != self.before[lo_:hi_])[0, 0])
+                raise AssertionError(f"{what}: byte {first - self.at} changed, outside the {written} bytes from 0 it may write")
+
+
+# ---- the device calls, every buffer guarded ----------------------------------------------------------------------------
+def _encode(ctx, data, block, src_offset, coder, dst_offset, invert):
+    """-> (dst, offs, offsets np.uint64): the guarded destination and table after the call and its checks."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    n = len(data)
+    nblocks = rcx.block_count(n, block)
+    src = Guarded(n, src_offset, data, salt=1, invert=invert)
+    dst = Guarded(rcx.encode_bound(n, block, coder), dst_offset, salt=2, invert=invert)
+    offs = Guarded(8 * (nblocks + 1), 0, salt=3, invert=invert)
+    ctx.encode_blocks_device(src.view, block, dst.view, offs.view.view(torch.int64), coder=coder)
+    ctx.sync_status()
+    offsets = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
+    src.check(0, "encode src")
+    offs.check(8 * (nblocks + 1), "encode offsets")
+    dst.check(int(offsets[-1]), "encode dst")
+    return dst, offs, offsets
+
+
+def gpu_encode(ctx, data, block, src_offset=0, coder=0, dst_offset=0, invert=False):
+    """-> (payload np.uint8, offsets np.uint64, the device views) through the device-pointer entry points.  Every buffer is
+    guarded (Guarded): the source is not written, and nothing is written past offsets[nblocks] of dst or around the table."""
+    dst, offs, offsets = _encode(ctx, data, block, src_offset, coder, dst_offset, invert)
+    return dst.view[: int(offsets[-1])].cpu().numpy(), offsets, (dst.view, offs.view.view(torch.int64))
+
+
+def gpu_decode(ctx, payload, offsets, n, block, dst_offset=0, comp_offset=0, coder=0, invert=False):
+    """Decode through the device-pointer entry point -> (out np.uint8, status, first bad block).  The compressed bytes
+    and the table are guarded inputs (not written; what lies behind comp_size is the guard pattern, not zeros), and
+    nothing is written outside the n output bytes."""
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
+    table = np.ascontiguousarray(np.asarray(offsets).astype(np.int64))
+    offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
+    out = Guarded(n, dst_offset, salt=6, invert=invert)
+    ctx.decode_blocks_device(comp.view, len(payload), offs.view.view(torch.int64), n, block, out.view, coder=coder)
+    st, bad = ctx.sync_status(raise_on_error=False)
+    comp.check(0, "decode comp")
+    offs.check(0, "decode offsets")
+    out.check(n, "decode dst")
+    return out.view.cpu().numpy(), st, bad
+
+
+def round_trip_on_device(ctx, data, block, dst_offset=0):
+    """Encode, then decode from the encoder's own device buffers where they lie -> (out np.uint8, status).  The encoder
+    writes only the streams and the table, the decoder only its n output bytes, and neither writes its input."""
+    n = len(data)
+    dst, offs, offsets = _encode(ctx, data, block, 0, 0, 0, False)
+    dst.before, offs.before = dst.tensor.clone(), offs.tensor.clone()  # the decoder's inputs: nothing may change now
+    out = Guarded(n, dst_offset, salt=6)
+    ctx.decode_blocks_device(dst.view, int(offsets[-1]), offs.view.view(torch.int64), n, block, out.view)
+    st, _ = ctx.sync_status(raise_on_error=False)
+    dst.check(0, "decode comp")
+    offs.check(0, "decode offsets")
+    out.check(n, "decode dst")
+    return out.view.cpu().numpy(), st
+
+
+def encode_items(ctx, items, coder, src_offset=0, dst_offset=0, invert=False):
+    """Through the device call with every buffer guarded -> (payload, comp_offsets): the source is not written, the
+    destination only in [0, comp_offsets[nitems]), the table only in its nitems + 1 entries."""
+    lengths = [len(x) for x in items]
+    soffs = rcx.item_offsets(lengths)
+    data = np.concatenate(items) if items else np.zeros(0, np.uint8)
+    src = Guarded(len(data), src_offset, data, salt=1, invert=invert)
+    dst = Guarded(rcx.encode_items_bound(soffs, coder), dst_offset, salt=2, invert=invert)
+    offs = Guarded(8 * len(soffs), 0, salt=3, invert=invert)
+    ctx.encode_items_device(src.view, soffs, dst.view, offs.view.view(torch.int64), coder=coder)
+    ctx.sync_status()
+    table = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
+    src.check(0, "encode src")
+    offs.check(8 * len(soffs), "encode table")
+    dst.check(int(table[-1]), "encode dst")
+    return dst.view[: int(table[-1])].cpu().numpy(), table
+
+
+def decode_items(ctx, payload, comp_offsets, lengths, coder, pick=None, comp_offset=0, dst_offset=0, invert=False):
+    """Through the device call, guarded -> (list of the picked items' bytes, status, first bad index).  `lengths` are the
+    decoded lengths of the picks."""
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
+    table = np.ascontiguousarray(np.asarray(comp_offsets).astype(np.int64))
+    offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
+    doffs = rcx.item_offsets(lengths)
+    n = int(doffs[-1])
+    out = Guarded(n, dst_offset, salt=6, invert=invert)
+    ctx.decode_items_device(comp.view, len(payload), offs.view.view(torch.int64), doffs, out.view, pick=pick, coder=coder)
+    st, bad = ctx.sync_status(raise_on_error=False)
+    comp.check(0, "decode comp")
+    offs.check(0, "decode table")
+    out.check(n, "decode dst")
+    flat = out.view.cpu().numpy()
+    return [flat[int(doffs[k]): int(doffs[k + 1])] for k in range(len(lengths))], st, bad
+
+
+# ---- comparisons with the oracle ---------------------------------------------------------------------------------------
+def _tag(label):
+    return "" if label is None else f"{label}: "
+
+
+def assert_same_blocks(payload, offsets, slots, sizes, label=None):
+    assert np.array_equal(np.diff(offsets.astype(np.int64)), sizes.astype(np.int64)), f"{_tag(label)}per-block sizes differ"
+    for b in range(len(sizes)):
+        got = payload[int(offsets[b]): int(offsets[b + 1])]
+        assert np.array_equal(got, slots[b, : int(sizes[b])]), f"{_tag(label)}block {b} differs"
+
+
+def assert_same_items(payload, offsets, want, label=None):
+    """`want`: every item's stream, None for an item of length 0 (which has no stream)."""
+    table = np.concatenate([[0], np.cumsum([0 if s is None else len(s) for s in want], dtype=np.int64)])
+    assert np.array_equal(np.asarray(offsets).astype(np.int64), table), f"{_tag(label)}comp_offsets differ from the oracle's sizes"
+    for i, s in enumerate(want):
+        got = payload[int(offsets[i]): int(offsets[i + 1])]
+        assert s is None or np.array_equal(got, s), f"{_tag(label)}item {i} differs"
+
+
+def check_blocks(ctx, oracle, data, block, coder=0, src_offset=0, dst_offset=0, comp_offset=0, threads=8, label=None):
+    """The oracle encodes, the GPU encodes (the source at src_offset), every block's stream is the oracle's, the GPU decodes
+    (from comp_offset, to dst_offset) and the bytes are `data` again -> (payload, offsets)."""
+    slots, sizes = oracle.encode_blocks(data, block, coder=coder, threads=threads)
+    payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=src_offset, coder=coder)
+    assert_same_blocks(payload, offsets, slots, sizes, label)
+    back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block, dst_offset=dst_offset, comp_offset=comp_offset, coder=coder)
+    assert st == 0 and np.array_equal(back, data), f"{_tag(label)}status {st}, round trip"
+    return payload, offsets
+
+
+def check_items(ctx, items, want, coder=0, src_offset=0, dst_offset=0, comp_offset=0, out_offset=0, label=None):
+    """The item twin: the GPU encodes `items` (the source at src_offset, the streams to dst_offset), every stream is its
+    entry of `want`, the GPU decodes (from comp_offset, to out_offset) and every item is back -> (payload, comp_offsets)."""
+    payload, offs = encode_items(ctx, items, coder, src_offset=src_offset, dst_offset=dst_offset)
+    assert_same_items(payload, offs, want, label)
+    back, st, _ = decode_items(ctx, payload, offs, [len(x) for x in items], coder, comp_offset=comp_offset, dst_offset=out_offset)
+    assert st == rcx.OK, f"{_tag(label)}status {st}"
+    for i, x in enumerate(items):
+        assert np.array_equal(back[i], x), f"{_tag(label)}item {i} ({len(x)} bytes) does not round-trip"
+    return payload, offs
+
+
+def check_golden_blocks(ctx, t, coder):
+    """One block table of tests/golden: the input is the one the table was made from, every block's size and fnv1a64 (and
+    the total, where the table has one) are the reference's, and the round trip returns the input."""
+    label = (t["workload"], t["block"], t["coder"])
+    data = workloads.by_name(t["workload"], t["n"], t["seed"])
+    assert oracle_lib.sha(data) == t["input_sha256"], label
+    payload, offsets, _ = gpu_encode(ctx, data, t["block"], coder=coder)
+    assert [int(x) for x in np.diff(offsets.astype(np.int64))] == t["sizes"], label
+    fnv = ["%016x" % oracle_lib.fnv1a64(payload[int(offsets[b]): int(offsets[b + 1])]) for b in range(len(t["sizes"]))]
+    assert fnv == t["fnv1a64"], label
+    if "total" in t:
+        assert int(offsets[-1]) == t["total"], label
+    back, st, _ = gpu_decode(ctx, payload, offsets, t["n"], t["block"], coder=coder)
+    assert st == 0 and np.array_equal(back, data), label
+
+
+def oracle_streams(oracle, items, coder, threads=16):
+    """The reference's stream of every item on its own (None for an item of length 0, which has no stream)."""
+    out = [None] * len(items)
+
+    def work(first):
+        for i in range(first, len(items), threads):
+            if len(items[i]):
+                slots, sizes = oracle.encode_blocks(items[i], len(items[i]), coder=coder)
+                out[i] = slots[0, : int(sizes[0])].copy()
+
+    pool = [threading.Thread(target=work, args=(t,)) for t in range(threads)]
+    for t in pool:
+        t.start()
+    for t in pool:
+        t.join()
+    return out
+
+
+def oracle_decode_one(oracle, stream, length, coder, block):
+    """The oracle on one stream alone, reading no byte past it -> (every symbol decoded, bytes).  `block` is the block
+    size the oracle is told (it sizes its sink from it); each caller passes its own."""
+    slots = np.zeros((1, len(stream) + 64), np.uint8)
+    slots[0, : len(stream)] = stream
+    out, ok = oracle.decode_blocks(slots, np.array([len(stream)], np.uint32), block, length, coder=coder)
+    return ok, out
+
+
+def chunk_blocks(block, decode, nblocks):
+    """csrc/rcx_host.hpp host_chunk_blocks(): how many blocks the host-buffer calls put into a chunk."""
+    cb = max(4096 if decode else 2048, -(-(16 << 20) // block))
+    while -(-nblocks // cb) > 2048:
+        cb *= 2
+    chunks = -(-nblocks // cb)
+    if chunks > 1:
+        cb = -(-nblocks // chunks)
+    return (cb + 63) & ~63
+
+
+# ---- damaged streams (include/rcx.h, "Damaged streams") ----------------------------------------------------------------
+# per coder; the static coder's bytes use every value, so no count is 0 and its damaged streams decode (see Damaged.damage)
+DATA = ("zipf", "uniform", "zipf", "canterbury")
+COUNT0 = "past the table onto a count of 0"
+
+
+def first_wrong(oracle, stream, good, block, coder):
+    ok, out = oracle_decode_one(oracle, stream, len(good), coder, block)
+    if not ok:
+        return None
+    diff = np.nonzero(out != good)[0]
+    return int(diff[0]) if len(diff) else None
+
+
+def flip_at_symbol(oracle, stream, size, good, block, coder, targets):
+    """A single byte flip in `stream` (`size` bytes of stream, then padding) whose first wrong symbol is one of `targets`
+    (a set of symbol indices), found by trying positions around the one that an even spread of the bytes gives."""
+    lo = HEAD[coder] + 4
+    pay = size - lo
+    for want in sorted(targets):
+        guess = lo + int(pay * want / max(len(good), 1))
+        for p in sorted(range(max(lo, guess - 48), min(len(stream) - 4, guess + 48)), key=lambda q: abs(q - guess)):
+            for x in (0x01, 0x80, 0x5A):
+                s = stream.copy()
+                s[p] ^= x
+                if first_wrong(oracle, s, good, block, coder) in targets:
+                    return s
+    return None
+
+
+class Damaged:
+    """Oracle streams of `data` with some blocks damaged: slots (rows padded as needed), sizes, and per block the kind."""
+
+    def __init__(self, oracle, data, block, coder, seed):
+        self.oracle, self.data, self.block, self.coder = oracle, data, block, coder
+        self.rs = np.random.RandomState(seed)
+        slots, sizes = oracle.encode_blocks(data, block, coder=coder, threads=8)
+        self.nblocks = len(sizes)
+        self.pad = 3 * block
+        self.orig = [slots[b, : int(sizes[b])].copy() for b in range(self.nblocks)]
+        self.rows = list(self.orig)
+        self.kind = {}
+
+    def length(self, b):
+        return min(self.block, len(self.data) - b * self.block)
+
+    def good(self, b):
+        return self.data[b * self.block: b * self.block + self.length(b)]
+
+    def padded(self, b):
+        return np.concatenate([self.orig[b], self.rs.randint(0, 256, self.pad).astype(np.uint8)])
+
+    def decode_one(self, b):
+        """The oracle on block b's stream as it is now, alone -> (ok, bytes)."""
+        return oracle_decode_one(self.oracle, self.rows[b], self.length(b), self.coder, self.block)
+
+    def damage(self, b, kind, stream, fails=False):
+        """fails: the reference cannot decode this stream, padding or not.  That is only the static coder's symbol of count
+        0: find() (cpprcoder.h:521-535) never fails -- a target at or past the total falls through to symbol 255 -- but if
+        the symbol it gives has count 0, range becomes 0 and the renormalisation (:506-513) runs dry.  Every other damaged
+        stream here is padded so that the oracle decodes it completely, and that is checked."""
+        ok, _ = oracle_decode_one(self.oracle, stream, self.length(b), self.coder, self.block)
+        assert ok != fails, f"block {b} ({kind}): the oracle {'decodes' if ok else 'fails on'} it"
+        self.rows[b], self.kind[b] = stream, kind
+
+    def restore(self, b):
+        self.rows[b] = self.orig[b]
+        self.kind.pop(b, None)
+
+    def truncate(self, b, k):
+        self.rows[b], self.kind[b] = self.orig[b][:-k], f"truncated by {k}"
+
+    def streams(self):
+        sizes = np.array([len(r) for r in self.rows], np.uint64)
+        offsets = np.zeros(self.nblocks + 1, np.uint64)
+        np.cumsum(sizes, out=offsets[1:])
+        return np.concatenate(self.rows), offsets
+
+    def expected(self):
+        """-> (status, first bad block or None, {block: expected bytes} for the blocks whose bytes are asserted)"""
+        bad, want = [], {}
+        for b in range(self.nblocks):
+            if b not in self.kind:
+                want[b] = self.good(b)
+                continue
+            ok, out = self.decode_one(b)
+            if not ok:
+                bad.append(b)
+            else:  # (a truncated stream the reference still decodes completely included)
+                want[b] = out
+        return (rcx.E_CORRUPT if bad else rcx.OK), (bad[0] if bad else None), want
+
+
+def build(oracle, coder, block, nblocks, seed):
+    """About nblocks blocks, the last one ragged; damage of every kind the coder has, in blocks spread over the call."""
+    data = workloads.by_name(DATA[coder], (nblocks - 1) * block + block // 4 + 7, seed)
+    d = Damaged(oracle, data, block, coder, seed)
+    groups = block // 16
+    b = 1
+    if coder in LOW:
+        s = d.padded(b)
+        s[LOW[coder][0]: LOW[coder][1]] = 0xFF  # the first target at or past the table
+        d.damage(b, "first target past the table", s)
+        b += 2
+        for name, targets in (("group position 0", {16 * g for g in range(3, 12)}), ("group position 1", {16 * g + 1 for g in range(3, 12)}),
+                              ("group position 15", {16 * g + 15 for g in range(3, 12)}),
+                              ("last group of the fast loop", set(range(16 * (groups - 1), 16 * groups - 2)))):
+            s = flip_at_symbol(oracle, d.padded(b), len(d.orig[b]), d.good(b), block, coder, targets)
+            assert s is not None, name
+            d.damage(b, name, s)
+            b += 2
+        for name, fill in (("run of 0xFF", 0xFF), ("run of 0x00", 0x00)):
+            s = d.padded(b)
+            at = HEAD[coder] + 4 + (len(d.orig[b]) - HEAD[coder]) // 2
+            s[at: at + 48] = fill
+            d.damage(b, name, s)
+            b += 2
+    if coder == rcx.CODER_STATIC:
+        for name in ("count to 0", "count moved"):
+            s = d.padded(b)
+            counts = s[4:516].view("<u2").copy()
+            used = np.nonzero(counts)[0]
+            src, dst = used[len(used) // 2], used[0]
+            if name == "count moved":
+                counts[dst] = min(int(counts[dst]) + int(counts[src]), 0xFFFF)
+            counts[src] = 0
+            s[4:516] = counts.view(np.uint8)
+            d.damage(b, name, s)
+            b += 2
+        # the first target past the table, where find() falls through to symbol 255, whose count is now 0: range 0, the
+        # reference runs dry whatever follows (cpprcoder.h:500-513), so the call reports RCX_E_CORRUPT for this block
+        s = d.padded(b)
+        s[4 + 2 * 255: 4 + 2 * 256] = 0
+        s[LOW[coder][0]: LOW[coder][1]] = 0xFF
+        d.damage(b, COUNT0, s, fails=True)
+        b += 2
+    if coder in (rcx.CODER_RANS, rcx.CODER_RANS8):
+        for i in range(4):
+            s = d.padded(b)
+            z = len(d.orig[b])
+            for _ in range(1 + i):
+                s[int(d.rs.randint(HEAD[coder] + 16, z))] ^= int(d.rs.randint(1, 256))
+            d.damage(b, f"payload flips ({1 + i})", s)
+            b += 2
+    last = d.nblocks - 1  # the ragged last block: a flip in its symbol-by-symbol tail
+    if coder in LOW:
+        n_last = d.length(last)
+        s = flip_at_symbol(oracle, d.padded(last), len(d.orig[last]), d.good(last), block, coder, set(range(16 * (n_last // 16), n_last)))
+        assert s is not None, "tail flip"
+        d.damage(last, "flip in the tail", s)
+    return d
+
+
+def check_call(ctx, d, block, dst_offset, label):
+    payload, offsets = d.streams()
+    n = len(d.data)
+    back, st, first = gpu_decode(ctx, payload, offsets, n, block, dst_offset=dst_offset, coder=d.coder)
+    want_st, want_first, want = d.expected()
+    assert st == want_st, (label, st, want_st)
+    if want_first is not None:
+        assert first == want_first, (label, first, want_first)
+    for b, w in want.items():
+        got = back[b * block: b * block + len(w)]
+        assert np.array_equal(got, w), (label, b, d.kind.get(b, "undamaged"))

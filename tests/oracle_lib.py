@@ -12,6 +12,7 @@ cpu_baseline leg import this module.
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import subprocess
 import threading
@@ -328,3 +329,8 @@ def fnv1a64(data) -> int:
     lib.rco_fnv1a64.restype, lib.rco_fnv1a64.argtypes = C.c_uint64, [C.c_void_p, C.c_uint64]
     a = _u8(data)
     return int(lib.rco_fnv1a64(a.ctypes.data, len(a)))
+
+
+def sha(b) -> str:
+    """sha256 of bytes, or of an array's bytes, in hex."""
+    return hashlib.sha256(bytes(b)).hexdigest()

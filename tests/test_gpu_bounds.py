@@ -1,6 +1,6 @@
 """Buffer bounds of the device calls, all four coders (include/rcx.h: what the device calls write and read).
 
-Every buffer is a view into a larger tensor with guard bytes on both sides (test_gpu_parity.Guarded).  Encode writes
+Every buffer is a view into a larger tensor with guard bytes on both sides (gpu_support.Guarded).  Encode writes
 exactly [dst, dst + offsets[nblocks]) and offsets[0 .. nblocks]; decode writes exactly [dst, dst + n); neither writes
 its input, and neither result depends on the bytes behind src + n or comp_size.  The cases reach every residue of the
 three pointers modulo 16, block sizes that are and are not multiples of 16 and 64, and last blocks whose length is 1, 15,
@@ -11,22 +11,13 @@ import numpy as np
 import pytest
 
 from cpprcoder_amd import rcx, workloads
-from test_gpu_parity import GUARD, Guarded, gpu_decode, gpu_encode
+from gpu_support import CODERS, GUARD, Guarded, ctx, gpu_decode, gpu_encode  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-CODERS = (rcx.CODER_ADAPTIVE, rcx.CODER_STATIC, rcx.CODER_RANS, rcx.CODER_RANS8)
 LASTS = (1, 15, 16, 17, 63, 64, 65)  # the last block's length, plus a multiple of 64 (65: residue 1 with a whole 64 in front)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    c = rcx.Context(0)
-    yield c
-    c.close()
 
 
 def alignments():

@@ -2,7 +2,6 @@
 the stored row index, periodic blocks included -- must be what the real reference wrote (tests/golden/bwt.json, made
 from the reference build by tests/golden/make_golden_bwt.py), and decode must give what BlkSort::decode gives, for
 transformed blocks and for arbitrary bytes (the oracle restates blksort.h and is itself pinned to that build)."""
-import hashlib
 import json
 import os
 
@@ -12,15 +11,13 @@ import pytest
 import bwt_cases
 import oracle_lib
 from cpprcoder_amd import workloads
+from gpu_support import knobs
+from oracle_lib import sha
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
 BLOCK, ENCODED = bwt_cases.BLOCK, bwt_cases.ENCODED
-
-
-def sha(b) -> str:
-    return hashlib.sha256(bytes(b)).hexdigest()
 
 
 @pytest.fixture(scope="module", params=["ballot", "atomic"])
@@ -30,15 +27,10 @@ def ctx(request):
     RCX_BWT_MATCH=atomic (read at the context's first block-sort call, so it stays set while the context lives)."""
     from cpprcoder_amd import rcx
     assert torch.cuda.is_available(), "GPU tests need a GPU"
-    before = os.environ.get("RCX_BWT_MATCH")
-    os.environ["RCX_BWT_MATCH"] = request.param
-    c = rcx.Context(0)
-    yield c
-    c.close()
-    if before is None:
-        os.environ.pop("RCX_BWT_MATCH", None)
-    else:
-        os.environ["RCX_BWT_MATCH"] = before
+    with knobs({"RCX_BWT_MATCH": request.param}):
+        c = rcx.Context(0)
+        yield c
+        c.close()
 
 
 @pytest.fixture(scope="module")

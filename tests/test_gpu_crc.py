@@ -15,21 +15,13 @@ import numpy as np
 import pytest
 
 from cpprcoder_amd import container, rcx, workloads
+from gpu_support import Guarded, ctx, oracle_decode_one  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0x5A5A5A5A
-GUARD = 8
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rcx.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")
@@ -49,16 +41,15 @@ def zlib_blocks(data, block):
 
 
 def guarded(count):
-    """A tensor of sentinels with room for `count` results in its middle -> (whole, the middle)."""
-    whole = torch.full((count + 2 * GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
-    return whole, whole[GUARD: GUARD + count]
+    """Room for `count` results in a guarded buffer (gpu_support.Guarded) -> (the buffer, its middle as int32)."""
+    whole = Guarded(4 * count, salt=7)
+    return whole, whole.view.view(torch.int32)
 
 
 def results(whole, count):
-    """The middle as uint32, after checking that nothing around it changed."""
-    host = whole.cpu().numpy().view(np.uint32)
-    assert np.all(host[:GUARD] == SENTINEL) and np.all(host[GUARD + count:] == SENTINEL), "wrote outside d_crc[0 .. count)"
-    return host[GUARD: GUARD + count].copy()
+    """The first `count` results as uint32, after checking that nothing else of the buffer or around it changed."""
+    whole.check(4 * count, "d_crc")
+    return whole.view[: 4 * count].cpu().numpy().view(np.uint32).copy()
 
 
 def items_on_gpu(ctx, d_src, offs):
@@ -182,7 +173,7 @@ def test_nothing_to_do_and_bad_arguments_write_nothing(ctx, noise):
                L.rcx_crc32_items(h, noise.ctypes.data, down.ctypes.data, 3, crc), L.rcx_crc32_items(h, None, o, 3, crc)):
         assert st == rcx.E_ARG
     assert ctx.sync_status(raise_on_error=False)[0] == rcx.OK  # the latch is clean
-    assert len(results(whole, 0)) == 0 and np.all(whole.cpu().numpy().view(np.uint32) == SENTINEL)
+    assert len(results(whole, 0)) == 0  # (not one of the 16 result words changed, nor anything around them)
     # and the context still works
     assert np.array_equal(items_on_gpu(ctx, d_src, offs), zlib_items(noise[:4096], offs))
 
@@ -273,17 +264,10 @@ def test_verify_items(ctx, noise):
 GAP_BLOCK = 4096
 
 
-def decode_one(oracle, stream, length, coder=0):
-    """The CPU oracle on one stream alone, reading no byte past it -> (every symbol decoded, bytes)."""
-    slots = np.zeros((1, len(stream) + 64), np.uint8)
-    slots[0, : len(stream)] = stream
-    out, ok = oracle.decode_blocks(slots, np.array([len(stream)], np.uint32), max(length, 16), length, coder=coder)
-    return ok, out
-
-
 def silent_flips(oracle, streams, goods, want=3, limit=200):
     """Single-bit flips in a stream's payload that the oracle decodes completely, to other bytes than the original:
-    -> [(stream index, byte in the stream, bit, what it decodes to)], scanning at most `limit` candidates."""
+    -> [(stream index, byte in the stream, bit, what it decodes to)], scanning at most `limit` candidates.  (The oracle
+    decodes one stream alone and reads no byte past it.)"""
     found, tried = [], 0
     for back in range(6, 6 + 64):  # towards the end of a stream a flip changes few symbols and little of what is read
         for b in range(len(streams)):
@@ -295,7 +279,7 @@ def silent_flips(oracle, streams, goods, want=3, limit=200):
             s = streams[b].copy()
             at, bit = len(s) - back, 1 << (tried % 8)
             s[at] ^= bit
-            ok, out = decode_one(oracle, s, len(goods[b]))
+            ok, out = oracle_decode_one(oracle, s, len(goods[b]), 0, max(len(goods[b]), 16))
             if ok and not np.array_equal(out, goods[b]):
                 found.append((b, at, bit, out))
     return found, tried

@@ -11,8 +11,7 @@ import numpy as np
 import pytest
 
 from cpprcoder_amd import rcx, workloads
-from test_gpu_damaged import Damaged, check_call, context
-from test_gpu_parity import assert_same_blocks, gpu_decode, gpu_encode
+from gpu_support import Damaged, assert_same_blocks, check_call, context, gpu_decode, gpu_encode
 
 pytestmark = pytest.mark.gpu
 
@@ -141,13 +140,8 @@ def test_target_past_the_table_among_valid_blocks(contexts, oracle, position):
     stream, at_symbol = made
     d.damage(b, f"target past the table at symbol {at_symbol}", stream)
     # the reference's find() falls through with symbol 0 and count = total there, and the block goes on differently from its data
-    ok, out = decode_one_block(d, b)
+    ok, out = d.decode_one(b)
     assert ok and np.array_equal(out[:at_symbol], d.good(b)[:at_symbol]) and out[at_symbol] == 0
     assert not np.array_equal(out, d.good(b))
     for name in ("quads16", "default"):
         check_call(contexts[name], d, BLOCK, 0, (name, position))
-
-
-def decode_one_block(d, b):
-    from test_gpu_damaged import decode_one
-    return decode_one(d.oracle, d.rows[b], d.length(b), d.block, d.coder)

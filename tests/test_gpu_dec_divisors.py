@@ -9,47 +9,12 @@ SIMD).  The encoder is held to the oracle elsewhere, so decode(encode(x)) == x i
 import numpy as np
 import pytest
 
-from cpprcoder_amd import rcx, workloads
+from cpprcoder_amd import workloads
+from gpu_support import ctx, round_trip_on_device  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-from test_gpu_parity import Guarded  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    c = rcx.Context(0)
-    yield c
-    c.close()
-
-
-def round_trip(ctx, data, block, dst_offset=0):
-    """Encode and decode on the device, every buffer guarded (test_gpu_parity.Guarded): the encoder writes only the
-    streams and the table, the decoder only its n output bytes, and neither writes its input."""
-    n = len(data)
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    nblocks = rcx.block_count(n, block)
-    src = Guarded(n, 0, data, salt=1)
-    dst = Guarded(rcx.encode_bound(n, block), 0, salt=2)
-    offs = Guarded(8 * (nblocks + 1), 0, salt=3)
-    table = offs.view.view(torch.int64)
-    ctx.encode_blocks_device(src.view, block, dst.view, table)
-    ctx.sync_status()
-    total = int(table[-1].item())
-    src.check(0, "encode src")
-    offs.check(8 * (nblocks + 1), "encode offsets")
-    dst.check(total, "encode dst")
-    dst.before, offs.before = dst.tensor.clone(), offs.tensor.clone()  # the decoder's inputs: nothing may change now
-    out = Guarded(n, dst_offset, salt=6)
-    ctx.decode_blocks_device(dst.view, total, table, n, block, out.view)
-    st, _ = ctx.sync_status(raise_on_error=False)
-    dst.check(0, "decode comp")
-    offs.check(0, "decode offsets")
-    out.check(n, "decode dst")
-    return out.view.cpu().numpy(), st
 
 
 def lengths_around_powers_of_two(top):
@@ -68,7 +33,7 @@ def test_single_blocks_across_shift_changes(ctx, wl):
     block = 1 << 18
     for i, n in enumerate(lengths_around_powers_of_two(block)):
         data = workloads.by_name(wl, n, 77 + i)
-        back, st = round_trip(ctx, data, block)
+        back, st = round_trip_on_device(ctx, data, block)
         assert st == 0 and np.array_equal(back, data), f"{wl}, {n} bytes"
 
 
@@ -79,7 +44,7 @@ def test_wave_with_a_ragged_block_across_a_shift_change(ctx, block):
     for last in ((1 << 11) - 256 + 3, (1 << 12) - 256 - 1, block - 1):
         n = 15 * block + last
         data = workloads.by_name("zipf", n, last)
-        back, st = round_trip(ctx, data, block)
+        back, st = round_trip_on_device(ctx, data, block)
         assert st == 0 and np.array_equal(back, data), f"block {block}, last {last}"
 
 
@@ -87,7 +52,7 @@ def test_wave_with_a_ragged_block_across_a_shift_change(ctx, block):
 def test_unaligned_output_runs_all_symbols_through_the_tail(ctx, block):
     n = 40 * block + 999
     data = workloads.by_name("uniform", n, block)
-    back, st = round_trip(ctx, data, block, dst_offset=3)
+    back, st = round_trip_on_device(ctx, data, block, dst_offset=3)
     assert st == 0 and np.array_equal(back, data)
 
 
@@ -96,5 +61,5 @@ def test_every_launch_shape(ctx, nblocks):
     block = 4096
     n = nblocks * block - 100
     data = workloads.by_name("zipf" if nblocks % 2 else "uniform", n, nblocks)
-    back, st = round_trip(ctx, data, block)
+    back, st = round_trip_on_device(ctx, data, block)
     assert st == 0 and np.array_equal(back, data), f"{nblocks} blocks"

@@ -12,8 +12,7 @@ import numpy as np
 import pytest
 
 from cpprcoder_amd import rcx
-from test_gpu_parity import assert_same_blocks, gpu_decode, gpu_encode
-from test_gpu_items import decode_items, encode_items, oracle_streams
+from gpu_support import check_blocks, check_items, ctx, oracle_streams  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +20,6 @@ torch = pytest.importorskip("torch")
 
 MANY = 8250  # = 128 x 64 + 58
 EDGES = np.array([0, 63, 64, 127, 128, 191, 192, 255], np.uint8)  # both sides of every level-3 boundary
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    c = rcx.Context(0)
-    yield c
-    c.close()
 
 
 def symbols(name, n, seed=0):
@@ -43,14 +34,6 @@ def symbols(name, n, seed=0):
 
 
 SETS = ("edges", "quarter0", "quarter1", "quarter2", "quarter3")
-
-
-def check_blocks(ctx, oracle, data, block, src_offset=0):
-    slots, sizes = oracle.encode_blocks(data, block, threads=8)
-    payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=src_offset)
-    assert_same_blocks(payload, offsets, slots, sizes)
-    back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block)
-    assert st == 0 and np.array_equal(back, data)
 
 
 @pytest.mark.parametrize("block", [16, 32, 48, 64, 4096])
@@ -90,17 +73,6 @@ def test_guarded_pipeline(ctx, oracle, name):
         for block, nblocks in ((64, MANY), (4096, 65)):
             check_blocks(ctx, oracle, symbols(name, block * nblocks, 10 + i), block, src_offset=off)
         check_blocks(ctx, oracle, symbols(name, 64 * (MANY - 1) + 17, 20 + i), 64, src_offset=off)
-
-
-def check_items(ctx, items, want):
-    payload, offs = encode_items(ctx, items, rcx.CODER_ADAPTIVE)
-    assert np.array_equal(np.diff(offs.astype(np.int64)), [len(s) for s in want]), "comp_offsets differ from the oracle's sizes"
-    for i, s in enumerate(want):
-        assert np.array_equal(payload[int(offs[i]): int(offs[i + 1])], s), f"item {i} ({len(items[i])} bytes) differs"
-    back, st, _ = decode_items(ctx, payload, offs, [len(x) for x in items], rcx.CODER_ADAPTIVE)
-    assert st == rcx.OK
-    for i, x in enumerate(items):
-        assert np.array_equal(back[i], x), f"item {i} does not round-trip"
 
 
 @pytest.mark.parametrize("name", ("uniform", "edges", "quarter3"))

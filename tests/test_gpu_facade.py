@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from cpprcoder_amd import workloads
+from oracle_lib import sha
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,8 +157,6 @@ def test_resumable_encoder_hands_on_what_the_reference_writes(oracle):
     handed on so far must be the prefix of the stream the reference's sink holds by then (tests/golden/encode_traces.json,
     from the reference build; the oracle for the bytes), the results its results -- also when its sink fills in a symbol
     (cpprcoder.h:708-711) or only in finish() (cpprcoder.h:716)."""
-    import hashlib
-
     import trace_cases
     from cpprcoder_amd import rcx
     want = _goldens()
@@ -186,7 +185,7 @@ def test_resumable_encoder_hands_on_what_the_reference_writes(oracle):
             assert [st, rq] == w["status"], (name, st, rq)
             assert sizes == w["sink_sizes"], name
             shown = bytes(sink) if cap is None else bytes(sink)[:cap]  # (the generator kept min(size, requested capacity) bytes)
-            assert hashlib.sha256(shown).hexdigest() == w["sink_sha256"], name
+            assert sha(shown) == w["sink_sha256"], name
             assert shown == osink, name
             es.close()
         # rewind: a call taken back leaves no trace
@@ -232,6 +231,5 @@ def test_facade_encoder_writes_to_its_sink_as_it_goes(exe, tmp_path):
             assert [st, rq] == w["status"] and sizes == w["sink_sizes"], name
         else:
             assert [st, rq] == w["status"] and sizes == w["sink_sizes"], name
-        import hashlib
         got = p_dst.read_bytes()
-        assert hashlib.sha256(got if cap is None else got[:cap]).hexdigest() == w["sink_sha256"], name
+        assert sha(got if cap is None else got[:cap]) == w["sink_sha256"], name

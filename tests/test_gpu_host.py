@@ -9,6 +9,7 @@ import pytest
 import bwt_cases
 import oracle_lib
 from cpprcoder_amd import workloads
+from gpu_support import chunk_blocks
 
 pytestmark = pytest.mark.gpu
 
@@ -16,17 +17,6 @@ torch = pytest.importorskip("torch")
 
 BLOCK = 4096                      # small blocks: chunks are about 4096 blocks = 16 MiB, so a modest buffer spans many
 N = 5 * (16 << 20) + (9 << 20) + 1234  # 6 chunks and a ragged last block (1234 bytes)
-
-
-def chunk_blocks(block, decode, nblocks):
-    """csrc/rcx_host.hpp host_chunk_blocks(): how many blocks the host-buffer calls put into a chunk."""
-    cb = max(4096 if decode else 2048, -(-(16 << 20) // block))
-    while -(-nblocks // cb) > 2048:
-        cb *= 2
-    chunks = -(-nblocks // cb)
-    if chunks > 1:
-        cb = -(-nblocks // chunks)
-    return (cb + 63) & ~63
 
 
 @pytest.fixture(scope="module")

@@ -2,31 +2,18 @@
 of their streams back.  Expected bytes always come from the CPU oracle, item by item -- an item's stream is what the
 reference emits for a file of those bytes -- never from the code under test.  Nothing here reads /root/reference.
 """
-import threading
-
 import numpy as np
 import pytest
 
 from cpprcoder_amd import container, rcx, workloads
-from test_gpu_parity import GUARD, Guarded  # noqa: F401  (the guarded buffers of the block tests)
+from gpu_support import CODERS, GUARD, HEAD, LOW, Guarded, ctx  # noqa: F401
+from gpu_support import assert_same_items, check_items, decode_items, encode_items, oracle_decode_one, oracle_streams
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-CODERS = (rcx.CODER_ADAPTIVE, rcx.CODER_STATIC, rcx.CODER_RANS, rcx.CODER_RANS8)
 SPECIAL = (1, 2, 15, 16, 17, 63, 64, 65, 1000, 4095, 4096, 4097, 65536, 65537, 200_000)
-HEAD = {0: 5, 1: 516, 2: 1032, 3: 1032}  # bytes in front of the coded payload
-LOW = {0: (5, 9), 1: (516, 521)}          # the bytes the range decoders' first renormalisation shifts in
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    c = rcx.Context(0)
-    yield c
-    c.close()
-
 
 _POOLS = {}
 
@@ -54,67 +41,12 @@ def make_items(lengths):
     return items
 
 
-def oracle_streams(oracle, items, coder, threads=16):
-    """The reference's stream of every item on its own (None for an item of length 0, which has no stream)."""
-    out = [None] * len(items)
-
-    def work(first):
-        for i in range(first, len(items), threads):
-            if len(items[i]):
-                slots, sizes = oracle.encode_blocks(items[i], len(items[i]), coder=coder)
-                out[i] = slots[0, : int(sizes[0])].copy()
-
-    pool_ = [threading.Thread(target=work, args=(t,)) for t in range(threads)]
-    for t in pool_:
-        t.start()
-    for t in pool_:
-        t.join()
-    return out
-
-
 def compact(streams):
     sizes = np.array([0 if s is None else len(s) for s in streams], np.uint64)
     offs = np.zeros(len(streams) + 1, np.uint64)
     np.cumsum(sizes, out=offs[1:])
     parts = [s for s in streams if s is not None]
     return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), offs
-
-
-def encode_items(ctx, items, coder, src_offset=0, dst_offset=0, invert=False):
-    """Through the device call with every buffer guarded -> (payload, comp_offsets): the source is not written, the
-    destination only in [0, comp_offsets[nitems]), the table only in its nitems + 1 entries."""
-    lengths = [len(x) for x in items]
-    soffs = rcx.item_offsets(lengths)
-    data = np.concatenate(items) if items else np.zeros(0, np.uint8)
-    src = Guarded(len(data), src_offset, data, salt=1, invert=invert)
-    dst = Guarded(rcx.encode_items_bound(soffs, coder), dst_offset, salt=2, invert=invert)
-    offs = Guarded(8 * len(soffs), 0, salt=3, invert=invert)
-    ctx.encode_items_device(src.view, soffs, dst.view, offs.view.view(torch.int64), coder=coder)
-    ctx.sync_status()
-    table = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
-    src.check(0, "encode src")
-    offs.check(8 * len(soffs), "encode table")
-    dst.check(int(table[-1]), "encode dst")
-    return dst.view[: int(table[-1])].cpu().numpy(), table
-
-
-def decode_items(ctx, payload, comp_offsets, lengths, coder, pick=None, comp_offset=0, dst_offset=0, invert=False):
-    """Through the device call, guarded -> (list of the picked items' bytes, status, first bad index).  `lengths` are the
-    decoded lengths of the picks."""
-    payload = np.ascontiguousarray(payload, dtype=np.uint8)
-    comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
-    table = np.ascontiguousarray(np.asarray(comp_offsets).astype(np.int64))
-    offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
-    doffs = rcx.item_offsets(lengths)
-    n = int(doffs[-1])
-    out = Guarded(n, dst_offset, salt=6, invert=invert)
-    ctx.decode_items_device(comp.view, len(payload), offs.view.view(torch.int64), doffs, out.view, pick=pick, coder=coder)
-    st, bad = ctx.sync_status(raise_on_error=False)
-    comp.check(0, "decode comp")
-    offs.check(0, "decode table")
-    out.check(n, "decode dst")
-    flat = out.view.cpu().numpy()
-    return [flat[int(doffs[k]): int(doffs[k + 1])] for k in range(len(lengths))], st, bad
 
 
 def ragged_lengths(seed, count=2200):
@@ -142,16 +74,7 @@ def test_ragged_parity(ctx, oracle, coder):
     the oracle's, and the round trip returns the items."""
     items, want = ragged_batch(oracle, coder)
     assert len(items) >= 2000 and sum(1 for x in items if len(x) == 0) >= 40
-    payload, offs = encode_items(ctx, items, coder, src_offset=3, dst_offset=5)
-    want_payload, want_offs = compact(want)
-    assert np.array_equal(offs, want_offs), "comp_offsets differ from the oracle's sizes"
-    for i, s in enumerate(want):
-        got = payload[int(offs[i]): int(offs[i + 1])]
-        assert len(got) == (0 if s is None else len(s)) and (s is None or np.array_equal(got, s)), f"item {i} ({len(items[i])} bytes) differs"
-    back, st, _ = decode_items(ctx, payload, offs, [len(x) for x in items], coder, comp_offset=1, dst_offset=7)
-    assert st == rcx.OK
-    for i, x in enumerate(items):
-        assert np.array_equal(back[i], x), f"item {i} does not round-trip"
+    check_items(ctx, items, want, coder, src_offset=3, dst_offset=5, comp_offset=1, out_offset=7)
     if coder in LOW:  # (the range coders' kernels keep the marks; nothing is marked on valid data)
         assert ctx.last_redo(sum(1 for x in items if len(x))) == 0
 
@@ -208,14 +131,6 @@ def test_bounds_at_every_alignment(ctx, oracle, coder):
     dst.check(cap, "encode dst beyond dst_cap")
 
 
-def decode_one(oracle, stream, length, coder):
-    """The oracle on one item's stream alone -> (ok, bytes)."""
-    slots = np.zeros((1, len(stream) + 64), np.uint8)
-    slots[0, : len(stream)] = stream
-    out, ok = oracle.decode_blocks(slots, np.array([len(stream)], np.uint32), max(length, 1), length, coder=coder)
-    return ok, out
-
-
 @pytest.mark.parametrize("coder", CODERS)
 def test_damaged_items(oracle, coder):
     """One item in the middle of a wave is damaged -- a payload byte, a target past the table (the range coders: the
@@ -252,7 +167,7 @@ def test_damaged_items(oracle, coder):
             if kind == "header":
                 ok, ref = False, None  # a header that disagrees with dst_offsets is corrupt, whatever the reference makes of it
             else:
-                ok, ref = decode_one(oracle, s, len(items[victim]), coder)
+                ok, ref = oracle_decode_one(oracle, s, len(items[victim]), coder, max(len(items[victim]), 1))
             got, st, bad = decode_items(c, payload, offs, lengths[pick], coder, pick=pick, dst_offset=int(rs.randint(0, 16)))
             if ok:
                 assert st == rcx.OK, (kind, st, bad)
@@ -382,9 +297,7 @@ def test_containers(ctx, oracle):
         blob = container.pack_items(items, coder, ctx)
         c = container.parse_items(blob)
         want = oracle_streams(oracle, [np.frombuffer(x, np.uint8) for x in items], coder)
-        for i, s in enumerate(want):
-            got = c["payload"][int(c["offsets"][i]): int(c["offsets"][i + 1])]
-            assert len(got) == (0 if s is None else len(s)) and (s is None or np.array_equal(got, s))
+        assert_same_items(c["payload"], c["offsets"], want, coder)
         assert container.unpack_items(blob, ctx=ctx) == items
         assert container.unpack_items(blob, pick=[6, 2, 2, 0, 3], ctx=ctx) == [items[6], items[2], items[2], items[0], items[3]]
         assert container.unpack_items(blob, pick=[], ctx=ctx) == []

@@ -4,114 +4,22 @@ Bit-exact bar: every block's stream must equal what the reference emits for that
 (cpprcoder.h:678-802), and decode(encode(x)) == x (the reference harness's own check,
 test/main.cpp:357-361).  Nothing here reads /root/reference.
 """
-import hashlib
-
 import numpy as np
 import pytest
 
-import oracle_lib
+import golden_cases
 from cpprcoder_amd import workloads
+from gpu_support import assert_same_blocks, check_blocks, check_golden_blocks, context, ctx, gpu_decode, gpu_encode  # noqa: F401
+from oracle_lib import sha
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from cpprcoder_amd import rcx
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    c = rcx.Context(0)
-    yield c
-    c.close()
-
-
-GUARD = 256  # bytes of guard pattern on each side of every buffer a device call is handed
-
-
-class Guarded:
-    """A buffer handed to a kernel, as a view into a larger cuda tensor: GUARD bytes, `offset` more, the buffer, GUARD
-    bytes.  Everything that is not buffer content holds a position-dependent pattern (nonzero; its complement with
-    `invert`), and a copy of the whole tensor is kept, so that a check after the call sees any byte written outside
-    the range the call may write, and any byte of an input that the call changed."""
-
-    def __init__(self, size, offset=0, content=None, salt=0, invert=False):
-        self.at = GUARD + offset
-        self.size = size
-        i = np.arange(self.at + size + GUARD, dtype=np.int64)
-        image = ((i * 37 + salt * 101 + 11) % 251 + 1).astype(np.uint8)
-        if invert:
-            image = ~image
-        if content is not None:
-            image[self.at: self.at + len(content)] = np.frombuffer(np.ascontiguousarray(content).tobytes(), np.uint8)
-        self.tensor = torch.from_numpy(image).cuda()
-        self.before = self.tensor.clone()
-        self.view = self.tensor[self.at: self.at + size]
-
-    def check(self, written=0, what="buffer"):
-        """Nothing changed but the first `written` bytes of the buffer."""
-        hi = self.at + written
-        for lo_, hi_ in ((0, self.at), (hi, self.tensor.numel())):
-            if not torch.equal(self.tensor[lo_:hi_], self.before[lo_:hi_]):
-                first = lo_ + int(torch.nonzero(self.tensor[lo_:hi_] != self.before[lo_:hi_])[0, 0])
-                raise AssertionError(f"{what}: byte {first - self.at} changed, outside the {written} bytes from 0 it may write")
-
-
-def gpu_encode(ctx, data, block, src_offset=0, coder=0, dst_offset=0, invert=False):
-    """-> (payload np.uint8, offsets np.uint64) through the device-pointer entry points.  Every buffer is guarded
-    (Guarded): the source is not written, and nothing is written past offsets[nblocks] of dst or around the table."""
-    from cpprcoder_amd import rcx
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n = len(data)
-    nblocks = rcx.block_count(n, block)
-    src = Guarded(n, src_offset, data, salt=1, invert=invert)
-    dst = Guarded(rcx.encode_bound(n, block, coder), dst_offset, salt=2, invert=invert)
-    offs = Guarded(8 * (nblocks + 1), 0, salt=3, invert=invert)
-    ctx.encode_blocks_device(src.view, block, dst.view, offs.view.view(torch.int64), coder=coder)
-    ctx.sync_status()
-    offsets = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
-    src.check(0, "encode src")
-    offs.check(8 * (nblocks + 1), "encode offsets")
-    dst.check(int(offsets[-1]), "encode dst")
-    return dst.view[: int(offsets[-1])].cpu().numpy(), offsets, (dst.view, offs.view.view(torch.int64))
-
-
-def gpu_decode(ctx, payload, offsets, n, block, dst_offset=0, comp_offset=0, coder=0, invert=False):
-    """Decode through the device-pointer entry point -> (out np.uint8, status, first bad block).  The compressed bytes
-    and the table are guarded inputs (not written; what lies behind comp_size is the guard pattern, not zeros), and
-    nothing is written outside the n output bytes."""
-    payload = np.ascontiguousarray(payload, dtype=np.uint8)
-    comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
-    table = np.ascontiguousarray(np.asarray(offsets).astype(np.int64))
-    offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
-    out = Guarded(n, dst_offset, salt=6, invert=invert)
-    ctx.decode_blocks_device(comp.view, len(payload), offs.view.view(torch.int64), n, block, out.view, coder=coder)
-    st, bad = ctx.sync_status(raise_on_error=False)
-    comp.check(0, "decode comp")
-    offs.check(0, "decode offsets")
-    out.check(n, "decode dst")
-    return out.view.cpu().numpy(), st, bad
-
-
-def assert_same_blocks(payload, offsets, slots, sizes):
-    assert np.array_equal(np.diff(offsets.astype(np.int64)), sizes.astype(np.int64)), "per-block sizes differ"
-    for b in range(len(sizes)):
-        got = payload[int(offsets[b]): int(offsets[b + 1])]
-        assert np.array_equal(got, slots[b, : int(sizes[b])]), f"block {b} differs"
-
-
 def test_golden_block_tables(ctx, golden):
     for t in golden["blocks"]:
-        coder = 0 if t["coder"] == "adaptive" else 1
-        data = workloads.by_name(t["workload"], t["n"], t["seed"])
-        assert hashlib.sha256(data.tobytes()).hexdigest() == t["input_sha256"]
-        payload, offsets, _ = gpu_encode(ctx, data, t["block"], coder=coder)
-        assert [int(x) for x in np.diff(offsets.astype(np.int64))] == t["sizes"], (t["workload"], t["block"])
-        fnv = ["%016x" % oracle_lib.fnv1a64(payload[int(offsets[b]): int(offsets[b + 1])]) for b in range(len(t["sizes"]))]
-        assert fnv == t["fnv1a64"], (t["workload"], t["block"])
-        assert int(offsets[-1]) == t["total"]
-        back, st, _ = gpu_decode(ctx, payload, offsets, t["n"], t["block"], coder=coder)
-        assert st == 0 and np.array_equal(back, data)
+        check_golden_blocks(ctx, t, 0 if t["coder"] == "adaptive" else 1)
 
 
 @pytest.mark.parametrize("block", [16, 48, 100, 1000, 4096, 16384, 65536, 65552, 262144, 1 << 20])
@@ -122,12 +30,8 @@ def test_ragged_sizes_match_oracle(ctx, oracle, block):
         n = block * (nblocks - 1) + int(rs.randint(1, block + 1))  # last block ragged, may be 1 byte
         wl = ("uniform", "zipf", "runs", "canterbury")[trial % 4] if trial else "uniform"
         data = workloads.by_name(wl, n, 1000 + trial)
-        slots, sizes = oracle.encode_blocks(data, block, threads=8)
         off = (0, 1, 5)[trial]  # the source need not be 16-byte aligned
-        payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=off)
-        assert_same_blocks(payload, offsets, slots, sizes)
-        back, st, _ = gpu_decode(ctx, payload, offsets, n, block, dst_offset=off, comp_offset=(0, 3, 2)[trial])
-        assert st == 0 and np.array_equal(back, data)
+        check_blocks(ctx, oracle, data, block, src_offset=off, dst_offset=off, comp_offset=(0, 3, 2)[trial], label=(block, wl, n))
 
 
 def test_edge_inputs(ctx, oracle):
@@ -139,11 +43,7 @@ def test_edge_inputs(ctx, oracle):
         (np.frombuffer(files["alice29.txt"], np.uint8), 1 << 20),  # BASELINE config 1: alice29 as ONE block
     ]
     for data, block in cases:
-        slots, sizes = oracle.encode_blocks(data, block, threads=8)
-        payload, offsets, _ = gpu_encode(ctx, data, block)
-        assert_same_blocks(payload, offsets, slots, sizes)
-        back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block)
-        assert st == 0 and np.array_equal(back, data)
+        check_blocks(ctx, oracle, data, block, label=(len(data), block))
     # alice29 single block: the README's pinned size (README.md:36, 0.573000 * 152089)
     data = np.frombuffer(files["alice29.txt"], np.uint8)
     payload, offsets, _ = gpu_encode(ctx, data, 1 << 20)
@@ -353,11 +253,7 @@ def test_bursts_of_very_improbable_symbols(ctx, oracle):
         d[5000:5000 + 255] = rs.permutation(others)  # and once early, at 13 bits per symbol
         return d
     data = np.concatenate([one(65, 1), one(0, 2), one(255, 3), workloads.zipf(block, 4)])
-    payload, offsets, _ = gpu_encode(ctx, data, block)
-    slots, sizes = oracle.encode_blocks(data, block, threads=4)
-    assert_same_blocks(payload, offsets, slots, sizes)
-    back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block)
-    assert st == 0 and np.array_equal(back, data)
+    check_blocks(ctx, oracle, data, block, threads=4)
     assert ctx.last_redo(4) == 0
 
 
@@ -377,7 +273,7 @@ def test_single_stream_semantics(ctx, oracle, golden):
     st, rq, out = ctx.stream_encode(u64k, sink_capacity=65536)  # {Pending, 112}
     pin = golden["kat"]["pins"]["overflow_uniform64k_into_65536"]
     assert [st, rq] == pin["status"] == [1, 112] and len(out) == pin["size"]
-    assert hashlib.sha256(out).hexdigest() == pin["prefix_sha256"]
+    assert sha(out) == pin["prefix_sha256"]
     rs = np.random.RandomState(77)
     for _ in range(25):
         n = int(rs.randint(1, 4000))
@@ -396,10 +292,10 @@ def test_single_stream_semantics(ctx, oracle, golden):
     comp = oracle.adaptive_encode(u64k[:3000])[1]
     st, rq, out = ctx.stream_decode(comp[:1500], 3000)
     assert [st, rq] == pins["decode_truncated"]["status"] and len(out) == pins["decode_truncated"]["size"]
-    assert hashlib.sha256(out).hexdigest() == pins["decode_truncated"]["out_sha256"]
+    assert sha(out) == pins["decode_truncated"]["out_sha256"]
     st, rq, out = ctx.stream_decode(comp, r16(1000))
     assert [st, rq] == pins["decode_sink_full"]["status"] and len(out) == pins["decode_sink_full"]["size"]
-    assert hashlib.sha256(out[:1000]).hexdigest() == pins["decode_sink_full"]["out_sha256"]  # the fixture hashed the first 1000 bytes
+    assert sha(out[:1000]) == pins["decode_sink_full"]["out_sha256"]  # the fixture hashed the first 1000 bytes
 
 
 FULL_SIZE_RATIOS = {  # SURVEY.md section 8(d) / the reference build on these very bytes (profiles/r02_coder_soak.txt)
@@ -460,12 +356,8 @@ def test_static_ragged_sizes_match_oracle(ctx, oracle, block):
         n = block * (nblocks - 1) + int(rs.randint(1, block + 1))
         wl = ("uniform", "zipf", "runs", "canterbury")[trial % 4] if trial else "canterbury"
         data = workloads.by_name(wl, n, 2000 + trial)
-        slots, sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
         off = (0, 1, 5)[trial]
-        payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=off, coder=1)
-        assert_same_blocks(payload, offsets, slots, sizes)
-        back, st, _ = gpu_decode(ctx, payload, offsets, n, block, dst_offset=off, comp_offset=(0, 3, 2)[trial], coder=1)
-        assert st == 0 and np.array_equal(back, data)
+        check_blocks(ctx, oracle, data, block, coder=1, src_offset=off, dst_offset=off, comp_offset=(0, 3, 2)[trial], label=(block, wl, n))
 
 
 def test_static_edge_inputs(ctx, oracle, golden):
@@ -479,17 +371,13 @@ def test_static_edge_inputs(ctx, oracle, golden):
         (np.frombuffer(files["alice29.txt"], np.uint8), 1 << 20),
     ]
     for data, block in cases:
-        slots, sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
-        payload, offsets, _ = gpu_encode(ctx, data, block, coder=1)
-        assert_same_blocks(payload, offsets, slots, sizes)
-        back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block, coder=1)
-        assert st == 0 and np.array_equal(back, data)
+        check_blocks(ctx, oracle, data, block, coder=1, label=(len(data), block))
     # README.md:20-30: the published static sizes, each file as one block
     for name in workloads.CANTERBURY_ORDER:
         data = np.frombuffer(files[name], np.uint8)
         payload, offsets, _ = gpu_encode(ctx, data, 1 << 20, coder=1)
         assert len(payload) == golden["kat"]["canterbury"][name]["static_size"]
-        assert hashlib.sha256(payload.tobytes()).hexdigest() == golden["kat"]["canterbury"][name]["static_sha256"]
+        assert sha(payload) == golden["kat"]["canterbury"][name]["static_sha256"]
 
 
 def test_static_corrupt_streams(ctx, oracle):
@@ -533,56 +421,41 @@ def test_superseded_kernels_in_the_diagnostic_build():
 def test_every_kernel_variant_is_bit_identical(oracle):
     """The selectable encode kernels of the product (one wave per 64 blocks / the five-wave split) and decode kernels
     (1 or 4 lanes per block) and their launch shapes must all produce the oracle's bytes."""
-    import os
-    from cpprcoder_amd import rcx
     data = workloads.canterbury_tiled(65536 * 37 + 4321)
-    saved = {k: os.environ.get(k) for k in ("RCX_ENC_VARIANT", "RCX_LANES_PER_BLOCK", "RCX_ENC_LANES", "RCX_DEC_QUADS")}
-    try:
-        for block in (4096, 65536):
-            slots, sizes = oracle.encode_blocks(data, block, threads=8)
-            ref_payload, ref_offsets = oracle.compact(slots, sizes)
-            for enc in ("0", "3"):
-                for dec in ("1", "4"):
-                    os.environ["RCX_ENC_VARIANT"], os.environ["RCX_LANES_PER_BLOCK"] = enc, dec
-                    c = rcx.Context(0)
-                    payload, offsets, _ = gpu_encode(c, data, block)
-                    assert np.array_equal(payload, ref_payload) and np.array_equal(offsets, ref_offsets), (block, enc)
-                    back, st, _ = gpu_decode(c, payload, offsets, len(data), block)
-                    assert st == 0 and np.array_equal(back, data), (block, dec)
-                    c.close()
-            # launch shapes (rcx_api.hip: encode_lanes / decode_quads): fewer blocks per workgroup / per wave
-            for lanes, quads in (("1", "1"), ("8", "4"), ("32", "8"), ("5", "2")):
-                os.environ["RCX_ENC_VARIANT"], os.environ["RCX_LANES_PER_BLOCK"] = "3", "4"
-                os.environ["RCX_ENC_LANES"], os.environ["RCX_DEC_QUADS"] = lanes, quads
-                c = rcx.Context(0)
-                for coder, want_p, want_o in ((0, ref_payload, ref_offsets), (1, None, None)):
-                    if coder == 1:
-                        s_slots, s_sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
-                        want_p, want_o = oracle.compact(s_slots, s_sizes)
-                    payload, offsets, _ = gpu_encode(c, data, block, coder=coder)
-                    assert np.array_equal(payload, want_p) and np.array_equal(offsets, want_o), (block, lanes, coder)
-                    back, st, _ = gpu_decode(c, payload, offsets, len(data), block, coder=coder)
-                    assert st == 0 and np.array_equal(back, data), (block, quads, coder)
+    for block in (4096, 65536):
+        slots, sizes = oracle.encode_blocks(data, block, threads=8)
+        ref_payload, ref_offsets = oracle.compact(slots, sizes)
+        for enc in ("0", "3"):
+            for dec in ("1", "4"):
+                c = context({"RCX_ENC_VARIANT": enc, "RCX_LANES_PER_BLOCK": dec})
+                payload, offsets, _ = gpu_encode(c, data, block)
+                assert np.array_equal(payload, ref_payload) and np.array_equal(offsets, ref_offsets), (block, enc)
+                back, st, _ = gpu_decode(c, payload, offsets, len(data), block)
+                assert st == 0 and np.array_equal(back, data), (block, dec)
                 c.close()
-                os.environ.pop("RCX_ENC_LANES"), os.environ.pop("RCX_DEC_QUADS")
-            # static coder: one-wave / three-wave encoder x one-lane / four-lane decoder
-            s_slots, s_sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
-            s_payload, s_offsets = oracle.compact(s_slots, s_sizes)
-            for enc in ("0", "3"):
-                for dec in ("1", "4"):
-                    os.environ["RCX_ENC_VARIANT"], os.environ["RCX_LANES_PER_BLOCK"] = enc, dec
-                    c = rcx.Context(0)
-                    payload, offsets, _ = gpu_encode(c, data, block, coder=1)
-                    assert np.array_equal(payload, s_payload) and np.array_equal(offsets, s_offsets), ("static", block, enc)
-                    back, st, _ = gpu_decode(c, payload, offsets, len(data), block, coder=1)
-                    assert st == 0 and np.array_equal(back, data), ("static", block, dec)
-                    c.close()
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+        # launch shapes (rcx_api.hip: encode_lanes / decode_quads): fewer blocks per workgroup / per wave
+        for lanes, quads in (("1", "1"), ("8", "4"), ("32", "8"), ("5", "2")):
+            c = context({"RCX_ENC_VARIANT": "3", "RCX_LANES_PER_BLOCK": "4", "RCX_ENC_LANES": lanes, "RCX_DEC_QUADS": quads})
+            for coder, want_p, want_o in ((0, ref_payload, ref_offsets), (1, None, None)):
+                if coder == 1:
+                    s_slots, s_sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
+                    want_p, want_o = oracle.compact(s_slots, s_sizes)
+                payload, offsets, _ = gpu_encode(c, data, block, coder=coder)
+                assert np.array_equal(payload, want_p) and np.array_equal(offsets, want_o), (block, lanes, coder)
+                back, st, _ = gpu_decode(c, payload, offsets, len(data), block, coder=coder)
+                assert st == 0 and np.array_equal(back, data), (block, quads, coder)
+            c.close()
+        # static coder: one-wave / three-wave encoder x one-lane / four-lane decoder
+        s_slots, s_sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
+        s_payload, s_offsets = oracle.compact(s_slots, s_sizes)
+        for enc in ("0", "3"):
+            for dec in ("1", "4"):
+                c = context({"RCX_ENC_VARIANT": enc, "RCX_LANES_PER_BLOCK": dec})
+                payload, offsets, _ = gpu_encode(c, data, block, coder=1)
+                assert np.array_equal(payload, s_payload) and np.array_equal(offsets, s_offsets), ("static", block, enc)
+                back, st, _ = gpu_decode(c, payload, offsets, len(data), block, coder=1)
+                assert st == 0 and np.array_equal(back, data), ("static", block, dec)
+                c.close()
 
 
 def test_streams_and_graph_replay(ctx, oracle):
@@ -633,11 +506,8 @@ def test_many_small_random_buffers(ctx, oracle):
         alpha = int(rs.choice([1, 2, 3, 16, 200, 256]))
         data = rs.randint(0, alpha, size=n).astype(np.uint8)
         coder = int(rs.randint(4))  # adaptive, static, rANS one state, rANS eight states
-        slots, sizes = oracle.encode_blocks(data, block, coder=coder, threads=4)
-        payload, offsets, _ = gpu_encode(ctx, data, block, coder=coder, src_offset=int(rs.randint(4)))
-        assert_same_blocks(payload, offsets, slots, sizes)
-        back, st, _ = gpu_decode(ctx, payload, offsets, n, block, coder=coder, comp_offset=int(rs.randint(16)))
-        assert st == 0 and np.array_equal(back, data), (block, n, alpha, coder)
+        check_blocks(ctx, oracle, data, block, coder=coder, src_offset=int(rs.randint(4)), comp_offset=int(rs.randint(16)), threads=4,
+                     label=(block, n, alpha, coder))
 
 
 # ---------------------------------------------------------------------------
@@ -646,15 +516,7 @@ def test_many_small_random_buffers(ctx, oracle):
 # ---------------------------------------------------------------------------
 def test_blocks_past_one_mebibyte(ctx, golden):
     for t in golden["long"]["blocks"]:
-        coder = 0 if t["coder"] == "adaptive" else 1
-        data = workloads.by_name(t["workload"], t["n"], t["seed"])
-        assert hashlib.sha256(data.tobytes()).hexdigest() == t["input_sha256"]
-        payload, offsets, _ = gpu_encode(ctx, data, t["block"], coder=coder)
-        assert [int(x) for x in np.diff(offsets.astype(np.int64))] == t["sizes"], (t["workload"], t["block"], t["coder"])
-        fnv = ["%016x" % oracle_lib.fnv1a64(payload[int(offsets[b]): int(offsets[b + 1])]) for b in range(len(t["sizes"]))]
-        assert fnv == t["fnv1a64"], (t["workload"], t["block"], t["coder"])
-        back, st, _ = gpu_decode(ctx, payload, offsets, t["n"], t["block"], coder=coder)
-        assert st == 0 and np.array_equal(back, data)
+        check_golden_blocks(ctx, t, 0 if t["coder"] == "adaptive" else 1)
 
 
 def test_block_of_the_largest_size(ctx, golden):
@@ -663,9 +525,9 @@ def test_block_of_the_largest_size(ctx, golden):
     from cpprcoder_amd import rcx
     g = golden["long"]["adaptive"]["zipf(NO_HALVING,4)"]
     data = workloads.zipf(rcx.MAX_BLOCK, 4)
-    assert hashlib.sha256(data.tobytes()).hexdigest() == g["input_sha256"]
+    assert sha(data) == g["input_sha256"]
     payload, offsets, _ = gpu_encode(ctx, data, rcx.MAX_BLOCK)
-    assert len(payload) == g["size"] and hashlib.sha256(payload.tobytes()).hexdigest() == g["sha256"]
+    assert len(payload) == g["size"] and sha(payload) == g["sha256"]
     back, st, _ = gpu_decode(ctx, payload, offsets, len(data), rcx.MAX_BLOCK)
     assert st == 0 and np.array_equal(back, data)
 
@@ -674,19 +536,18 @@ def test_long_single_streams(ctx, golden):
     """rcx_stream_encode / rcx_stream_decode on streams of 2 MiB ... 2^24 + 70000 symbols: the reference's bytes
     (cpprcoder.h:697-720 has no size cap), including the halve-and-resum step (cpprcoder.h:1138-1176) and, for the
     static coder, count()'s second rescale (cpprcoder.h:561-570)."""
-    import test_oracle_golden
-    adaptive, static = test_oracle_golden.long_inputs()
+    adaptive, static = golden_cases.LONG_ADAPTIVE, golden_cases.LONG_STATIC
     for label, g in golden["long"]["adaptive"].items():
         v = adaptive[label]()
         st, rq, comp = ctx.stream_encode(v)
         assert (st, rq, len(comp)) == (0, 0, g["size"]), label
-        assert hashlib.sha256(comp).hexdigest() == g["sha256"], label
+        assert sha(comp) == g["sha256"], label
         st, rq, back = ctx.stream_decode(comp, len(v))
         assert (st, rq) == (0, 0) and back == v.tobytes(), label
     for label, g in golden["long"]["static"].items():
         v = static[label]()
         st, rq, comp = ctx.stream_encode(v, coder=1)
-        assert st == 0 and len(comp) == g["size"] and hashlib.sha256(comp).hexdigest() == g["sha256"], label
+        assert st == 0 and len(comp) == g["size"] and sha(comp) == g["sha256"], label
         st, rq, back = ctx.stream_decode(comp, len(v), coder=1)
         assert st == 0 and back == v.tobytes(), label
     # a long stream into a sink that fills: {Pending, remaining} as cpprcoder.h:708-711
@@ -725,11 +586,7 @@ def test_static_histogram_past_65535_symbols(ctx, oracle):
     squeeze = np.concatenate([workloads.runs(block * 3, 5), np.full(block, 7, np.uint8),
                               np.concatenate([np.full(70000, 1, np.uint8), workloads.zipf(block - 70000 - 65000, 3), np.full(65000, 1, np.uint8)])])
     for data in (calm, text, squeeze):
-        slots, sizes = oracle.encode_blocks(data, block, coder=1, threads=8)
-        payload, offsets, _ = gpu_encode(ctx, data, block, coder=1)
-        assert_same_blocks(payload, offsets, slots, sizes)
-        back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block, coder=1)
-        assert st == 0 and np.array_equal(back, data)
+        check_blocks(ctx, oracle, data, block, coder=1)
 
 
 def test_resumable_decoder_fed_in_pieces(ctx, oracle, golden):

@@ -2,39 +2,29 @@
 stream must equal what the reference's rANS::encode / encode_simd return for that block (fixtures made from the
 reference build: tests/golden/rans.json; the oracle restates cppans.h and is itself pinned to that build), and
 decode(encode(x)) == x (test/main.cpp:387-393)."""
-import hashlib
-
 import numpy as np
 import pytest
 
-import oracle_lib
+import golden_cases
 from cpprcoder_amd import workloads
-from test_gpu_parity import assert_same_blocks, gpu_decode, gpu_encode
+from gpu_support import check_blocks, check_golden_blocks, ctx, gpu_decode, gpu_encode  # noqa: F401
+from oracle_lib import sha
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-CODERS = ((2, "rans"), (3, "rans8"))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from cpprcoder_amd import rcx
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    c = rcx.Context(0)
-    yield c
-    c.close()
+RANS = ((2, "rans"), (3, "rans8"))
 
 
 def test_rans_kats_through_the_stream_calls(ctx, golden):
     for k in golden["rans"]["kat"]:
         v = bytes.fromhex(k["input_hex"])
-        for coder, key in CODERS:
+        for coder, key in RANS:
             st, rq, comp = ctx.stream_encode(v, coder=coder)
             assert st == 0 and comp.hex() == k[key + "_hex"], (v, key)
             st, rq, back = ctx.stream_decode(comp, max(len(v), 16), coder=coder)
             assert st == 0 and back == v
     from cpprcoder_amd import rcx
-    for coder, _ in CODERS:
+    for coder, _ in RANS:
         assert ctx.stream_encode(b"", coder=coder)[0] == rcx.ERROR            # cppans.h:501: 0 < src_size
         st, _, comp = ctx.stream_encode(b"abc" * 100, coder=coder)
         assert ctx.stream_decode(comp, 299, coder=coder)[0] == rcx.ERROR      # cppans.h:541 / :618: destination too small
@@ -42,34 +32,24 @@ def test_rans_kats_through_the_stream_calls(ctx, golden):
 
 
 def test_rans_generated_and_canterbury_files(ctx, golden):
-    import test_oracle_rans
-    gens = test_oracle_rans.generated()
     for name, g in golden["rans"]["generated"].items():
-        v = gens[name]()
-        for coder, key in CODERS:
+        v = golden_cases.RANS_GENERATED[name]()
+        for coder, key in RANS:
             st, _, comp = ctx.stream_encode(v, coder=coder)
-            assert st == 0 and (len(comp), hashlib.sha256(comp).hexdigest()) == (g[key + "_size"], g[key + "_sha256"]), (name, key)
+            assert st == 0 and (len(comp), sha(comp)) == (g[key + "_size"], g[key + "_sha256"]), (name, key)
             st, _, back = ctx.stream_decode(comp, len(v), coder=coder)
             assert st == 0 and back == v.tobytes()
     files = workloads.canterbury_files()
     for name, g in golden["rans"]["canterbury"].items():
         v = np.frombuffer(files[name], np.uint8)
-        for coder, key in CODERS:
+        for coder, key in RANS:
             st, _, comp = ctx.stream_encode(v, coder=coder)
-            assert st == 0 and (len(comp), hashlib.sha256(comp).hexdigest()) == (g[key + "_size"], g[key + "_sha256"]), (name, key)
+            assert st == 0 and (len(comp), sha(comp)) == (g[key + "_size"], g[key + "_sha256"]), (name, key)
 
 
 def test_rans_golden_block_tables(ctx, golden):
     for t in golden["rans"]["blocks"]:
-        coder = 2 if t["coder"] == "rans" else 3
-        data = workloads.by_name(t["workload"], t["n"], t["seed"])
-        assert hashlib.sha256(data.tobytes()).hexdigest() == t["input_sha256"]
-        payload, offsets, _ = gpu_encode(ctx, data, t["block"], coder=coder)
-        assert [int(x) for x in np.diff(offsets.astype(np.int64))] == t["sizes"], (t["workload"], t["block"], t["coder"])
-        fnv = ["%016x" % oracle_lib.fnv1a64(payload[int(offsets[b]): int(offsets[b + 1])]) for b in range(len(t["sizes"]))]
-        assert fnv == t["fnv1a64"], (t["workload"], t["block"], t["coder"])
-        back, st, _ = gpu_decode(ctx, payload, offsets, t["n"], t["block"], coder=coder)
-        assert st == 0 and np.array_equal(back, data)
+        check_golden_blocks(ctx, t, 2 if t["coder"] == "rans" else 3)
 
 
 @pytest.mark.parametrize("block", [16, 24, 100, 1000, 4096, 65536, 65552, 262144])
@@ -81,12 +61,8 @@ def test_rans_ragged_sizes_match_oracle(ctx, oracle, block):
         wl = ("uniform", "zipf", "runs", "canterbury")[trial % 4] if trial else "canterbury"
         data = workloads.by_name(wl, n, 3000 + trial)
         off = (0, 1, 5)[trial]  # the source need not be aligned
-        for coder, _ in CODERS:
-            slots, sizes = oracle.encode_blocks(data, block, coder=coder, threads=8)
-            payload, offsets, _ = gpu_encode(ctx, data, block, src_offset=off, coder=coder)
-            assert_same_blocks(payload, offsets, slots, sizes)
-            back, st, _ = gpu_decode(ctx, payload, offsets, n, block, dst_offset=off, comp_offset=(0, 3, 2)[trial], coder=coder)
-            assert st == 0 and np.array_equal(back, data)
+        for coder, _ in RANS:
+            check_blocks(ctx, oracle, data, block, coder=coder, src_offset=off, dst_offset=off, comp_offset=(0, 3, 2)[trial], label=(block, wl, n, coder))
 
 
 def test_rans_edge_inputs(ctx, oracle):
@@ -101,18 +77,14 @@ def test_rans_edge_inputs(ctx, oracle):
         (np.frombuffer(workloads.canterbury_files()["ptt5"], np.uint8), 65536),
     ]
     for data, block in cases:
-        for coder, _ in CODERS:
-            slots, sizes = oracle.encode_blocks(data, block, coder=coder, threads=8)
-            payload, offsets, _ = gpu_encode(ctx, data, block, coder=coder)
-            assert_same_blocks(payload, offsets, slots, sizes)
-            back, st, _ = gpu_decode(ctx, payload, offsets, len(data), block, coder=coder)
-            assert st == 0 and np.array_equal(back, data)
+        for coder, _ in RANS:
+            check_blocks(ctx, oracle, data, block, coder=coder, label=(len(data), block, coder))
 
 
 def test_rans_damaged_streams_are_reported(ctx, oracle):
     from cpprcoder_amd import rcx
     data = workloads.zipf(65536 * 3 + 500, 8)
-    for coder, _ in CODERS:
+    for coder, _ in RANS:
         payload, offsets, _ = gpu_encode(ctx, data, 65536, coder=coder)
         cut = offsets.copy()
         cut[-1] -= 30  # the last block loses its tail
@@ -143,7 +115,7 @@ def test_rans_full_size_round_trip(ctx, oracle):
     nblocks = n // block
     data = workloads.zipf(n, 12345)
     src = torch.from_numpy(data).cuda()
-    for coder, _ in CODERS:
+    for coder, _ in RANS:
         dst = torch.empty(rcx.encode_bound(n, block, coder), dtype=torch.uint8, device="cuda")
         offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
         ctx.encode_blocks_device(src, block, dst, offs, coder=coder)

@@ -1,7 +1,6 @@
 """The block-sort restatement (oracle/bwt_oracle.c) against what the real reference produced (tests/golden/bwt.json,
 made by tests/golden/make_golden_bwt.py from /root/reference/blksort.h) and, where oracle/_ref travelled, against the
 reference build itself.  CPU only."""
-import hashlib
 import json
 import os
 
@@ -11,12 +10,9 @@ import pytest
 import agreement_cases
 import bwt_cases
 from cpprcoder_amd import workloads
+from oracle_lib import sha
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def sha(b) -> str:
-    return hashlib.sha256(bytes(b)).hexdigest()
 
 
 @pytest.fixture(scope="module")

@@ -4,28 +4,14 @@ and against the real reference build itself when oracle/_ref/ is present.
 Mirrors what the reference's own harness checks (round trip, test/main.cpp:357-361) plus the
 only pinned results the reference publishes (README.md:16-46 ratios).
 """
-import hashlib
-
 import numpy as np
 import pytest
 
 import agreement_cases
+import golden_cases
 import oracle_lib
 from cpprcoder_amd import workloads
-
-
-def sha(b):
-    return hashlib.sha256(bytes(b)).hexdigest()
-
-
-GENERATED = {
-    "A*65535": lambda: b"A" * 65535, "A*65536": lambda: b"A" * 65536, "A*65537": lambda: b"A" * 65537,
-    "ff*70000": lambda: b"\xff" * 70000,
-    "uniform(65536,12345)": lambda: workloads.uniform(65536, 12345).tobytes(),
-    "uniform(100000,7)": lambda: workloads.uniform(100000, 7).tobytes(),
-    "zipf(65536,12345)": lambda: workloads.zipf(65536, 12345).tobytes(),
-    "runs(200000,7)": lambda: workloads.runs(200000, 7).tobytes(),
-}
+from oracle_lib import sha
 
 
 def test_small_kats(oracle, golden):
@@ -61,7 +47,7 @@ def test_survey_vectors(oracle):
 
 def test_generated(oracle, golden):
     for name, g in golden["kat"]["generated"].items():
-        v = GENERATED[name]()
+        v = golden_cases.GENERATED[name]()
         assert len(v) == g["n"] and sha(v) == g["input_sha256"], name
         st, out, size = oracle.adaptive_encode(v)
         assert (size, sha(out), list(st)) == (g["adaptive_size"], g["adaptive_sha256"], g["adaptive_status"]), name
@@ -174,26 +160,10 @@ def test_damaged_streams_against_reference_build(oracle, reference):
                           agreement_cases.damaged(reference) if live else None)
 
 
-def long_inputs():
-    """The recipes of tests/golden/make_golden_long.py (label -> bytes)."""
-    no_halving = (1 << 24) - 256
-    adaptive = {
-        "uniform(2MiB+77,3)": lambda: workloads.uniform((2 << 20) + 77, 3),
-        "zipf(NO_HALVING,4)": lambda: workloads.zipf(no_halving, 4),
-        "uniform(NO_HALVING+5000,11)": lambda: workloads.uniform(no_halving + 5000, 11),
-        "min(zipf(2^24+70000,5),3)": lambda: np.minimum(workloads.zipf((1 << 24) + 70000, 5), 3).astype(np.uint8),
-    }
-    static = {
-        "zipf(2^24+1000,6)": lambda: workloads.zipf((1 << 24) + 1000, 6),
-        "runs(3MiB,2)": lambda: workloads.runs(3 << 20, 2),
-    }
-    return adaptive, static
-
-
 def test_long_streams_and_big_blocks(oracle, golden):
     # past 1 MiB, up to and through the halving at total = 2^24 (cpprcoder.h:1138-1176) and the static coder's
     # second rescale (cpprcoder.h:561-570): the restatement against the reference's own output
-    adaptive, static = long_inputs()
+    adaptive, static = golden_cases.LONG_ADAPTIVE, golden_cases.LONG_STATIC
     for label, g in golden["long"]["adaptive"].items():
         v = adaptive[label]()
         assert sha(v) == g["input_sha256"]
@@ -217,7 +187,6 @@ def test_long_streams_and_big_blocks(oracle, golden):
 def test_encode_traces_from_the_reference_build(oracle, reference):
     """AdaptiveRangeEncoder<T>::encode in pieces: the sink's size after initialize() and after every call, the last call's
     result and the sink's bytes -- tests/golden/encode_traces.json, made by the real reference (make_golden_traces.py)."""
-    import hashlib
     import json
     import os
 
@@ -228,11 +197,11 @@ def test_encode_traces_from_the_reference_build(oracle, reference):
     seen = 0
     for name, data, piece, cap in trace_cases.cases():
         w = want[name]
-        assert hashlib.sha256(bytes(data)).hexdigest() == w["input_sha256"], name
+        assert sha(data) == w["input_sha256"], name
         for chk in (oracle, reference):
             if chk is None:
                 continue
             (st, rq), sink, sizes = chk.adaptive_encode_trace(data, piece, cap)
-            assert [st, rq] == w["status"] and sizes == w["sink_sizes"] and hashlib.sha256(sink).hexdigest() == w["sink_sha256"], (name, chk.kind)
+            assert [st, rq] == w["status"] and sizes == w["sink_sizes"] and sha(sink) == w["sink_sha256"], (name, chk.kind)
         seen += 1
     assert seen >= 15

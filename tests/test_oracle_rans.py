@@ -1,26 +1,13 @@
 """The CPU restatement of the reference's rANS coders (oracle/rans_oracle.c; cppans.h:497-649) against the golden
 vectors made from the real reference (tests/golden/rans.json), and against the reference build itself when
 oracle/_ref/libcppans_ref.so is present.  The reference publishes no rANS numbers: its compiled output is the pin."""
-import hashlib
-
 import numpy as np
 
 import agreement_cases
+import golden_cases
 import oracle_lib
 from cpprcoder_amd import workloads
-
-
-def sha(b):
-    return hashlib.sha256(bytes(b)).hexdigest()
-
-
-def generated():
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location("make_golden_rans", os.path.join(os.path.dirname(__file__), "golden", "make_golden_rans.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.GENERATED
+from oracle_lib import sha
 
 
 def test_rans_kats(oracle, golden):
@@ -38,9 +25,8 @@ def test_rans_kats(oracle, golden):
 
 
 def test_rans_generated_and_canterbury(oracle, golden):
-    gens = generated()
     for name, g in golden["rans"]["generated"].items():
-        v = gens[name]()
+        v = golden_cases.RANS_GENERATED[name]()
         assert sha(v) == g["input_sha256"]
         for simd, key in ((False, "rans"), (True, "rans8")):
             comp = oracle.rans_encode(v, simd)

@@ -1,0 +1,149 @@
+"""The shared test support (tests/gpu_support.py) held to its contract, on CPU tensors: every "writes nothing outside
+its buffer" claim of the GPU tests rests on Guarded.check failing when it should, their launch shapes on knobs leaving the
+environment as it found it, and their parity claims on the two comparisons."""
+import os
+
+import numpy as np
+import pytest
+
+from gpu_support import GUARD, Guarded, assert_same_blocks, assert_same_items, chunk_blocks, knobs
+
+SIZES, OFFSETS = (0, 1, 33), (0, 15)
+
+
+def guarded(size, offset, invert=False):
+    return Guarded(size, offset, np.arange(size, dtype=np.uint8), salt=2, invert=invert, device="cpu")
+
+
+@pytest.mark.parametrize("invert", [False, True])
+def test_an_untouched_buffer_passes(invert):
+    for size in SIZES:
+        for offset in OFFSETS:
+            g = guarded(size, offset, invert)
+            assert g.view.numel() == size and g.view.tolist() == list(range(size))
+            assert g.tensor.numel() == GUARD + offset + size + GUARD
+            g.check(0)
+            g.check(size)
+            g.view.fill_(0)  # the call wrote all it may
+            g.check(size)
+
+
+def changed(g, position, written):
+    """check(written) after one byte at `position` (relative to the buffer) changed -> the AssertionError's text."""
+    g.tensor[g.at + position] ^= 0x40
+    with pytest.raises(AssertionError) as e:
+        g.check(written, "dst")
+    return str(e.value)
+
+
+@pytest.mark.parametrize("offset", OFFSETS)
+@pytest.mark.parametrize("size", SIZES)
+def test_one_changed_byte_outside_what_may_be_written_fails(size, offset):
+    for written in sorted({0, size // 2, size}):
+        for position in (-1, -(GUARD + offset), written, size + GUARD - 1):
+            msg = changed(guarded(size, offset), position, written)
+            assert msg.startswith(f"dst: byte {position} changed") and f"the {written} bytes" in msg, msg
+    if size:  # an input: none of its bytes may change
+        for position in (0, size - 1):
+            assert f"byte {position} changed" in changed(guarded(size, offset), position, 0)
+
+
+def test_the_lowest_changed_byte_is_named():
+    g = guarded(33, 15)
+    g.tensor[g.at + 40] ^= 1
+    assert "byte 20 changed" in changed(g, 20, 10)
+    g.tensor[g.at - 3] ^= 1
+    with pytest.raises(AssertionError, match="byte -3 changed"):
+        g.check(10)
+
+
+def test_the_pattern_is_nonzero_and_differs_by_salt_and_inversion():
+    images = {}
+    for salt in (1, 2):
+        for invert in (False, True):
+            t = Guarded(1000, 3, salt=salt, invert=invert, device="cpu").tensor.numpy()
+            assert t.min() >= 1, (salt, invert)  # (251 + 1 at the most, so the complement is nonzero too)
+            images[salt, invert] = t
+    assert np.array_equal(images[1, True], ~images[1, False])
+    keys = list(images)
+    for i, a in enumerate(keys):
+        for b in keys[i + 1:]:
+            assert np.count_nonzero(images[a] != images[b]) > 900, (a, b)
+
+
+class Boom(Exception):
+    pass
+
+
+@pytest.mark.parametrize("fail", [False, True])
+def test_knobs_restore_the_environment(monkeypatch, fail):
+    monkeypatch.setenv("RCX_T_SET", "before")
+    monkeypatch.setenv("RCX_T_CLEARED", "kept")
+    monkeypatch.delenv("RCX_T_UNSET", raising=False)
+    monkeypatch.delenv("RCX_T_CLEARED_UNSET", raising=False)
+    whole = dict(os.environ)
+    try:
+        with knobs({"RCX_T_SET": "inside", "RCX_T_UNSET": "1"}, clear=("RCX_T_CLEARED", "RCX_T_CLEARED_UNSET")):
+            assert os.environ["RCX_T_SET"] == "inside" and os.environ["RCX_T_UNSET"] == "1"
+            assert "RCX_T_CLEARED" not in os.environ and "RCX_T_CLEARED_UNSET" not in os.environ
+            if fail:
+                raise Boom
+    except Boom:
+        assert fail
+    assert dict(os.environ) == whole
+    # a variable both cleared and set is set inside, and back to what it was afterwards
+    with knobs({"RCX_T_CLEARED": "2"}, clear=("RCX_T_CLEARED",)):
+        assert os.environ["RCX_T_CLEARED"] == "2"
+    assert dict(os.environ) == whole
+
+
+def test_chunk_blocks_restates_host_chunk_blocks():
+    """csrc/rcx_host.hpp host_chunk_blocks(), by hand: 2048 (encode) or 4096 (decode) blocks, at least 16 MiB worth, doubled
+    until there are at most 2048 chunks, then equal chunks, rounded up to a multiple of 64."""
+    for (block, decode, nblocks), want in {
+        (4096, True, 100): 4096,            # one chunk: the floor of 16 MiB / 4096 itself
+        (4096, False, 100): 4096,           # (the encoder's 2048 is below that floor)
+        (65536, False, 100): 2048,          # the floor is 256 blocks: the defaults stand
+        (65536, True, 100): 4096,
+        (16, True, 1): 1 << 20,             # 16 MiB of 16-byte blocks
+        (4096, True, 9092): 3072,           # 3 chunks of 4096 -> 3031 each -> the next multiple of 64
+        (4096, False, 22785): 3840,         # 6 chunks -> 3798 each -> 3840
+        (65536, False, 4273): 1472,         # 3 chunks of 2048 -> 1425 each -> 1472
+        (65536, True, 16384): 4096,         # 4 equal chunks exactly
+        (1 << 20, True, 1 << 23): 4096,     # 2048 chunks: the most there may be
+        (1 << 20, True, (1 << 23) + 1): 8192,  # one block more: 8192 a chunk, 1025 chunks of 8185 -> 8192
+    }.items():
+        assert chunk_blocks(block, decode, nblocks) == want, (block, decode, nblocks)
+
+
+def four_blocks():
+    sizes = np.array([5, 7, 3, 6], np.uint32)
+    slots = np.arange(4 * 16, dtype=np.uint8).reshape(4, 16) + 1
+    streams = [slots[b, : int(sizes[b])] for b in range(4)]
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    return np.concatenate(streams), offsets, slots, sizes, streams
+
+
+def test_the_comparisons_fail_when_they_should():
+    payload, offsets, slots, sizes, streams = four_blocks()
+    assert_same_blocks(payload, offsets, slots, sizes)
+    assert_same_items(payload, offsets, streams)
+    # an item of length 0 has no stream
+    assert_same_items(payload, np.insert(offsets, 2, offsets[2]), streams[:2] + [None] + streams[2:])
+    # a size mismatch: a byte moves from block 1 to block 2
+    moved = offsets.copy()
+    moved[2] -= 1
+    with pytest.raises(AssertionError, match="sizes differ"):
+        assert_same_blocks(payload, moved, slots, sizes)
+    with pytest.raises(AssertionError, match="sizes"):
+        assert_same_items(payload, moved, streams)
+    with pytest.raises(AssertionError, match="sizes"):
+        assert_same_items(payload, offsets, streams[:2] + [None] + streams[3:])
+    # one byte of a middle block differs
+    for at, b in ((int(offsets[2]), 2), (int(offsets[2]) - 1, 1)):
+        bad = payload.copy()
+        bad[at] ^= 1
+        with pytest.raises(AssertionError, match=f"here: block {b} differs"):
+            assert_same_blocks(bad, offsets, slots, sizes, "here")
+        with pytest.raises(AssertionError, match=f"here: item {b} differs"):
+            assert_same_items(bad, offsets, streams, "here")
