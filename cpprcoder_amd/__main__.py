@@ -1,14 +1,19 @@
 """python -m cpprcoder_amd c|d|t ...  -- compress / decompress / test files with the MI355X block coder.
 
-    python -m cpprcoder_amd c [-b BLOCK] [--blksort] [--crc] [--static | --coder adaptive|static|rans|rans8] IN OUT
+    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W] [--crc] [--static | --coder adaptive|static|rans|rans8] IN OUT
                                                                IN -> RCXB container (cpprcoder_amd/container.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
+                                                               --planes W: IN is elements of W = 2, 4 or 8 bytes (bf16,
+                                                               fp32, int64 ...), taken apart into byte planes first
+                                                               (include/rcx_planes.h) -> RCXT container;
                                                                --crc: a CRC-32 per block goes into the container
-    python -m cpprcoder_amd d [--no-verify] IN OUT             container -> original bytes.  A container with checksums
+    python -m cpprcoder_amd d [--no-verify] IN OUT             container (RCXB or RCXT, told apart by the magic; an RCXI
+                                                               container holds items, not a file) -> original bytes.
+                                                               A container with checksums
                                                                is verified: on a mismatch the bad block is named on
                                                                stderr, the exit status is 1 and OUT is not written
                                                                (--no-verify: write what the decoder produced)
-    python -m cpprcoder_amd t [--crc] FILE...                  the reference harness's row per file
+    python -m cpprcoder_amd t [--crc] [--planes W] FILE...     the reference harness's row per file
                                                                (|file|ratio|encode|decode|, test/main.cpp:346-356):
                                                                pack, unpack, compare, times incl. PCIe copies
 """
@@ -27,7 +32,9 @@ def parser() -> argparse.ArgumentParser:
     c.add_argument("-b", "--block", type=int, default=65536)
     c.add_argument("--static", action="store_true")
     c.add_argument("--coder", choices=CODERS, default=None)
-    c.add_argument("--blksort", action="store_true")
+    first = c.add_mutually_exclusive_group()  # what goes in front of the coder: one of the two, or nothing
+    first.add_argument("--blksort", action="store_true")
+    first.add_argument("--planes", type=int, choices=(2, 4, 8), default=None, metavar="W")
     c.add_argument("--crc", action="store_true")
     c.add_argument("src")
     c.add_argument("dst")
@@ -39,7 +46,9 @@ def parser() -> argparse.ArgumentParser:
     t.add_argument("-b", "--block", type=int, default=65536)
     t.add_argument("--static", action="store_true")
     t.add_argument("--coder", choices=CODERS, default=None)
-    t.add_argument("--blksort", action="store_true")
+    first = t.add_mutually_exclusive_group()  # what goes in front of the coder: one of the two, or nothing
+    first.add_argument("--blksort", action="store_true")
+    first.add_argument("--planes", type=int, choices=(2, 4, 8), default=None, metavar="W")
     t.add_argument("--crc", action="store_true")
     t.add_argument("files", nargs="+")
     return ap
@@ -50,15 +59,28 @@ def main(argv=None) -> int:
     from . import container, rcx
     coder = CODERS.index(a.coder) if getattr(a, "coder", None) else (1 if getattr(a, "static", False) else 0)
     ctx = rcx.Context(0)
+
+    def pack(data):
+        if a.planes:
+            return container.pack_typed(data, a.planes, a.block, coder, ctx, checksum=a.crc)
+        return container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc)
+
+    def unpack(blob, verify=True):
+        if bytes(blob[:4]) == container.TYPED_MAGIC:
+            return container.unpack_typed(blob, ctx, verify=verify)
+        if bytes(blob[:4]) == container.ITEM_MAGIC:
+            raise container.ContainerError("an RCXI container holds items, not one file: container.unpack_items()")
+        return container.unpack(blob, ctx, verify=verify)
+
     try:
         if a.cmd == "c":
             data = open(a.src, "rb").read()
-            blob = container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc)
+            blob = pack(data)
             open(a.dst, "wb").write(blob)
             print(f"{a.src}: {len(data)} -> {len(blob)} bytes ({len(blob) / max(len(data), 1):.6f})")
         elif a.cmd == "d":
             try:
-                out = container.unpack(open(a.src, "rb").read(), ctx, verify=not a.no_verify)
+                out = unpack(open(a.src, "rb").read(), verify=not a.no_verify)
             except container.ChecksumError as e:
                 print(f"{a.src}: {e}; nothing written", file=sys.stderr)
                 return 1
@@ -71,9 +93,9 @@ def main(argv=None) -> int:
             for path in a.files:
                 data = open(path, "rb").read()
                 t0 = time.perf_counter()
-                blob = container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc)
+                blob = pack(data)
                 t1 = time.perf_counter()
-                back = container.unpack(blob, ctx)
+                back = unpack(blob)
                 t2 = time.perf_counter()
                 ok = back == data
                 bad += not ok

@@ -46,6 +46,26 @@ rejecting what it does not know:
     ..  8 * (nitems + 1)  offsets of the item streams in the payload
     ..  version 2: 4 * nitems  the CRC-32 of each item (u32 LE; 0 for an empty one)
     ..  payload: the item streams back to back
+
+The typed container holds one buffer of 2-, 4- or 8-byte elements (bf16 / fp16 / fp32 values, int32 / int64 indices) that
+went through the byte-plane filter (include/rcx_planes.h; cpprcoder_amd/planes.py) in front of the coder: within a
+superblock of width * block bytes, block s * width + p holds byte p of every element, so each byte position gets a model
+of its own.  A third magic, so that parse() and parse_items() keep refusing what they do not know:
+    0   4  magic  b"RCXT"
+    4   1  version (1)
+    5   1  coder
+    6   2  flags: bit 1 = checksums (FLAG_CRC32); every other bit 0
+    8   4  block size in bytes
+    12  8  n
+    20  8  nblocks = ceil(n / block)
+    28  1  width: bytes per element (2, 4 or 8)
+    29  7  zero
+    36  8 * (nblocks + 1)  offsets of the block streams in the payload
+    ..  with bit 1: 4 * nblocks  the CRC-32 of each block of the SPLIT text (what the coder saw, as with the block sort)
+    ..  payload
+unpack_typed_range(blob, start, stop) decodes the blocks of the superblocks that cover [start, stop) and joins that span
+as a buffer of its own: the transform of a span from one superblock border to another, or to n, is the transform of the
+span taken alone.
 """
 import struct
 
@@ -61,6 +81,10 @@ ITEM_MAGIC = b"RCXI"
 ITEM_VERSION = 1
 _ITEM_FIXED = struct.Struct("<4sBBHQ")
 MAX_ITEM = (1 << 24) - 256  # RCX_MAX_BLOCK
+TYPED_MAGIC = b"RCXT"
+TYPED_VERSION = 1
+_TYPED_FIXED = struct.Struct("<4sBBHIQQB7s")
+WIDTHS = (2, 4, 8)
 
 
 def coded_size(n: int, flags: int) -> int:
@@ -197,8 +221,9 @@ def _unpack_checked(ctx, c) -> bytes:
     return d_out.cpu().numpy().tobytes()
 
 
-def _decode_picked_checked(ctx, c, lengths, pick, kind: str) -> list:
-    """Streams pick[k] of a checked container, decoded back to back and verified -> their bytes."""
+def _decode_picked_device(ctx, c, lengths, pick, kind: str, checked: bool):
+    """Streams pick[k] of a container, decoded back to back on the device and, if `checked`, verified there
+    -> (the device buffer, the table of where each pick lies in it)."""
     import torch
     from . import rcx
     pick = np.asarray(pick, dtype=np.uint64)
@@ -206,8 +231,15 @@ def _decode_picked_checked(ctx, c, lengths, pick, kind: str) -> list:
     d_out = torch.empty(max(int(doffs[-1]), 1), dtype=torch.uint8, device="cuda")
     ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), doffs, d_out, pick=pick, coder=c["coder"])
     ctx.sync_status()
-    ctx.verify_items_device(d_out, doffs, _cuda(c["crcs"][pick.astype(np.int64)]))
-    _sync_checked(ctx, kind, lambda k: int(pick[k]))
+    if checked:
+        ctx.verify_items_device(d_out, doffs, _cuda(c["crcs"][pick.astype(np.int64)]))
+        _sync_checked(ctx, kind, lambda k: int(pick[k]))
+    return d_out, doffs
+
+
+def _decode_picked_checked(ctx, c, lengths, pick, kind: str) -> list:
+    """Streams pick[k] of a checked container, decoded back to back and verified -> their bytes."""
+    d_out, doffs = _decode_picked_device(ctx, c, lengths, pick, kind, True)
     out = d_out.cpu().numpy()
     return [out[int(doffs[k]): int(doffs[k + 1])] for k in range(len(pick))]
 
@@ -372,3 +404,163 @@ def unpack_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
     finally:
         if own:
             ctx.close()
+
+
+# ---- the typed container: the byte-plane filter in front of the coder ---------------------------------------------------
+def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs=None) -> bytes:
+    offsets = np.ascontiguousarray(offsets, dtype="<u8")
+    nblocks = len(offsets) - 1
+    if width not in WIDTHS:
+        raise ContainerError("an element is 2, 4 or 8 bytes wide")
+    if nblocks != (n + block - 1) // block:
+        raise ContainerError("offsets do not match n and the block size")
+    flags, table = 0, b""
+    if crcs is not None:
+        crcs = np.ascontiguousarray(crcs, dtype="<u4")
+        if len(crcs) != nblocks:
+            raise ContainerError("one checksum per block or item")
+        flags, table = FLAG_CRC32, crcs.tobytes()
+    return _TYPED_FIXED.pack(TYPED_MAGIC, TYPED_VERSION, coder, flags, block, n, nblocks, width, bytes(7)) + offsets.tobytes() + table
+
+
+def parse_typed(blob):
+    """-> dict(coder, flags, block, n, nblocks, width, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, payload uint8 view)"""
+    buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+    if len(buf) < _TYPED_FIXED.size:
+        raise ContainerError("shorter than a header")
+    magic, version, coder, flags, block, n, nblocks, width, reserved = _TYPED_FIXED.unpack(bytes(buf[: _TYPED_FIXED.size]))
+    if magic != TYPED_MAGIC:
+        raise ContainerError("not an RCXT container")
+    if version != TYPED_VERSION or coder not in (0, 1, 2, 3) or flags & ~FLAG_CRC32:
+        raise ContainerError("unsupported container version, coder or flags")
+    if width not in WIDTHS or reserved != bytes(7):
+        raise ContainerError("an element is 2, 4 or 8 bytes wide, and the reserved bytes are zero")
+    if block < 16 or block > (1 << 24) - 256 or nblocks != (n + block - 1) // block:
+        raise ContainerError("inconsistent header")
+    end = _TYPED_FIXED.size + 8 * (nblocks + 1)
+    if nblocks > len(buf) or len(buf) < end:
+        raise ContainerError("truncated offset table")
+    offsets = np.frombuffer(bytes(buf[_TYPED_FIXED.size:end]), dtype="<u8").astype(np.uint64)
+    crcs = None
+    if flags & FLAG_CRC32:
+        if len(buf) < end + 4 * nblocks:
+            raise ContainerError("truncated checksum table")
+        crcs = np.frombuffer(bytes(buf[end: end + 4 * nblocks]), dtype="<u4").astype(np.uint32)
+        end += 4 * nblocks
+    if offsets[0] != 0 or np.any(np.diff(offsets.astype(np.int64)) < 0) or end + int(offsets[-1]) != len(buf):
+        raise ContainerError("offset table does not match the payload")
+    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "width": width, "offsets": offsets, "crcs": crcs,
+            "payload": buf[end:]}
+
+
+def _typed_source(data, width):
+    """-> (the bytes: a uint8 cuda tensor if `data` lies on the GPU, else a uint8 numpy array; the element width)"""
+    if type(data).__module__.split(".")[0] == "torch":
+        import torch
+        if not data.is_contiguous():
+            raise ContainerError("a tensor must be contiguous")
+        width = data.element_size() if width is None else width
+        flat = data.detach().reshape(-1).view(torch.uint8)
+        src = flat if flat.is_cuda else flat.numpy()
+    elif isinstance(data, np.ndarray):
+        width = data.dtype.itemsize if width is None else width
+        src = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    else:
+        src = np.frombuffer(data, dtype=np.uint8)
+    if width is None:
+        raise ContainerError("plain bytes have no element size: give the width")
+    if width not in WIDTHS:
+        raise ContainerError(f"an element is 2, 4 or 8 bytes wide, not {width}")
+    return src, width
+
+
+def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False) -> bytes:
+    """data: bytes, a numpy array or a contiguous torch tensor (CPU or GPU) -> an RCXT container.  width=None: the
+    element size of the array or tensor.  One upload (none for a GPU tensor), then split, encode and, with checksum=True,
+    the CRC-32 of every block of the split text, all with the device calls."""
+    import torch
+    from . import planes, rcx
+    src, width = _typed_source(data, width)
+    n = int(src.numel()) if hasattr(src, "numel") else len(src)
+    if n == 0:
+        return typed_header_bytes(coder, block, 0, width, np.zeros(1, np.uint64), np.zeros(0, np.uint32) if checksum else None)
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        d_src = src if hasattr(src, "numel") else _cuda(src)
+        nblocks = rcx.block_count(n, block)
+        d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
+        d_dst = torch.empty(rcx.encode_bound(n, block, coder), dtype=torch.uint8, device="cuda")
+        d_offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
+        planes.split_device(ctx, d_src, width, block, d_split)
+        ctx.encode_blocks_device(d_split, block, d_dst, d_offs, coder=coder)
+        crcs = None
+        if checksum:
+            d_crc = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
+            ctx.crc32_blocks_device(d_split, block, d_crc)
+        ctx.sync_status()
+        if checksum:
+            crcs = _crcs_of(d_crc)
+        offsets = d_offs.cpu().numpy().astype(np.uint64)
+        return typed_header_bytes(coder, block, n, width, offsets, crcs) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
+    finally:
+        if own:
+            ctx.close()
+
+
+def unpack_typed(blob, ctx=None, verify: bool = True) -> bytes:
+    """Decode, verify the split text block by block if the container carries checksums (verify=False skips that), join."""
+    import torch
+    from . import planes, rcx
+    c = parse_typed(blob)
+    n = c["n"]
+    if n == 0:
+        return b""
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
+        ctx.decode_blocks_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), n, c["block"], d_split, coder=c["coder"])
+        ctx.sync_status()
+        if verify and c["crcs"] is not None:
+            ctx.verify_blocks_device(d_split, c["block"], _cuda(c["crcs"]))
+            _sync_checked(ctx, "block")
+        d_out = torch.empty(n, dtype=torch.uint8, device="cuda")
+        planes.join_device(ctx, d_split, c["width"], c["block"], d_out)
+        return d_out.cpu().numpy().tobytes()
+    finally:
+        if own:
+            ctx.close()
+
+
+def unpack_typed_range(blob, start: int, stop: int, ctx=None, verify: bool = True) -> bytes:
+    """The bytes [start, stop) of the original: only the blocks of the superblocks that cover them are decoded and, in a
+    container with checksums, verified; their span is joined as a buffer of its own."""
+    import torch
+    from . import planes, rcx
+    c = parse_typed(blob)
+    n, block, width, nblocks = c["n"], c["block"], c["width"], c["nblocks"]
+    if not 0 <= start <= stop <= n:
+        raise ContainerError("range outside the data")
+    if start == stop:
+        return b""
+    superblock = width * block
+    first, last = start // superblock, (stop - 1) // superblock
+    pick = np.arange(first * width, min(nblocks, (last + 1) * width), dtype=np.uint64)
+    lengths = np.full(nblocks, block, dtype=np.uint64)
+    lengths[-1] = n - (nblocks - 1) * block
+    span = min(n, (last + 1) * superblock) - first * superblock
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        # the picked blocks follow one another and all but the container's last are whole: back to back they are the span's split text
+        d_split, doffs = _decode_picked_device(ctx, c, lengths, pick, "block", verify and c["crcs"] is not None)
+        if int(doffs[-1]) != span:
+            raise ContainerError("decoded size differs from the header")
+        d_out = torch.empty(span, dtype=torch.uint8, device="cuda")
+        planes.join_device(ctx, d_split[:span], width, block, d_out)
+        out = d_out.cpu().numpy()
+    finally:
+        if own:
+            ctx.close()
+    return out[start - first * superblock: stop - first * superblock].tobytes()

@@ -422,6 +422,15 @@ class Context:
         _check(lib().rcx_crc32_items(self._h, src.ctypes.data, offs.ctypes.data, len(offs) - 1, crc.ctypes.data), "rcx_crc32_items")
         return crc
 
+    # ---- the byte-plane filter for typed data (include/rcx_planes.h; cpprcoder_amd/planes.py) ----
+    def planes_split_device(self, src, width: int, block: int, dst, stream=None) -> None:
+        from . import planes
+        planes.split_device(self, src, width, block, dst, stream)
+
+    def planes_join_device(self, src, width: int, block: int, dst, stream=None) -> None:
+        from . import planes
+        planes.join_device(self, src, width, block, dst, stream)
+
     # ---- block sort (blksort.h) ----------------------------------------------
     def bwt_encode(self, data) -> np.ndarray:
         """BlkSort::encode on a host buffer -> the encoded bytes."""

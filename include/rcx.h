@@ -250,6 +250,9 @@ int rcx_crc32_verify_items_device(rcx_ctx* ctx, const void* d_src, const uint64_
 int rcx_crc32_blocks(rcx_ctx* ctx, const uint8_t* src, uint64_t n, uint32_t block, uint32_t* crc);
 int rcx_crc32_items(rcx_ctx* ctx, const uint8_t* src, const uint64_t* src_offsets, uint64_t nitems, uint32_t* crc);
 
+/* The byte-plane filter for typed data (bf16 / fp32 values, int64 indices ...) in front of these coders has a header of
+ * its own, rcx_planes.h, which includes this one. */
+
 /*
  * Single-stream calls with the reference's exact stream semantics, used by the
  * C++ facade: one stream of any size 0 .. RCX_MAX_STREAM, coded by one GPU lane.
