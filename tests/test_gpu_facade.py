@@ -69,6 +69,25 @@ def test_facade_full_sink(exe, tmp_path, oracle, golden):
     assert [st, rq] == pin["status"] and size == pin["size"]
 
 
+def test_facade_decoder_in_pieces_into_a_sink_that_fills(exe, tmp_path, oracle):
+    """AdaptiveRangeDecoder<>::decode fed piece by piece (cpprcoder.h:872-924) when writeByte fails (:909-911): the facade takes
+    the symbols from the device 65536 at a time, so the sink may fill in a later trip of its loop, on that border exactly
+    (a sink of 65536 bytes), or while the input has not even filled one chunk (16 bytes).  Status, request size, the sink's
+    size and its bytes are the oracle's for the same pieces and capacity (a MemoryStream rounds its capacity up to 16)."""
+    v = workloads.zipf(200_000, 5).tobytes()
+    comp = oracle.adaptive_encode(v)[1]
+    for piece, cap in ((1000, 65536), (1000, 65537), (4096, 100_000), (0, 70_000), (1000, 16)):
+        (rst, rrq), rout, rsize = oracle.adaptive_decode_chunked(comp, piece or len(comp), cap)
+        assert rst == 1 and rsize == (cap + 15) // 16 * 16 and rrq == len(v) - rsize  # (the oracle's answers, pinned)
+        (st, rq, size, _), out = run(exe, tmp_path, "dec", comp, cap, piece)
+        assert (st, rq, size) == (rst, rrq, rsize) and out[: len(rout)] == rout and out == v[:rsize], (piece, cap)
+    # the input runs dry instead: the first half of the stream, in pieces
+    half = comp[: len(comp) // 2]
+    (rst, rrq), rout, rsize = oracle.adaptive_decode_chunked(half, 1000, len(v))
+    (st, rq, size, _), out = run(exe, tmp_path, "dec", half, len(v), 1000)
+    assert rst == 1 and (st, rq, size) == (rst, rrq, rsize) and out == rout == v[:rsize]
+
+
 def test_facade_block_coder(exe, tmp_path, oracle):
     data = workloads.canterbury_tiled(700_001)
     (total, noff), comp = run(exe, tmp_path, "blocks", data.tobytes(), 65536)

@@ -147,3 +147,49 @@ def test_the_comparisons_fail_when_they_should():
             assert_same_blocks(bad, offsets, slots, sizes, "here")
         with pytest.raises(AssertionError, match=f"here: item {b} differs"):
             assert_same_items(bad, offsets, streams, "here")
+
+
+# ---- tests/resumable_cases.py: what the GPU tests of the resumable coders take for granted about their inputs -------------
+def test_a_constant_piece_ends_at_the_halving():
+    import resumable_cases as rc
+    from golden_cases import LONG_ADAPTIVE, NO_HALVING
+    assert rc.H == NO_HALVING == (1 << 24) - 256 and NO_HALVING % 1_048_560 == 0 and rc.HALVING_PIECE == 1_048_560
+    assert rc.LONG_UNIFORM in LONG_ADAPTIVE and rc.LONG_MIN_ZIPF in LONG_ADAPTIVE
+    sizes = rc.around_halving(NO_HALVING + 5000)
+    assert sizes == [NO_HALVING - 1, 1, 1, 4999] and sum(sizes) == NO_HALVING + 5000
+    assert rc.constant(10, 4) == [4, 4, 2] and rc.split(b"abcdefghij", [4, 4, 2]) == [b"abcd", b"efgh", b"ij"]
+    assert sum(rc.uneven(311_564)) == 311_564 and rc.uneven(311_564)[:5] == [100_000, 1, 1, 70_000, 8]
+
+
+def test_the_carry_input_outgrows_the_facades_guess(oracle):
+    import resumable_cases as rc
+    data = rc.carry_input()
+    assert len(data) == rc.CARRY_N
+    (st, rq), sink, sizes = oracle.adaptive_encode_trace(data, rc.CARRY_PIECE)
+    jumps = np.diff(sizes)
+    assert (st, rq) == (0, 0) and int(jumps.max()) > 3 * 64 + 4096 == rc.FACADE_ROOM
+    assert int(np.count_nonzero(jumps > rc.FACADE_ROOM)) == 1
+    # the writer restated in resumable_cases agrees with the oracle about where the run ends, and how
+    j = rc.carrying_symbol(data)
+    assert j // rc.CARRY_PIECE == int(np.argmax(jumps))
+    assert b"\x00" * (rc.CARRY_RUN - 1) in sink and b"\xff" * rc.CARRY_RUN not in sink
+
+
+def test_the_altered_piece_does_not_carry(oracle):
+    import resumable_cases as rc
+    data = rc.carry_input()
+    altered, j = rc.without_the_carry(data)
+    assert len(altered) == len(data) and np.array_equal(altered[:j], data[:j]) and altered[j] != data[j]
+    long_runs = [e for e in rc.writer_events(altered) if e[1] >= rc.CARRY_RUN]
+    assert len(long_runs) == 1 and long_runs[0][0] == j and not long_runs[0][2]  # the run ends in symbol j, by a smaller byte
+    assert b"\xff" * rc.CARRY_RUN in oracle.adaptive_encode(altered)[1]
+
+
+def test_the_launch_loop_input_is_long_and_codes_small(oracle):
+    import resumable_cases as rc
+    v = rc.loop_input()
+    assert len(v) == rc.LOOP_N == 2_621_440 == 5 * rc.CHUNK // 2 and int(v.max()) == 3
+    assert len(oracle.adaptive_encode(v)[1]) < 1_000_000
+    assert [-(-rc.LOOP_N // cap) for cap in rc.LOOP_CAPS + (rc.LOOP_ONE_CALL,)] == [3, 3, 3, 2, 1]
+    kinds = [(k, len(b)) for k, b, _ in rc.interleaved_inputs()]
+    assert [k for k, _ in kinds] == ["dec", "enc", "dec", "enc"] and all(20_000 <= n <= 70_000 for _, n in kinds)

@@ -6,6 +6,7 @@ from __future__ import annotations
 import numpy as np
 
 import carry_runs
+import resumable_cases
 from cpprcoder_amd import workloads
 
 
@@ -26,6 +27,13 @@ def cases():
     for run in (3, 40, 300):
         data = carry_runs.carry_run_block(4096, run, 5 + run)
         out.append((f"carry through a run of {run} pending bytes, pieces of 64", bytes(data), 64, None))
+    # a run of 5000 pending bytes that begins with the stream's second byte (tests/resumable_cases.py): for 83 calls the sink
+    # stays at 5 bytes, and the call that carries hands on 5005 -- more than a caller's guess of 3 * 64 + 4096 for a piece of
+    # 64 (the facade's), so rcx_estream_encode refuses once with RCX_E_CAPACITY.  Then into a sink that fills inside the
+    # run, about 2000 bytes into it: the reference writes the carried byte and zeros until its writeByte fails.
+    long_run = bytes(resumable_cases.carry_input())
+    out.append(("carry through a run of 5000 pending bytes, pieces of 64", long_run, resumable_cases.CARRY_PIECE, None))
+    out.append(("carry through a run of 5000 pending bytes, the sink fills inside the run", long_run, resumable_cases.CARRY_PIECE, 2000))
     # a sink that fills: in a symbol of some piece, and in the last piece's finish()
     out.append(("zipf, sink of 5000 bytes", zipf, 777, 5000))
     out.append(("uniform, sink of 16384 bytes", uni, 4096, 16384))
