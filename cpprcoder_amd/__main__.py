@@ -1,11 +1,17 @@
 """python -m cpprcoder_amd c|d|t ...  -- compress / decompress / test files with the MI355X block coder.
 
-    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W] [--crc] [--static | --coder adaptive|static|rans|rans8] IN OUT
+    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag]] [--crc]
+                              [--static | --coder adaptive|static|rans|rans8] IN OUT
                                                                IN -> RCXB container (cpprcoder_amd/container.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
                                                                --planes W: IN is elements of W = 2, 4 or 8 bytes (bf16,
                                                                fp32, int64 ...), taken apart into byte planes first
                                                                (include/rcx_planes.h) -> RCXT container;
+                                                               --predict delta|zigzag (with --planes only): the elements
+                                                               are integers with small differences (sorted keys, offsets,
+                                                               timestamps, samples): each becomes its difference to the
+                                                               one in front first, zigzag for differences of both signs
+                                                               (include/rcx_predict.h); unsorted data gets worse by it;
                                                                --crc: a CRC-32 per block goes into the container
     python -m cpprcoder_amd d [--no-verify] IN OUT             container (RCXB or RCXT, told apart by the magic; an RCXI
                                                                container holds items, not a file) -> original bytes.
@@ -13,7 +19,8 @@
                                                                is verified: on a mismatch the bad block is named on
                                                                stderr, the exit status is 1 and OUT is not written
                                                                (--no-verify: write what the decoder produced)
-    python -m cpprcoder_amd t [--crc] [--planes W] FILE...     the reference harness's row per file
+    python -m cpprcoder_amd t [--crc] [--planes W [--predict delta|zigzag]] FILE...
+                                                               the reference harness's row per file
                                                                (|file|ratio|encode|decode|, test/main.cpp:346-356):
                                                                pack, unpack, compare, times incl. PCIe copies
 """
@@ -23,10 +30,21 @@ import time
 
 
 CODERS = ("adaptive", "static", "rans", "rans8")  # include/rcx.h: RCX_CODER_*
+PREDICTORS = ("delta", "zigzag")                  # include/rcx_predict.h: RCX_PRED_DELTA, RCX_PRED_ZIGZAG
+
+
+class _Parser(argparse.ArgumentParser):
+    """One rule argparse has no word for: --predict without --planes is an argument error."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if getattr(a, "predict", None) and not a.planes:
+            self.error("--predict needs --planes W: the predictor works on elements")
+        return a
 
 
 def parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(prog="python -m cpprcoder_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = _Parser(prog="python -m cpprcoder_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
     c = sub.add_parser("c")
     c.add_argument("-b", "--block", type=int, default=65536)
@@ -35,6 +53,7 @@ def parser() -> argparse.ArgumentParser:
     first = c.add_mutually_exclusive_group()  # what goes in front of the coder: one of the two, or nothing
     first.add_argument("--blksort", action="store_true")
     first.add_argument("--planes", type=int, choices=(2, 4, 8), default=None, metavar="W")
+    c.add_argument("--predict", choices=PREDICTORS, default=None)
     c.add_argument("--crc", action="store_true")
     c.add_argument("src")
     c.add_argument("dst")
@@ -49,6 +68,7 @@ def parser() -> argparse.ArgumentParser:
     first = t.add_mutually_exclusive_group()  # what goes in front of the coder: one of the two, or nothing
     first.add_argument("--blksort", action="store_true")
     first.add_argument("--planes", type=int, choices=(2, 4, 8), default=None, metavar="W")
+    t.add_argument("--predict", choices=PREDICTORS, default=None)
     t.add_argument("--crc", action="store_true")
     t.add_argument("files", nargs="+")
     return ap
@@ -62,7 +82,7 @@ def main(argv=None) -> int:
 
     def pack(data):
         if a.planes:
-            return container.pack_typed(data, a.planes, a.block, coder, ctx, checksum=a.crc)
+            return container.pack_typed(data, a.planes, a.block, coder, ctx, checksum=a.crc, predict=a.predict)
         return container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc)
 
     def unpack(blob, verify=True):

@@ -52,20 +52,23 @@ went through the byte-plane filter (include/rcx_planes.h; cpprcoder_amd/planes.p
 superblock of width * block bytes, block s * width + p holds byte p of every element, so each byte position gets a model
 of its own.  A third magic, so that parse() and parse_items() keep refusing what they do not know:
     0   4  magic  b"RCXT"
-    4   1  version (1)
+    4   1  version (1; 2 with a predictor)
     5   1  coder
     6   2  flags: bit 1 = checksums (FLAG_CRC32); every other bit 0
     8   4  block size in bytes
     12  8  n
     20  8  nblocks = ceil(n / block)
     28  1  width: bytes per element (2, 4 or 8)
-    29  7  zero
+    29  1  version 2: the predictor in front of the filter (include/rcx_predict.h: 1 delta, 2 delta + zigzag); version 1: zero
+    30  6  zero
     36  8 * (nblocks + 1)  offsets of the block streams in the payload
-    ..  with bit 1: 4 * nblocks  the CRC-32 of each block of the SPLIT text (what the coder saw, as with the block sort)
+    ..  with bit 1: 4 * nblocks  the CRC-32 of each block of the SPLIT text (what the coder saw, as with the block sort;
+        with a predictor the predicted and split text)
     ..  payload
 unpack_typed_range(blob, start, stop) decodes the blocks of the superblocks that cover [start, stop) and joins that span
 as a buffer of its own: the transform of a span from one superblock border to another, or to n, is the transform of the
-span taken alone.
+span taken alone.  A predictor (pack_typed(..., predict="delta" | "zigzag"): for integers whose differences are small) is
+opt-in and restarts in every superblock, so all of that holds with it; without one a container is byte for byte version 1.
 """
 import struct
 
@@ -83,6 +86,8 @@ _ITEM_FIXED = struct.Struct("<4sBBHQ")
 MAX_ITEM = (1 << 24) - 256  # RCX_MAX_BLOCK
 TYPED_MAGIC = b"RCXT"
 TYPED_VERSION = 1
+TYPED_VERSION_PRED = 2  # the same layout + the predictor at byte 29; only with a predictor
+PREDICTORS = {None: 0, "delta": 1, "zigzag": 2}  # include/rcx_predict.h: RCX_PRED_*
 _TYPED_FIXED = struct.Struct("<4sBBHIQQB7s")
 WIDTHS = (2, 4, 8)
 
@@ -407,11 +412,13 @@ def unpack_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
 
 
 # ---- the typed container: the byte-plane filter in front of the coder ---------------------------------------------------
-def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs=None) -> bytes:
+def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs=None, pred: int = 0) -> bytes:
     offsets = np.ascontiguousarray(offsets, dtype="<u8")
     nblocks = len(offsets) - 1
     if width not in WIDTHS:
         raise ContainerError("an element is 2, 4 or 8 bytes wide")
+    if type(pred) is not int or pred not in (0, 1, 2):
+        raise ContainerError("a predictor is 0 (none), 1 (delta) or 2 (zigzag)")
     if nblocks != (n + block - 1) // block:
         raise ContainerError("offsets do not match n and the block size")
     flags, table = 0, b""
@@ -420,21 +427,24 @@ def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs
         if len(crcs) != nblocks:
             raise ContainerError("one checksum per block or item")
         flags, table = FLAG_CRC32, crcs.tobytes()
-    return _TYPED_FIXED.pack(TYPED_MAGIC, TYPED_VERSION, coder, flags, block, n, nblocks, width, bytes(7)) + offsets.tobytes() + table
+    version = TYPED_VERSION_PRED if pred else TYPED_VERSION  # version 2 only with a predictor
+    return _TYPED_FIXED.pack(TYPED_MAGIC, version, coder, flags, block, n, nblocks, width, bytes([pred]) + bytes(6)) + offsets.tobytes() + table
 
 
 def parse_typed(blob):
-    """-> dict(coder, flags, block, n, nblocks, width, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, payload uint8 view)"""
+    """-> dict(coder, flags, block, n, nblocks, width, pred, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, payload uint8 view);
+    pred is 0 for a version 1 container"""
     buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
     if len(buf) < _TYPED_FIXED.size:
         raise ContainerError("shorter than a header")
     magic, version, coder, flags, block, n, nblocks, width, reserved = _TYPED_FIXED.unpack(bytes(buf[: _TYPED_FIXED.size]))
     if magic != TYPED_MAGIC:
         raise ContainerError("not an RCXT container")
-    if version != TYPED_VERSION or coder not in (0, 1, 2, 3) or flags & ~FLAG_CRC32:
+    if version not in (TYPED_VERSION, TYPED_VERSION_PRED) or coder not in (0, 1, 2, 3) or flags & ~FLAG_CRC32:
         raise ContainerError("unsupported container version, coder or flags")
-    if width not in WIDTHS or reserved != bytes(7):
-        raise ContainerError("an element is 2, 4 or 8 bytes wide, and the reserved bytes are zero")
+    pred = reserved[0]
+    if width not in WIDTHS or reserved[1:] != bytes(6) or (pred not in (1, 2) if version == TYPED_VERSION_PRED else pred != 0):
+        raise ContainerError("an element is 2, 4 or 8 bytes wide, version 2 names its predictor, and the reserved bytes are zero")
     if block < 16 or block > (1 << 24) - 256 or nblocks != (n + block - 1) // block:
         raise ContainerError("inconsistent header")
     end = _TYPED_FIXED.size + 8 * (nblocks + 1)
@@ -449,8 +459,8 @@ def parse_typed(blob):
         end += 4 * nblocks
     if offsets[0] != 0 or np.any(np.diff(offsets.astype(np.int64)) < 0) or end + int(offsets[-1]) != len(buf):
         raise ContainerError("offset table does not match the payload")
-    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "width": width, "offsets": offsets, "crcs": crcs,
-            "payload": buf[end:]}
+    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "width": width, "pred": pred, "offsets": offsets,
+            "crcs": crcs, "payload": buf[end:]}
 
 
 def _typed_source(data, width):
@@ -474,16 +484,21 @@ def _typed_source(data, width):
     return src, width
 
 
-def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False) -> bytes:
+def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False, predict=None) -> bytes:
     """data: bytes, a numpy array or a contiguous torch tensor (CPU or GPU) -> an RCXT container.  width=None: the
-    element size of the array or tensor.  One upload (none for a GPU tensor), then split, encode and, with checksum=True,
-    the CRC-32 of every block of the split text, all with the device calls."""
-    import torch
-    from . import planes, rcx
+    element size of the array or tensor.  predict=None, "delta" or "zigzag": the predictor of include/rcx_predict.h in front of
+    the filter, for integers whose differences are small (never chosen for the caller: unsorted data gets worse by it).  One
+    upload (none for a GPU tensor), then split, encode and, with checksum=True, the CRC-32 of every block of the split text,
+    all with the device calls."""
+    if not (predict is None or isinstance(predict, str)) or predict not in PREDICTORS:
+        raise ContainerError(f"a predictor is None, 'delta' or 'zigzag', not {predict!r}")
+    pred = PREDICTORS[predict]
     src, width = _typed_source(data, width)
+    import torch
+    from . import predict as predictor, rcx
     n = int(src.numel()) if hasattr(src, "numel") else len(src)
     if n == 0:
-        return typed_header_bytes(coder, block, 0, width, np.zeros(1, np.uint64), np.zeros(0, np.uint32) if checksum else None)
+        return typed_header_bytes(coder, block, 0, width, np.zeros(1, np.uint64), np.zeros(0, np.uint32) if checksum else None, pred)
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
@@ -492,7 +507,7 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
         d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
         d_dst = torch.empty(rcx.encode_bound(n, block, coder), dtype=torch.uint8, device="cuda")
         d_offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
-        planes.split_device(ctx, d_src, width, block, d_split)
+        predictor.split_device(ctx, d_src, width, block, pred, d_split)  # (no predictor: the plane filter's own kernel)
         ctx.encode_blocks_device(d_split, block, d_dst, d_offs, coder=coder)
         crcs = None
         if checksum:
@@ -502,7 +517,7 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
         if checksum:
             crcs = _crcs_of(d_crc)
         offsets = d_offs.cpu().numpy().astype(np.uint64)
-        return typed_header_bytes(coder, block, n, width, offsets, crcs) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
+        return typed_header_bytes(coder, block, n, width, offsets, crcs, pred) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
     finally:
         if own:
             ctx.close()
@@ -511,7 +526,7 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
 def unpack_typed(blob, ctx=None, verify: bool = True) -> bytes:
     """Decode, verify the split text block by block if the container carries checksums (verify=False skips that), join."""
     import torch
-    from . import planes, rcx
+    from . import predict as predictor, rcx
     c = parse_typed(blob)
     n = c["n"]
     if n == 0:
@@ -526,7 +541,7 @@ def unpack_typed(blob, ctx=None, verify: bool = True) -> bytes:
             ctx.verify_blocks_device(d_split, c["block"], _cuda(c["crcs"]))
             _sync_checked(ctx, "block")
         d_out = torch.empty(n, dtype=torch.uint8, device="cuda")
-        planes.join_device(ctx, d_split, c["width"], c["block"], d_out)
+        predictor.join_device(ctx, d_split, c["width"], c["block"], c["pred"], d_out)
         return d_out.cpu().numpy().tobytes()
     finally:
         if own:
@@ -537,7 +552,7 @@ def unpack_typed_range(blob, start: int, stop: int, ctx=None, verify: bool = Tru
     """The bytes [start, stop) of the original: only the blocks of the superblocks that cover them are decoded and, in a
     container with checksums, verified; their span is joined as a buffer of its own."""
     import torch
-    from . import planes, rcx
+    from . import predict as predictor, rcx
     c = parse_typed(blob)
     n, block, width, nblocks = c["n"], c["block"], c["width"], c["nblocks"]
     if not 0 <= start <= stop <= n:
@@ -558,7 +573,7 @@ def unpack_typed_range(blob, start: int, stop: int, ctx=None, verify: bool = Tru
         if int(doffs[-1]) != span:
             raise ContainerError("decoded size differs from the header")
         d_out = torch.empty(span, dtype=torch.uint8, device="cuda")
-        planes.join_device(ctx, d_split[:span], width, block, d_out)
+        predictor.join_device(ctx, d_split[:span], width, block, c["pred"], d_out)
         out = d_out.cpu().numpy()
     finally:
         if own:
