@@ -1,9 +1,10 @@
 """What the GPU tests share: the launch-shape knobs and contexts made under them, the `ctx` fixture, guarded buffers and
-the device calls wrapped in them, the comparisons with the oracle that most tests make, and damaged streams.
+the device calls wrapped in them, the comparisons with the oracle that most tests make, the launch shapes restated with
+the block counts at which they change, and damaged streams.
 
 A test file imports what it needs from here (the fixture by name: `from gpu_support import ctx  # noqa: F401`, one
-context per importing module), never from another test file.  tests/test_support_cpu.py holds Guarded, knobs, chunk_blocks
-and the two comparisons to their contracts on CPU tensors.  Nothing here reads /root/reference.
+context per importing module), never from another test file.  tests/test_support_cpu.py holds Guarded, knobs, chunk_blocks,
+shape_edges and the two comparisons to their contracts on CPU tensors.  Nothing here reads /root/reference.
 """
 import contextlib
 import os
@@ -279,6 +280,40 @@ def chunk_blocks(block, decode, nblocks):
     if chunks > 1:
         cb = -(-nblocks // chunks)
     return (cb + 63) & ~63
+
+
+# ---- launch shapes by block count (csrc/rcx_launch.hpp) ------------------------------------------------------------------
+STATIC_ONE_WAVE = 32768  # blocks from which the static encoder is the one-wave kernel (encode_launches, static3)
+
+
+def _pow2_at_least(x):
+    p = 1
+    while p < x:
+        p <<= 1
+    return p
+
+
+def encode_lanes(nblocks, cus):
+    """encode_lanes(): blocks per workgroup of the multi-wave encoders -- the power of two that gives every CU a
+    workgroup, 64 at the most."""
+    return min(_pow2_at_least(-(-nblocks // cus)), 64)
+
+
+def decode_quads(nblocks, cus):
+    """decode_quads(): blocks per wave of the 4-lane decoders -- the power of two that gives every SIMD (4 a CU) a wave,
+    16 at the most."""
+    return min(_pow2_at_least(-(-nblocks // (4 * cus))), 16)
+
+
+SHAPE_EDGE_IDS = tuple(f"{k}cus{d:+d}" if d else f"{k}cus" for k in (1, 2, 4, 8, 16, 32) for d in (-1, 0, 1)) + ("32767", "32768", "32769")
+
+
+def shape_edges(cus):
+    """The block counts at which a launch shape changes on a device of `cus` compute units, and their neighbours: m - 1,
+    m, m + 1 for m = cus x 1, 2, 4, ... 32 (encode_lanes doubles behind each; decode_quads behind 4, 8, 16 and 32 cus),
+    and 32767 ... 32769 (the static encoder's change of kernel).  One entry per SHAPE_EDGE_IDS, in that order; a count
+    is 1 at the least."""
+    return [max(k * cus + d, 1) for k in (1, 2, 4, 8, 16, 32) for d in (-1, 0, 1)] + [STATIC_ONE_WAVE - 1, STATIC_ONE_WAVE, STATIC_ONE_WAVE + 1]
 
 
 # ---- damaged streams (include/rcx.h, "Damaged streams") ----------------------------------------------------------------

@@ -126,6 +126,74 @@ def test_many_shapes_against_the_oracle(ctx):
     assert np.array_equal(ctx.bwt_decode(enc), data)
 
 
+# ---- the forward kernel's switch points (tests/bwt_cases.py; their premises: tests/test_bwt_cases_cpu.py) ---------------------
+@pytest.fixture(scope="module")
+def switch_points():
+    """name -> (blocks, data, the oracle's encoding), made once for both rank forms.  The run-keyed blocks are dealt out
+    so that the oracle's threads, which take consecutive blocks, each get their share of the slow ones (one long run:
+    deep comparisons, 0.8 - 1.6 s a block).  Oracle passes, 16 threads asked for, measured on 8 cores: the three ladders
+    0.04 / 0.04 / 0.16 s, the RUNNY ladder 0.05 s, the 55 run-keyed blocks 8.9 s (51 s of single-thread work); on the
+    MI355X host, 16 cores, this whole fixture took 2.2 s and each test that uses it 0.02 s at the most."""
+    o = oracle_lib.oracle()
+    sets = {f"open {limit}": bwt_cases.open_ladder(limit) for limit in bwt_cases.LIST_LENGTHS}
+    sets["runny"] = bwt_cases.runny_ladder()
+    keyed = list(bwt_cases.run_key_cases().values())
+    sets["run keys"] = [keyed[(i * 28) % len(keyed)] for i in range(len(keyed))]   # (28 and 55 have no common factor)
+    out = {}
+    for name, blocks in sets.items():
+        data = np.concatenate(blocks)
+        out[name] = (blocks, data, o.bwt_encode(data, threads=16))
+    return out
+
+
+def check_every_block(ctx, blocks, data, want):
+    enc = ctx.bwt_encode(data)
+    assert ctx.bwt_last_ties() == 0
+    assert len(enc) == len(want)
+    for b in range(len(blocks)):
+        assert np.array_equal(enc[b * ENCODED:(b + 1) * ENCODED], want[b * ENCODED:(b + 1) * ENCODED]), b
+    assert np.array_equal(ctx.bwt_decode(enc), data)
+
+
+@pytest.mark.parametrize("limit", bwt_cases.LIST_LENGTHS)
+def test_open_counts_around_a_list_length(ctx, switch_points, limit):
+    """A round of rcx_bwt_fwd_k takes its form from `open`: full passes above 11264, else a list of 11264, 3072 or 1024
+    entries, exactly full at those counts.  Seven blocks whose rounds with shift 8 begin, by the model of
+    bwt_cases.open_counts (derived from the code, not measured: the kernel does not report `open`), with limit - 3 ...
+    limit + 3 rotations open; every block against the oracle."""
+    check_every_block(ctx, *switch_points[f"open {limit}"])
+
+
+def test_a_ladder_one_byte_off_a_16_byte_border(ctx, switch_points):
+    """The 3072 ladder through the device call, the source one byte behind a 16-byte border and the destination one
+    byte in front of one: the block's image in LDS is shifted, and the run detection reads it bytewise."""
+    _, data, want = switch_points["open 3072"]
+    src = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
+    dst = torch.full((len(want) + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
+    src[1: 1 + len(data)] = torch.from_numpy(data.copy()).cuda()
+    ctx.bwt_encode_device(src[1: 1 + len(data)], dst[15: 15 + len(want)])
+    ctx.sync_status()
+    got = dst.cpu().numpy()
+    for b in range(len(want) // ENCODED):
+        assert np.array_equal(got[15 + b * ENCODED: 15 + (b + 1) * ENCODED], want[b * ENCODED:(b + 1) * ENCODED]), b
+    assert (got[:15] == 0xA5).all() and (got[15 + len(want):] == 0xA5).all()
+    assert ctx.bwt_last_ties() == 0
+
+
+def test_changes_around_the_run_key_threshold(ctx, switch_points):
+    """Blocks of 4092 ... 4100 runs: below RCX_BWT_RUNNY = 4096 changes a block starts from run keys, from there on
+    from two-byte keys; every other block has a run round its end."""
+    check_every_block(ctx, *switch_points["runny"])
+
+
+def test_run_keys_with_runs_over_the_block_end(ctx, switch_points):
+    """Run-keyed blocks, as built and turned so that one run lies over the block's end (next_change past 32768 and the
+    wrapped place behind the run in run_key): two runs, a^k b^(32768 - k), one run of 32767, runs of 31 ... 65 bytes
+    at places 0, 1 and 31 modulo 32, runs whose keys tie, runs of 64 and long runs."""
+    check_every_block(ctx, *switch_points["run keys"])
+
+
 def test_inverse_of_arbitrary_bytes_is_the_reference_walk(ctx):
     """BlkSort::decode is defined for any column and any row below 32768 (the walk just follows a permutation, possibly
     round a short cycle): the GPU must follow it the same way."""

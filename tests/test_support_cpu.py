@@ -6,7 +6,8 @@ import os
 import numpy as np
 import pytest
 
-from gpu_support import GUARD, Guarded, assert_same_blocks, assert_same_items, chunk_blocks, knobs
+from gpu_support import (GUARD, SHAPE_EDGE_IDS, Guarded, assert_same_blocks, assert_same_items, chunk_blocks, decode_quads, encode_lanes,
+                         knobs, shape_edges)
 
 SIZES, OFFSETS = (0, 1, 33), (0, 15)
 
@@ -114,6 +115,36 @@ def test_chunk_blocks_restates_host_chunk_blocks():
         (1 << 20, True, (1 << 23) + 1): 8192,  # one block more: 8192 a chunk, 1025 chunks of 8185 -> 8192
     }.items():
         assert chunk_blocks(block, decode, nblocks) == want, (block, decode, nblocks)
+
+
+@pytest.mark.parametrize("cus", [256, 304])
+def test_shape_edges_sit_on_every_change_of_launch_shape(cus):
+    """csrc/rcx_launch.hpp encode_lanes() / decode_quads(), by hand, and the counts tests/test_gpu_launch_shapes.py walks:
+    one block more than each multiple changes the shape, so a list without m + 1 would miss the change."""
+    edges = shape_edges(cus)
+    assert len(edges) == len(SHAPE_EDGE_IDS) == 21 and len(set(SHAPE_EDGE_IDS)) == 21
+    for k, quads in ((1, 1), (2, 2), (4, 4), (8, 8)):
+        m = 4 * cus * k
+        assert (decode_quads(m - 1, cus), decode_quads(m, cus), decode_quads(m + 1, cus)) == (quads, quads, 2 * quads), m
+        assert {m - 1, m, m + 1} <= set(edges)
+    for k in (1, 2, 4, 8, 16, 32):
+        m = cus * k
+        assert (encode_lanes(m, cus), encode_lanes(m + 1, cus)) == (k, 2 * k), m
+        assert encode_lanes(m - 1, cus) == k or k == 1
+        assert {m - 1, m, m + 1} <= set(edges)
+    assert decode_quads(1, cus) == encode_lanes(1, cus) == 1
+    assert decode_quads(1 << 20, cus) == 16 and encode_lanes(1 << 20, cus) == 64          # the caps
+    assert {32767, 32768, 32769} <= set(edges)
+    assert edges == sorted(edges) or cus * 32 > 32767    # (in ascending order where the device is no larger than 1023 CUs)
+
+
+def test_shape_edges_of_256_compute_units():
+    edges = shape_edges(256)
+    assert {1025, 8193, 32768} <= set(edges) and edges[:4] == [255, 256, 257, 511] and min(shape_edges(1)) == 1
+    assert [decode_quads(n, 256) for n in (1024, 1025, 2048, 2049, 4096, 4097, 8192, 8193)] == [1, 2, 2, 4, 4, 8, 8, 16]
+    assert [encode_lanes(n, 256) for n in (256, 257, 8192, 8193, 32768)] == [1, 2, 32, 64, 64]
+    # neither power-of-two rounding nor the cap is taken for granted: 3 workgroups' worth rounds up to 4
+    assert encode_lanes(3 * 256, 256) == 4 and decode_quads(3 * 1024, 256) == 4 and decode_quads(5 * 1024, 256) == 8
 
 
 def four_blocks():
