@@ -12,8 +12,7 @@
 #include "rcx_streams.hpp"  // single streams, whole and resumable
 #include "rcx_bwt_api.hpp"  // the block sort
 #include "rcx_crc_api.hpp"  // CRC-32 per block or item
-#include "rcx_planes_api.hpp" // the byte-plane filter (include/rcx_planes.h)
-#include "rcx_predict_api.hpp" // the delta predictor in front of it (include/rcx_predict.h)
+#include "rcx_typed_api.hpp" // the byte-plane filter and the delta predictor in front of it (include/rcx_planes.h, rcx_predict.h)
 
 extern "C" {
 

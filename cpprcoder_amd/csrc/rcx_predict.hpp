@@ -3,11 +3,9 @@
 // the zigzag undone, then an inclusive prefix sum per superblock.  Superblocks, units and the plane layout are those of
 // rcx_planes.hpp; the predictor restarts in every superblock.  All arithmetic is modulo 2^(8W).
 //
-// Forward, rcx_predict_split_k<W, ZIGZAG>: the shape of rcx_planes_k's split -- a lane's unit is 16 elements, a fixed grid
-// loops, a workgroup takes RCX_PLANES_U4 / W rows of 256 units at a time with all their loads in flight, a guarded last
-// step, a byte-wise rest.  The difference is taken in registers between load and transpose; the element in front of a
-// unit comes from one more W-byte load at (the unit's first element - W), a line the neighbouring lane fetches anyway, and
-// is 0 for the first unit of a superblock.  A rest byte's lane loads its element and the one in front.  No LDS.
+// Forward is rcx_planes_k<W, false, PRED> of rcx_planes.hpp, which also has the element type and the forward arithmetic
+// (RcxElem, rcx_zigzag, rcx_elem_get, rcx_elems_put, rcx_predict_unit, rcx_load_elem).  This file holds what only the
+// inverse uses: rcx_unzigzag, the two halves of a unit's scan, rcx_store_elem, the wave scan and the kernel.
 //
 // Inverse, rcx_predict_join_k<W, ZIGZAG>: ONE WAVE OWNS WHOLE SUPERBLOCKS and walks each one TILE by tile, carrying the
 // running element in a register.  THE TILE IS 64 LANES x ONE UNIT = 1024 ELEMENTS (a workgroup is one wave).  Per tile:
@@ -24,7 +22,7 @@
 // byte by byte from the planes, the same wave scan, the same carry.  The R % W tail bytes are copied.
 // No wave ever waits for another: no LDS, no barrier, no flag in memory, no scratch, nothing allocated.
 //
-// Both read exactly [src, src + n) and write exactly [dst, dst + n), at any alignment (the byte-addressed accesses of
+// It reads exactly [src, src + n) and writes exactly [dst, dst + n), at any alignment (the byte-addressed accesses of
 // rcx_planes.hpp and W-byte ones of the same kind).  No floating point, no inline assembly.
 #pragma once
 
@@ -32,80 +30,13 @@
 
 #define RCX_PREDICT_TILE_UNITS 64u // the inverse kernel's tile: one wave, one unit a lane = 1024 elements
 
-// ---- the arithmetic of one unit: plain functions, also compiled for the host (tests/sim/predict_sim.cpp) -------------------
-// An element of W bytes lives in the low 8W bits of a T: u32 for W = 2 and 4, u64 for W = 8.
-template <u32 W>
-struct RcxElem {
-    typedef u32 T;
-};
-template <>
-struct RcxElem<8> {
-    typedef u64 T;
-};
-
-template <u32 W>
-RCX_DEV typename RcxElem<W>::T rcx_elem_mask()
-{
-    typedef typename RcxElem<W>::T T;
-    return W == 2 ? (T)0xFFFFu : (T) ~(T)0;
-}
-
-// z = (d << 1) XOR (0 - (d >> (8W - 1))), logical shifts; d < 2^(8W)
-template <u32 W>
-RCX_DEV typename RcxElem<W>::T rcx_zigzag(typename RcxElem<W>::T d)
-{
-    typedef typename RcxElem<W>::T T;
-    return ((T)(d << 1) ^ (T)((T)0 - (T)(d >> (8 * W - 1)))) & rcx_elem_mask<W>();
-}
-
+// ---- the arithmetic of one unit, inverse: plain functions, also compiled for the host (tests/sim/predict_sim.cpp) -----------
 // d = (z >> 1) XOR (0 - (z & 1))
 template <u32 W>
 RCX_DEV typename RcxElem<W>::T rcx_unzigzag(typename RcxElem<W>::T z)
 {
     typedef typename RcxElem<W>::T T;
     return ((T)(z >> 1) ^ (T)((T)0 - (T)(z & 1u))) & rcx_elem_mask<W>();
-}
-
-// Element k (0 .. 15) of a unit held as 4W little-endian words in memory order, and the other way.
-template <u32 W>
-RCX_DEV typename RcxElem<W>::T rcx_elem_get(const u32 (&w)[4 * W], u32 k)
-{
-    typedef typename RcxElem<W>::T T;
-    if constexpr (W == 2) return (w[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-    else if constexpr (W == 4) return w[k];
-    else return (T)w[2 * k] | ((T)w[2 * k + 1] << 32);
-}
-
-template <u32 W>
-RCX_DEV void rcx_elems_put(const typename RcxElem<W>::T (&e)[16], u32 (&w)[4 * W])
-{
-#pragma unroll
-    for (u32 k = 0; k < 16; ++k) {
-        if constexpr (W == 2) {
-            if (k & 1u) w[k >> 1] = (u32)e[k - 1] | ((u32)e[k] << 16);
-        } else if constexpr (W == 4) {
-            w[k] = e[k];
-        } else {
-            w[2 * k] = (u32)e[k];
-            w[2 * k + 1] = (u32)(e[k] >> 32);
-        }
-    }
-}
-
-// Forward: out element k = in element k - in element k - 1 (`prev` in front of element 0), zigzagged if ZIGZAG.
-template <u32 W, bool ZIGZAG>
-RCX_DEV void rcx_predict_unit(const u32 (&in)[4 * W], typename RcxElem<W>::T prev, u32 (&out)[4 * W])
-{
-    typedef typename RcxElem<W>::T T;
-    T d[16];
-#pragma unroll
-    for (u32 k = 0; k < 16; ++k) {
-        const T e = rcx_elem_get<W>(in, k);
-        const T x = (T)(e - prev) & rcx_elem_mask<W>();
-        d[k] = ZIGZAG ? rcx_zigzag<W>(x) : x;
-        prev = e;
-    }
-    rcx_elems_put<W>(d, out);
 }
 
 // Inverse, first half: e[k] = the sum of the unit's (un-zigzagged) elements 0 .. k; e[15] is the unit's total.
@@ -135,20 +66,7 @@ RCX_DEV void rcx_unpredict_finish(const typename RcxElem<W>::T (&e)[16], typenam
 
 #if !defined(RCX_HOST_SIM)
 
-// W bytes at any byte address as an element, and back.
-template <class V>
-struct __attribute__((packed, aligned(1))) RcxAnyAlign {
-    V v;
-};
-
-template <u32 W>
-__device__ __forceinline__ typename RcxElem<W>::T rcx_load_elem(const u8* p)
-{
-    if constexpr (W == 2) return reinterpret_cast<const RcxAnyAlign<uint16_t>*>(p)->v;
-    else if constexpr (W == 4) return reinterpret_cast<const RcxAnyAlign<u32>*>(p)->v;
-    else return reinterpret_cast<const RcxAnyAlign<u64>*>(p)->v;
-}
-
+// An element to W bytes at any byte address.
 template <u32 W>
 __device__ __forceinline__ void rcx_store_elem(u8* p, typename RcxElem<W>::T v)
 {
@@ -157,98 +75,6 @@ __device__ __forceinline__ void rcx_store_elem(u8* p, typename RcxElem<W>::T v)
     else reinterpret_cast<RcxAnyAlign<u64>*>(p)->v = v;
 }
 
-// ===========================================================================
-// Forward.  rcx_planes_step's split with the difference between load and transpose.
-// ===========================================================================
-template <u32 W, bool ZIGZAG, bool GUARD>
-__device__ __forceinline__ void rcx_predict_split_step(const u8* __restrict__ src, u8* __restrict__ dst, u64 base, u64 total, u32 units, u64 nfull,
-                                                       u32 block, u32 m_last, u32 tid)
-{
-    typedef typename RcxElem<W>::T T;
-    constexpr u32 K = RCX_PLANES_U4 / W;
-    const u64 s0 = base / units;
-    const u32 u0 = (u32)(base - s0 * units);
-    u32 w[K][4 * W];
-    T prev[K];
-    u64 to[K];
-    u32 m[K];
-#pragma unroll
-    for (u32 j = 0; j < K; ++j) {
-        const u32 off = u0 + j * RCX_PLANES_THREADS + tid; // < 2^20 + 2048
-        const u32 ds = off / units;
-        const u64 s = s0 + ds;
-        const u32 u = off - ds * units;
-        m[j] = s < nfull ? block : m_last;
-        const u64 at = s * ((u64)W * block);
-        const u64 elements = at + (u64)u * (16u * W);
-        to[j] = at + 16ull * u; // plane p: + p * m
-        prev[j] = 0;            // the predictor restarts with the superblock
-        if (!GUARD || base + j * RCX_PLANES_THREADS + tid < total) {
-#pragma unroll
-            for (u32 i = 0; i < W; ++i) rcx_load16_any(src + elements + 16ull * i, &w[j][4 * i]);
-            if (u) prev[j] = rcx_load_elem<W>(src + elements - W);
-        }
-    }
-#pragma unroll
-    for (u32 j = 0; j < K; ++j) {
-        if (!GUARD || base + j * RCX_PLANES_THREADS + tid < total) {
-            u32 d[4 * W], o[4 * W];
-            rcx_predict_unit<W, ZIGZAG>(w[j], prev[j], d);
-            rcx_planes_unit<W, false>(d, o);
-#pragma unroll
-            for (u32 i = 0; i < W; ++i) rcx_store16<true>(dst + to[j] + (u64)i * m[j], U4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]});
-        }
-    }
-}
-
-template <u32 W, bool ZIGZAG>
-__global__ __launch_bounds__(RCX_PLANES_THREADS) void rcx_predict_split_k(const u8* __restrict__ src, u8* __restrict__ dst, u64 n, u32 block, u64 nfull)
-{
-    typedef typename RcxElem<W>::T T;
-    constexpr u32 STEP = RCX_PLANES_U4 / W * RCX_PLANES_THREADS; // units a workgroup takes at a time
-    const u64 super = (u64)W * block;                            // bytes of a whole superblock
-    const u32 r_last = (u32)(n - nfull * super);                 // bytes of the ragged last one, < W * block <= 2^27
-    const u32 m_last = r_last / W;
-    const u32 units = block >> 4, units_last = m_last >> 4;      // whole units of a whole superblock (>= 1), of the last one
-    const u64 total = nfull * units + units_last;
-    const u32 tid = threadIdx.x;
-
-    for (u64 base = (u64)blockIdx.x * STEP; base < total; base += (u64)gridDim.x * STEP) {
-        if (base + STEP <= total) rcx_predict_split_step<W, ZIGZAG, false>(src, dst, base, total, units, nfull, block, m_last, tid);
-        else rcx_predict_split_step<W, ZIGZAG, true>(src, dst, base, total, units, nfull, block, m_last, tid);
-    }
-
-    // What is left of every superblock behind its whole units, one byte a lane: (m % 16) elements, each against the element
-    // in front of it, then R % W tail bytes as they are.
-    const u32 rest = (block & 15u) * W;                          // of a whole superblock (0 for blocks that are multiples of 16)
-    const u32 rest_last = r_last - units_last * (16u * W);       // of the last one, < 17 * W
-    const u64 rest_whole = nfull * rest, rest_total = rest_whole + rest_last;
-    for (u64 t = (u64)blockIdx.x * RCX_PLANES_THREADS + tid; t < rest_total; t += (u64)gridDim.x * RCX_PLANES_THREADS) {
-        u64 s = nfull;
-        u32 j = (u32)(t - rest_whole), mm = m_last;
-        if (t < rest_whole) {
-            s = t / rest;
-            j = (u32)(t - s * rest);
-            mm = block;
-        }
-        const u64 at = s * super;
-        const u32 e0 = mm & ~15u, in_elements = (mm - e0) * W;
-        if (j < in_elements) {
-            const u32 e = e0 + j / W, p = j % W;
-            const u8* element = src + at + (u64)e * W;
-            const T here = rcx_load_elem<W>(element), front = e ? rcx_load_elem<W>(element - W) : (T)0;
-            const T d = (T)(here - front) & rcx_elem_mask<W>();
-            dst[at + (u64)p * mm + e] = (u8)((ZIGZAG ? rcx_zigzag<W>(d) : d) >> (8u * p));
-        } else {
-            const u64 i = at + (u64)mm * W + (j - in_elements);
-            dst[i] = src[i];
-        }
-    }
-}
-
-// ===========================================================================
-// Inverse.
-// ===========================================================================
 // Inclusive sum over the wave's 64 lanes; every lane takes part.
 template <class T>
 __device__ __forceinline__ T rcx_wave_scan(T x, u32 lane)

@@ -91,6 +91,21 @@ class Guarded:
 
 
 # ---- the device calls, every buffer guarded ----------------------------------------------------------------------------
+def run_filter(ctx, call, what, x, src_offset=0, dst_offset=0):
+    """One device call of a typed filter, call(src, dst), with both buffers guarded -> the n bytes written; the source is
+    unchanged, and nothing but the n bytes of the destination is written.  `what` names the call in a failure."""
+    n = len(x)
+    src = Guarded(n, src_offset, x, salt=1)
+    dst = Guarded(n, dst_offset, salt=2)
+    assert n == 0 or (src.view.data_ptr() % 16 == src_offset % 16 and dst.view.data_ptr() % 16 == dst_offset % 16)
+    call(src.view, dst.view)
+    assert ctx.sync_status(raise_on_error=False)[0] == rcx.OK
+    what = f"{what} n={n} offsets {src_offset}, {dst_offset}"
+    src.check(0, what + ": src")
+    dst.check(n, what + ": dst")
+    return dst.view.cpu().numpy()
+
+
 def _encode(ctx, data, block, src_offset, coder, dst_offset, invert):
     """-> (dst, offs, offsets np.uint64): the guarded destination and table after the call and its checks."""
     data = np.ascontiguousarray(data, dtype=np.uint8)

@@ -16,7 +16,7 @@ import pytest
 
 import planes_cases as pc
 from cpprcoder_amd import container, planes, rcx
-from gpu_support import CODERS, Guarded, ctx, oracle_decode_one  # noqa: F401
+from gpu_support import CODERS, Guarded, ctx, oracle_decode_one, run_filter  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,18 +36,9 @@ def bf16():
 
 
 def run(ctx, join, x, width, block, src_offset=0, dst_offset=0):
-    """One device call with both buffers guarded -> the n bytes written; the source is unchanged, and nothing but the n bytes
-    of the destination is written."""
-    n = len(x)
-    src = Guarded(n, src_offset, x, salt=1)
-    dst = Guarded(n, dst_offset, salt=2)
-    assert n == 0 or (src.view.data_ptr() % 16 == src_offset % 16 and dst.view.data_ptr() % 16 == dst_offset % 16)
-    (planes.join_device if join else planes.split_device)(ctx, src.view, width, block, dst.view)
-    assert ctx.sync_status(raise_on_error=False)[0] == rcx.OK
-    what = f"{'join' if join else 'split'} w={width} B={block} n={n} offsets {src_offset}, {dst_offset}"
-    src.check(0, what + ": src")
-    dst.check(n, what + ": dst")
-    return dst.view.cpu().numpy()
+    """gpu_support.run_filter of one plane call."""
+    fn = planes.join_device if join else planes.split_device
+    return run_filter(ctx, lambda src, dst: fn(ctx, src, width, block, dst), f"{'join' if join else 'split'} w={width} B={block}", x, src_offset, dst_offset)
 
 
 # ---- the kernel against numpy ----------------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ import pytest
 import planes_cases as pc
 import predict_cases as pr
 from cpprcoder_amd import container, predict, rcx
-from gpu_support import CODERS, Guarded, ctx, oracle_decode_one  # noqa: F401
+from gpu_support import CODERS, Guarded, ctx, oracle_decode_one, run_filter  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,18 +37,10 @@ def noise():
 
 
 def run(ctx, join, x, width, block, pred, src_offset=0, dst_offset=0):
-    """One device call with both buffers guarded -> the n bytes written; the source is unchanged, and nothing but the n bytes
-    of the destination is written."""
-    n = len(x)
-    src = Guarded(n, src_offset, x, salt=1)
-    dst = Guarded(n, dst_offset, salt=2)
-    assert n == 0 or (src.view.data_ptr() % 16 == src_offset % 16 and dst.view.data_ptr() % 16 == dst_offset % 16)
-    (predict.join_device if join else predict.split_device)(ctx, src.view, width, block, pred, dst.view)
-    assert ctx.sync_status(raise_on_error=False)[0] == rcx.OK
-    what = f"{'join' if join else 'split'} w={width} B={block} pred={pred} n={n} offsets {src_offset}, {dst_offset}"
-    src.check(0, what + ": src")
-    dst.check(n, what + ": dst")
-    return dst.view.cpu().numpy()
+    """gpu_support.run_filter of one predictor call."""
+    fn = predict.join_device if join else predict.split_device
+    return run_filter(ctx, lambda src, dst: fn(ctx, src, width, block, pred, dst), f"{'join' if join else 'split'} w={width} B={block} pred={pred}", x,
+                      src_offset, dst_offset)
 
 
 # ---- the kernels against numpy ----------------------------------------------------------------------------------------------
@@ -91,7 +83,7 @@ def test_eight_mebibytes_and_five_bytes(ctx, noise, width):
 
 @pytest.mark.parametrize("case", range(4))
 def test_more_superblocks_than_the_inverse_grid_has_waves(ctx, case):
-    waves = 32 * torch.cuda.get_device_properties(0).multi_processor_count  # predict_join_launch's grid
+    waves = 32 * torch.cuda.get_device_properties(0).multi_processor_count  # typed_launch's grid for the inverse with a predictor
     width, block, n = pr.looping_cases(waves)[case]
     assert -(-n // (width * block)) > waves
     x = np.random.RandomState(77 + case).randint(0, 256, n, dtype=np.uint8)

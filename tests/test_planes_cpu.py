@@ -69,7 +69,7 @@ def test_header_exports_and_library_agree():
     assert '#include "rcx.h"' in text
     # rcx.h itself is what it was: no new function, the same version
     assert len(rcx.EXPORTS) == 57 and not set(planes.EXPORTS) & set(rcx.EXPORTS) and rcx.lib().rcx_version() == 300
-    assert "rcx_planes.hpp" in build.HEADERS and "rcx_planes_api.hpp" in build.HEADERS
+    assert all(h in build.HEADERS for h in ("rcx_planes.hpp", "rcx_predict.hpp", "rcx_typed_api.hpp"))  # (one kernel template, one API file)
 
 
 # ---- the RCXT header -----------------------------------------------------------------------------------------------------------

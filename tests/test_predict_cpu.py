@@ -173,7 +173,7 @@ def test_header_exports_and_library_agree():
     # rcx.h and rcx_planes.h are what they were
     assert len(rcx.EXPORTS) == 57 and len(planes.EXPORTS) == 4 and rcx.lib().rcx_version() == 300
     assert not set(predict.EXPORTS) & (set(rcx.EXPORTS) | set(planes.EXPORTS))
-    assert "rcx_predict.hpp" in build.HEADERS and "rcx_predict_api.hpp" in build.HEADERS
+    assert all(h in build.HEADERS for h in ("rcx_planes.hpp", "rcx_predict.hpp", "rcx_typed_api.hpp"))
     assert any(h.endswith("rcx_predict.h") for h in build.HEADERS)
 
 

@@ -10,13 +10,18 @@ device source that only moves.  Every kernel is put into a class:
     differs anything else; the exit status is non-zero if there is one, or if the sets of kernels differ
 
     python tools/diag/kernel_diff.py before/rcx_api-hip-amdgcn-amd-amdhsa-gfx950.s after/rcx_api-hip-amdgcn-amd-amdhsa-gfx950.s
+
+--rename PATTERN REPLACEMENT (may be given more than once, applied in order): a regular expression substituted in the
+second file's text before anything is compared, for a change that renames kernels and is meant to do nothing else.
 """
 import re
 import sys
 
 
-def kernels(path):
+def kernels(path, renames=()):
     txt = open(path).read()
+    for pattern, replacement in renames:
+        txt = re.sub(pattern, replacement, txt)
     out = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", txt, re.S):
         name = m.group(1)
@@ -54,7 +59,14 @@ def classify(a, b):
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        if i + 2 >= len(args):
+            raise SystemExit("usage: kernel_diff.py BEFORE.s AFTER.s [--rename PATTERN REPLACEMENT]... [-v]")
+        renames.append((args[i + 1], args[i + 2]))
+        del args[i:i + 3]
+    a, b = kernels(args[0]), kernels(args[1], renames)
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     cls = {k: classify(a[k], b[k]) for k in sorted(set(a) & set(b))}
     moved, differ = [k for k in cls if cls[k] == "moved"], [k for k in cls if cls[k] == "differs"]
@@ -63,7 +75,7 @@ def main():
     for what, names in (("only before", only_a), ("only after", only_b), ("moved", moved), ("differs", differ)):
         for k in names:
             print(f"  {what}: {k}")
-    if "-v" in sys.argv[3:]:
+    if "-v" in args[2:]:
         for k in cls:
             print(f"  {cls[k]:8s}{k}")
     raise SystemExit(1 if only_a or only_b or differ else 0)

@@ -112,7 +112,7 @@ def main():
                      "split_over_scatter": round(plain["split"]["ms_median"] / yard["scatter"]["ms_median"], 3),
                      "join_over_scatter": round(plain["join"]["ms_median"] / yard["scatter"]["ms_median"], 3)})
         for name, _ in PREDS[1:]:
-            row = {"part": "fused", "kernel": "rcx_predict_split_k / rcx_predict_join_k", "predictor": name, "bytes": n, "block": BLOCK, "width": width,
+            row = {"part": "fused", "kernel": "rcx_planes_k<W, false, PRED> / rcx_predict_join_k", "predictor": name, "bytes": n, "block": BLOCK, "width": width,
                    "data": "uniform mt19937(12345)"}
             for what, coder in (("split", "encode"), ("join", "decode")):
                 s = row[what] = stats(ms[f"{what}_{name}_w{width}"], n)
