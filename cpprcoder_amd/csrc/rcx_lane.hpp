@@ -82,7 +82,11 @@ RCX_DEV u32 rcx_perm(u32 hi, u32 lo, u32 sel)
 }
 RCX_DEV u32 rcx_bswap(u32 x) { return __builtin_bswap32(x); }
 RCX_DEV void rcx_lds_inc(u32* p) { *p += 1; }
+#if defined(RCX_SIM_RCP) /* tests/sim/lane_sim.cpp: the rounded reciprocal moved by 0 or +-1 ulp, as v_rcp_f32 may */
+RCX_DEV float rcx_rcp(float x) { return RCX_SIM_RCP(1.0f / x); }
+#else
 RCX_DEV float rcx_rcp(float x) { return 1.0f / x; }
+#endif
 RCX_DEV bool rcx_any(bool p) { return p; }
 RCX_DEV u32 rcx_funnel_shr(u32 hi, u32 lo, u32 sh) { return (u32)(((((u64)hi) << 32) | lo) >> (sh & 31u)); }
 #define RCX_COLD inline
@@ -694,6 +698,75 @@ struct DecLane {
         return c;
     }
 };
+
+// ---------------------------------------------------------------------------
+// The static coder's table of one lane and the one-lane decoder's symbol step (rcx_static.hpp, rcx_dec_static_k).
+// The table is 257 dwords, dword-interleaved over the lanes: entry i of the lane at col[i * RCX_LANES].
+// ---------------------------------------------------------------------------
+struct StaticTable {
+    u32* col; // this lane's column
+    RCX_DEV u32 get(u32 i) const { return col[i * RCX_LANES]; }
+    RCX_DEV void set(u32 i, u32 v) const { col[i * RCX_LANES] = v; }
+    RCX_DEV void inc(u32 i) const { rcx_lds_inc(col + i * RCX_LANES); }
+    // cpprcoder.h:573-583: counts -> exclusive running sums, entry 256 = total
+    RCX_DEV u32 accumulate() const
+    {
+        u32 run = 0;
+        for (u32 i = 0; i < 256; ++i) {
+            const u32 c = get(i);
+            set(i, run);
+            run += c;
+        }
+        set(256, run);
+        return run;
+    }
+};
+
+// floor(low / t) for every low < 2^32, every 1 <= t < 2^32 and every rcx_rcp within 1 ulp of the correctly rounded
+// reciprocal.  The two conversions, the reciprocal (1.5 ulp from the true one) and the product each add a relative
+// error: 3 * 2^-23 in all, so the first estimate is off by up to low/t * 3 * 2^-23 + 1 (truncation) -- 1537 at the most,
+// 7 for the quotients below 2^24 that a valid stream has.  What that leaves of low is therefore within 1537 * t of 0, and
+// its own quotient by t, estimated the same way and rounded to nearest, is off by less than 0.5 + 0.001: the sum is
+// floor(low / t) or one more, which the last step settles (both ways, for good measure).  One estimate and a step of
+// +-1 alone is exact only for quotients below 2^21.
+RCX_DEV u32 rcx_static_target(u32 low, u32 t)
+{
+    const float r = rcx_rcp((float)t);
+    u64 q = (u64)((float)low * r);
+    const int64_t rest = (int64_t)low - (int64_t)(q * t);
+    q = (u64)((int64_t)q + (int64_t)__builtin_rintf((float)rest * r));
+    if (q * t > low) q -= 1;
+    else if (low - q * t >= t) q += 1;
+    return (u32)q;
+}
+
+// One symbol, cpprcoder.h:500-517.  find() (:521-535) returns the number of entries cum[1..255] that are <= target (the
+// table is non-decreasing), counted here in two levels of 15 probes; coarse[q] = cum[16 (q + 1)].  `bad`: a symbol of
+// count 0 was named.
+RCX_DEV u32 rcx_static_symbol(DecLane& dec, const StaticTable& tab, const u32 (&coarse)[15], const DivEntry& k, u32 total, bool& bad)
+{
+    const u32 t = rcx_div(dec.range, k);
+    u32 target = rcx_static_target(dec.low, t);
+    if (dec.low >= total * t) target = 0xFFFFFFFFu; // corrupt: past the table, find() says 255
+    u32 chunk = 0;
+#pragma unroll
+    for (u32 q = 0; q < 15; ++q) chunk += coarse[q] <= target ? 1u : 0u;
+    u32 c = chunk * 16;
+    u32 fine = 0;
+#pragma unroll
+    for (u32 q = 1; q < 16; ++q) fine += tab.get(c + q) <= target ? 1u : 0u;
+    c += fine;
+    if (c > 255u) c = 255u;
+    const u32 lo = tab.get(c), hi = tab.get(c + 1);
+    dec.low -= lo * t;
+    dec.range = (hi - lo) * t;
+    if (dec.range == 0) { // a symbol with count 0: corrupt; the reference runs dry and fails
+        dec.range = 1u << 31;
+        bad = true;
+    }
+    dec.pull();
+    return c;
+}
 
 // ---------------------------------------------------------------------------
 // One decoder step on plain state, for the resumable single-stream decoder (rcx_dstream_*): no input ring, the

@@ -20,25 +20,8 @@
 #define RCX_STATIC_HEADER 516u
 #define RCX_STATIC_LDS_DW (257 * RCX_LANES)
 
-struct StaticTable {
-    u32* col; // this lane's column
-    __device__ __forceinline__ u32 get(u32 i) const { return col[i * RCX_LANES]; }
-    __device__ __forceinline__ void set(u32 i, u32 v) const { col[i * RCX_LANES] = v; }
-    __device__ __forceinline__ void inc(u32 i) const { rcx_lds_inc(col + i * RCX_LANES); }
-    // cpprcoder.h:573-583: counts -> exclusive running sums, entry 256 = total
-    __device__ __forceinline__ u32 accumulate() const
-    {
-        u32 run = 0;
-        for (u32 i = 0; i < 256; ++i) {
-            const u32 c = get(i);
-            set(i, run);
-            run += c;
-        }
-        set(256, run);
-        return run;
-    }
-};
-
+// (StaticTable, the table of one lane, is in rcx_lane.hpp with the one-lane decoder's symbol step: the host lane simulator
+// of the tests compiles both.)
 
 // count() (cpprcoder.h:543-571) for the symbols [from, to) of every lane's block, with the order-dependent 16-bit
 // squeeze (:549-555): when a count is 0xFFFF or more BEFORE its increment, every non-zero count becomes
@@ -474,45 +457,13 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
     bool bad = false;
     u32 short_at = 0xFFFFFFFFu;
 
-    // One symbol, cpprcoder.h:500-517.  find() (:521-535) returns the number of entries cum[1..255] that
-    // are <= target (the table is non-decreasing), counted here in two levels of 15 probes.
-#define RCX_STATIC_SYMBOL(SYM)                                                                   \
-    {                                                                                            \
-        const u32 t_ = rcx_div(dec.range, k);                                                    \
-        /* target = low / t, exact: f32 estimate (|error| < 1 for quotients < 2^21) + correction */ \
-        u32 q_ = (u32)((float)dec.low * rcx_rcp((float)t_));                                     \
-        {                                                                                        \
-            const u64 prod_ = (u64)q_ * t_; /* t can be anything up to 2^32-1 here: 64-bit check */ \
-            if (prod_ > dec.low) q_ -= 1;                                                        \
-            else if (dec.low - prod_ >= t_) q_ += 1;                                             \
-        }                                                                                        \
-        if (dec.low >= total * t_) q_ = 0xFFFFFFFFu; /* corrupt: past the table, find() says 255 */ \
-        u32 chunk_ = 0;                                                                          \
-        _Pragma("unroll") for (u32 q = 0; q < 15; ++q) chunk_ += coarse[q] <= q_ ? 1u : 0u;      \
-        u32 c_ = chunk_ * 16;                                                                    \
-        u32 fine_ = 0;                                                                           \
-        _Pragma("unroll") for (u32 q = 1; q < 16; ++q) fine_ += tab.get(c_ + q) <= q_ ? 1u : 0u; \
-        c_ += fine_;                                                                             \
-        if (c_ > 255u) c_ = 255u;                                                                \
-        const u32 lo_ = tab.get(c_), hi_ = tab.get(c_ + 1);                                      \
-        dec.low -= lo_ * t_;                                                                     \
-        dec.range = (hi_ - lo_) * t_;                                                            \
-        if (dec.range == 0) { /* a symbol with count 0: corrupt; the reference runs dry and fails */ \
-            dec.range = 1u << 31;                                                                \
-            bad = true;                                                                          \
-        }                                                                                        \
-        dec.pull();                                                                              \
-        (SYM) = c_;                                                                              \
-    }
-
     if (full) {
         for (u32 i = 0; i < maxlen; i += 16) {
             u32 word[4] = {0, 0, 0, 0};
             dec.topup();
 #pragma unroll
             for (u32 s = 0; s < 16; ++s) {
-                u32 sym;
-                RCX_STATIC_SYMBOL(sym);
+                const u32 sym = rcx_static_symbol(dec, tab, coarse, k, total, bad); // (rcx_lane.hpp)
                 word[s >> 2] |= sym << (8 * (s & 3));
             }
             U4 o;
@@ -526,14 +477,11 @@ __global__ __launch_bounds__(64) void rcx_dec_static_k(const u8* __restrict__ co
         for (u32 i = 0; i < maxlen; ++i) {
             if ((i & 15u) == 0) dec.topup();
             if (i < len) {
-                u32 sym;
-                RCX_STATIC_SYMBOL(sym);
-                out[i] = (u8)sym;
+                out[i] = (u8)rcx_static_symbol(dec, tab, coarse, k, total, bad);
                 if (STREAM && short_at == 0xFFFFFFFFu && (bad || dec.taken() + (RCX_STATIC_HEADER - 3) > stream_len)) short_at = i;
             }
         }
     }
-#undef RCX_STATIC_SYMBOL
     // cpprcoder.h:506-509: running out of input inside the renormalisation is a failure
     if (STREAM) {
         if (lane == 0) track[0] = live ? short_at : 0u;

@@ -452,11 +452,10 @@ static uint8_t static_find(const static_table* t, uint32_t target)
     return (uint8_t)lo;
 }
 
-/* cpprcoder.h:375-458 */
-static int static_encode_stream(rco_stream* s, uint32_t n, const uint8_t* bytes)
+/* cpprcoder.h:375-458 behind count(): t holds the 256 counts */
+static int static_encode_counted(rco_stream* s, uint32_t n, const uint8_t* bytes, const static_table* tp)
 {
-    static_table t;
-    static_count(&t, n, bytes);
+    static_table t = *tp;
     uint32_t range = 0xFFFFFFFFu, low = 0, pending = 0, held = 0;
     uint8_t hdr[4] = {(uint8_t)n, (uint8_t)(n >> 8), (uint8_t)(n >> 16), (uint8_t)(n >> 24)};
     if (rco_stream_write(s, 4, hdr) <= 0) return 0;
@@ -509,10 +508,25 @@ static int static_encode_stream(rco_stream* s, uint32_t n, const uint8_t* bytes)
     return 0 < rco_stream_write(s, 4, tail);
 }
 
+/* cpprcoder.h:375-458 */
+static int static_encode_stream(rco_stream* s, uint32_t n, const uint8_t* bytes)
+{
+    static_table t;
+    static_count(&t, n, bytes);
+    return static_encode_counted(s, n, bytes, &t);
+}
+
 /* cpprcoder.h:460-519.  Deviation, for safety only: a corrupt table whose
  * total is 0, or a step of 0, divides by zero in the reference; here it
  * returns false. */
+static int static_decode_traced(rco_stream* s, uint32_t size, const uint8_t* bytes, uint32_t* trace_low, uint32_t* trace_range);
 static int static_decode_stream(rco_stream* s, uint32_t size, const uint8_t* bytes)
+{
+    return static_decode_traced(s, size, bytes, NULL, NULL);
+}
+
+/* The same; trace_low[i], trace_range[i] (where given) = low and range in front of symbol i. */
+static int static_decode_traced(rco_stream* s, uint32_t size, const uint8_t* bytes, uint32_t* trace_low, uint32_t* trace_range)
 {
     static_table t;
     uint32_t range = 0xFFFFFFFFu, low;
@@ -532,6 +546,8 @@ static int static_decode_stream(rco_stream* s, uint32_t size, const uint8_t* byt
     bytes += 5;
     if (t.cum[256] == 0) return 0;
     for (uint32_t i = 0; i < n; ++i) {
+        if (trace_low) trace_low[i] = low;
+        if (trace_range) trace_range[i] = range;
         uint32_t step = range / t.cum[256];
         if (step == 0) return 0;
         uint8_t c = static_find(&t, low / step);
@@ -552,6 +568,37 @@ int rco_static_encode(const uint8_t* src, uint32_t n, uint8_t* dst, uint64_t dst
     rco_stream s;
     rco_stream_init_cap(&s, (int32_t)dst_cap);
     int ok = static_encode_stream(&s, n, src);
+    if (out_size) *out_size = (uint64_t)s.size;
+    if (dst) memcpy(dst, s.buffer, (size_t)((uint64_t)s.size < dst_cap ? (uint64_t)s.size : dst_cap));
+    rco_stream_free(&s);
+    return ok;
+}
+
+/* rco_static_encode with count() replaced by the caller's table: counts[c] <= 65535, and >= 1 for every byte value
+ * that occurs in src (else 0 is returned).  The header holds those counts and n, so a decoder meets a total that the
+ * block's own histogram need not have.  trace_low / trace_range (each n entries, or NULL): the decoder's low and range
+ * in front of every symbol of the stream made. */
+int rco_static_encode_table(const uint32_t* counts, const uint8_t* src, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_size,
+                            uint32_t* trace_low, uint32_t* trace_range)
+{
+    static_table t;
+    for (int i = 0; i < 256; ++i) {
+        if (counts[i] > 0xFFFFu) return 0;
+        t.cum[i] = counts[i];
+    }
+    t.cum[256] = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (t.cum[src[i]] == 0) return 0;
+    rco_stream s;
+    rco_stream_init_cap(&s, (int32_t)dst_cap);
+    int ok = static_encode_counted(&s, n, src, &t);
+    if (ok && (trace_low || trace_range)) {
+        rco_stream back;
+        rco_stream_init_cap(&back, (int32_t)n);
+        ok = static_decode_traced(&back, (uint32_t)s.size, s.buffer, trace_low, trace_range) && (uint32_t)back.size == n &&
+             memcmp(back.buffer, src, n) == 0;
+        rco_stream_free(&back);
+    }
     if (out_size) *out_size = (uint64_t)s.size;
     if (dst) memcpy(dst, s.buffer, (size_t)((uint64_t)s.size < dst_cap ? (uint64_t)s.size : dst_cap));
     rco_stream_free(&s);

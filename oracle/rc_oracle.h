@@ -102,6 +102,10 @@ rco_result rco_adaptive_decode(const uint8_t* comp, uint64_t comp_size, uint8_t*
 /* Static (two-pass) coder, RangeEncoder<T>::encode/decode (:375-519). 1 = true. */
 int rco_static_encode(const uint8_t* src, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_size);
 int rco_static_decode(const uint8_t* comp, uint32_t comp_size, uint8_t* dst, uint64_t dst_cap, uint64_t* out_size);
+/* rco_static_encode with count() replaced by the caller's 256 counts (each <= 65535, >= 1 for every byte that occurs);
+ * trace_low / trace_range (n entries each, or NULL): the decoder's low and range in front of every symbol. */
+int rco_static_encode_table(const uint32_t* counts, const uint8_t* src, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_size,
+                            uint32_t* trace_low, uint32_t* trace_range);
 
 /* ------------------------------------------------------------------ */
 /* Many independent blocks: block b = src[b*block, min(n,(b+1)*block)),*/

@@ -70,6 +70,10 @@ class Checker:
         self._senc.restype, self._senc.argtypes = C.c_int, [u8p, C.c_uint32, u8p, C.c_uint64, u64p]
         self._sdec = getattr(L, p + "static_decode")
         self._sdec.restype, self._sdec.argtypes = C.c_int, [u8p, C.c_uint32, u8p, C.c_uint64, u64p]
+        self._senct = getattr(L, p + "static_encode_table", None)  # the restatement only
+        if self._senct is not None:
+            self._senct.restype = C.c_int
+            self._senct.argtypes = [u32p, u8p, C.c_uint32, u8p, C.c_uint64, u64p, u32p, u32p]
         self._ebr = getattr(L, p + "encode_block_range")
         self._ebr.restype = C.c_int
         self._ebr.argtypes = [u8p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u8p, C.c_uint64, u32p, C.c_int]
@@ -183,6 +187,24 @@ class Checker:
         cap = (len(src) + len(src) // 32 + 2048) if sink_capacity is None else int(sink_capacity)
         ok, out, size = self._oneshot(self._senc, src, cap)
         return bool(ok), out, size
+
+    def static_encode_table(self, counts, data, trace=False):
+        """static_encode with count() replaced by the caller's 256 counts (each <= 65535, >= 1 for every byte that occurs)
+        -> the stream, or (stream, low, range) with trace: the decoder's low and range in front of every symbol."""
+        src = _u8(data)
+        tab = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert tab.shape == (256,)
+        cap = len(src) + len(src) // 32 + 2048
+        out = np.zeros(cap + 32, dtype=np.uint8)
+        low = np.zeros(len(src) if trace else 0, dtype=np.uint32)
+        rng = np.zeros(len(src) if trace else 0, dtype=np.uint32)
+        size = C.c_uint64()
+        ok = self._senct(tab.ctypes.data, src.ctypes.data, len(src), out.ctypes.data, cap, C.byref(size),
+                         low.ctypes.data if trace else None, rng.ctypes.data if trace else None)
+        if not ok or size.value > cap:
+            raise RuntimeError("static_encode_table: a count past 65535, a byte of count 0, or a stream that does not decode")
+        stream = out[: size.value].copy()
+        return (stream, low, rng) if trace else stream
 
     def static_decode(self, comp, sink_capacity):
         ok, out, size = self._oneshot(self._sdec, comp, sink_capacity)

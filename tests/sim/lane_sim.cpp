@@ -9,6 +9,11 @@
 #include <cstring>
 #include <vector>
 
+// rcx_rcp on the device is v_rcp_f32, 1 ulp: the host's rounded 1 / x is moved by sim_rcp_ulp (0, +1, -1) ulp
+static int sim_rcp_ulp = 0;
+static inline float sim_rcp_moved(float r) { return sim_rcp_ulp == 0 ? r : __builtin_nextafterf(r, sim_rcp_ulp > 0 ? 2.0f : 0.0f); }
+#define RCX_SIM_RCP(r) sim_rcp_moved(r)
+
 #include "../../cpprcoder_amd/csrc/rcx_divtab.hpp"
 #include "../../cpprcoder_amd/csrc/rcx_bwt_tie.hpp"
 
@@ -359,6 +364,57 @@ uint64_t sim_decode_blocks(const uint8_t* comp, const uint64_t* offsets, uint64_
         if (d.taken() > s1 - s0) return b + 1;
     }
     return 0;
+}
+
+// rcx_static_target (rcx_lane.hpp) against the true quotient, with the reciprocal moved by `ulp` -> how many of the n
+// pairs differ; first[0] = the index of the first that does.
+uint64_t sim_static_target_check(const uint32_t* lows, const uint32_t* ts, uint64_t n, int ulp, uint64_t* first)
+{
+    sim_rcp_ulp = ulp;
+    uint64_t wrong = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        if (rcx_static_target(lows[i], ts[i]) != lows[i] / ts[i]) {
+            if (wrong == 0 && first) first[0] = i;
+            ++wrong;
+        }
+    sim_rcp_ulp = 0;
+    return wrong;
+}
+
+// One static stream (cpprcoder.h:460-519) of `len` symbols through rcx_dec_static_k's steps: the table from the header,
+// low from the bytes behind it, rcx_static_symbol per symbol.  -> 0, or 1 if the stream is not one the kernel would take,
+// 2 if it ran past its input or named a symbol of count 0.
+uint32_t sim_static_decode_block(const uint8_t* comp, uint64_t comp_size, uint32_t len, uint8_t* dst, uint32_t lane, int ulp)
+{
+    if (comp_size < 516 + 5) return 1;
+    const uint32_t declared = (u32)comp[0] | ((u32)comp[1] << 8) | ((u32)comp[2] << 16) | ((u32)comp[3] << 24);
+    if (declared != len) return 1;
+    std::vector<u32> lds(257 * RCX_LANES + RCX_RING_DW * RCX_LANES);
+    StaticTable tab{lds.data() + lane};
+    for (u32 i = 0; i < 256; ++i) tab.set(i, (u32)comp[4 + 2 * i] | ((u32)comp[5 + 2 * i] << 8));
+    const u32 total = tab.accumulate();
+    if (total == 0) return 1;
+    std::vector<uint8_t> pad(comp_size + 64); // (the aligned 16-byte loads: see sim_decode_blocks)
+    uint8_t* base = pad.data();
+    while (((uintptr_t)base & 15) != 0) ++base;
+    base += 16 + 7;
+    memcpy(base, comp, comp_size);
+    DecLane dec;
+    const u8* h = base + 516 - 3; // as the kernel: begin() 3 bytes early, low = the 4 bytes behind the lead-in
+    dec.begin(h, base + comp_size, lds.data() + 257 * RCX_LANES + lane);
+    dec.low = ((u32)h[4] << 24) | ((u32)h[5] << 16) | ((u32)h[6] << 8) | (u32)h[7];
+    dec.range = 0xFFFFFFFFu;
+    const DivEntry k = rcx_make_div_entry(total);
+    u32 coarse[15];
+    for (u32 q = 0; q < 15; ++q) coarse[q] = tab.get(16 * (q + 1));
+    bool bad = false;
+    sim_rcp_ulp = ulp;
+    for (uint32_t i = 0; i < len; ++i) {
+        if ((i & 15u) == 0) dec.topup();
+        dst[i] = (uint8_t)rcx_static_symbol(dec, tab, coarse, k, total, bad);
+    }
+    sim_rcp_ulp = 0;
+    return (bad || dec.taken() + (516 - 3) > comp_size) ? 2 : 0;
 }
 
 // The row index of a periodic 32 KiB block (period p, a power of two), by the replay of the reference's sort that the

@@ -35,6 +35,10 @@ def sim():
     L.sim_counters.restype, L.sim_counters.argtypes = None, [C.c_void_p, C.c_int]
     L.sim_stream_encode_long.restype, L.sim_stream_encode_long.argtypes = C.c_uint32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
     L.sim_stream_decode_long.restype, L.sim_stream_decode_long.argtypes = C.c_uint32, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+    L.sim_static_target_check.restype = C.c_uint64
+    L.sim_static_target_check.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    L.sim_static_decode_block.restype = C.c_uint32
+    L.sim_static_decode_block.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int]
     return L
 
 
@@ -212,3 +216,73 @@ def test_wave_wide_tie_replay_moves_every_row_like_the_scalar_one(sim):
             assert sim.sim_bwt_tie_compare(w.ctypes.data, p, depth) == 0, (p, depth, word[:8])
             checked += 1
     assert checked >= 150
+
+
+# ---------------------------------------------------------------------------
+# The one-lane static decoder's symbol step (rcx_static_target, rcx_static_symbol in csrc/rcx_lane.hpp), with the host's
+# reciprocal moved by 0, +1 and -1 ulp: what v_rcp_f32's stated accuracy allows
+# ---------------------------------------------------------------------------
+ULPS = (0, 1, -1)
+
+
+def target_errors(sim, low, t, ulp):
+    low, t = np.ascontiguousarray(low, np.uint32), np.ascontiguousarray(t, np.uint32)
+    first = C.c_uint64(0)
+    wrong = sim.sim_static_target_check(low.ctypes.data, t.ctypes.data, len(low), ulp, C.byref(first))
+    return int(wrong), (int(low[first.value]), int(t[first.value])) if wrong else None
+
+
+def test_static_target_is_the_quotient(sim):
+    """rcx_static_target(low, t) == low // t on the decoder states of every crafted block (tests/static_cases.py), on 2^24
+    seeded pairs with quotients up to 2^24 and on the multiples of t around quotients of 2^21 ... 2^24, and on pairs of any
+    size.  The arithmetic it replaced (static_cases.parent_estimate: the same check fails on it, with the counts
+    stated there and asserted by tests/test_static_cases_cpu.py) gets 353 951 of the near-flat table's 16.7 M targets wrong
+    with the exactly rounded reciprocal."""
+    import static_cases as sc
+    for name, counts in sc.tables().items():
+        total = np.uint32(int(counts.sum()))
+        for b, (_, _, low, rng) in enumerate(sc.crafted_blocks(name, trace=True)):
+            for ulp in ULPS:
+                assert target_errors(sim, low, rng // total, ulp) == (0, None), (name, b, ulp)
+    rs = np.random.RandomState(11)
+    t = rs.randint(1, (1 << 12) + 1, 1 << 24).astype(np.uint32)
+    quotient = rs.randint(0, 1 << 24, 1 << 24) % np.minimum(1 << 24, (1 << 32) // t.astype(np.int64))  # low < 2^24 t, and < 2^32
+    low = (quotient * t.astype(np.int64) + rs.randint(0, 1 << 12, 1 << 24) % t).astype(np.uint32)
+    edges_t = np.concatenate([np.arange(1, 258), rs.randint(1, 1 << 8, 2000)]).astype(np.uint64)
+    ks = np.concatenate([np.arange(k - 40, k + 40) for k in (1 << 21, 1 << 22, 1 << 23, (1 << 24) - 40)]).astype(np.uint64)
+    edge_low = (ks[None, :, None] * edges_t[:, None, None] + np.array([-1, 0, 1], np.int64)[None, None, :].astype(np.uint64))
+    edge_t = np.broadcast_to(edges_t[:, None, None], edge_low.shape)
+    keep = edge_low < (1 << 32)
+    # any low and t below 2^32, small and large quotients alike
+    any_t = np.concatenate([rs.randint(1, 1 << 32, 1 << 20, dtype=np.uint64) >> rs.randint(0, 32, 1 << 20).astype(np.uint64), [1, 1, 0xFFFFFFFF, 0xFFFFFFFF]])
+    any_t = np.maximum(any_t, 1).astype(np.uint32)
+    any_low = np.concatenate([rs.randint(0, 1 << 32, 1 << 20, dtype=np.uint64), [0xFFFFFFFF, 0, 0xFFFFFFFF, 0xFFFFFFFE]]).astype(np.uint32)
+    for ulp in ULPS:
+        assert target_errors(sim, low, t, ulp) == (0, None), ulp
+        assert target_errors(sim, edge_low[keep].astype(np.uint32), edge_t[keep].astype(np.uint32), ulp) == (0, None), ulp
+        assert target_errors(sim, any_low, any_t, ulp) == (0, None), ulp
+
+
+def static_decode(sim, stream, n, lane, ulp):
+    comp = np.ascontiguousarray(stream, np.uint8)
+    out = np.zeros(n, np.uint8)
+    return sim.sim_static_decode_block(comp.ctypes.data, len(comp), n, out.ctypes.data, lane, ulp), out
+
+
+def test_static_block_decode_through_the_symbol_step(sim, oracle):
+    """The sim's static decoder -- DecLane's input ring and rcx_static_symbol, as rcx_dec_static_k runs them -- returns
+    every crafted block, and on the aimed streams (a low on the targets that the earlier arithmetic got wrong) what the
+    oracle returns, whichever way the reciprocal is rounded."""
+    import static_cases as sc
+    for name in sc.tables():
+        for b, (data, stream) in enumerate(sc.crafted_blocks(name)):
+            ulp = ULPS[b % 3] if b >= 3 else None
+            for u in (ULPS if ulp is None else (ulp,)):  # the first three blocks of a table under every perturbation
+                st, out = static_decode(sim, stream, len(data), (7 * b) % 64, u)
+                assert st == 0 and np.array_equal(out, data), (name, b, u)
+        for aimed_at in ULPS:
+            for s in sc.aimed_streams(name, aimed_at):
+                ok, want, _ = oracle.static_decode(s, 4096)
+                for u in ULPS:
+                    st, out = static_decode(sim, s, 4096, 5, u)
+                    assert ok and st == 0 and out.tobytes() == want, (name, aimed_at, u)
