@@ -2,8 +2,8 @@
 the device calls wrapped in them, the comparisons with the oracle that most tests make, the launch shapes restated with
 the block counts at which they change, and damaged streams.
 
-A test file imports what it needs from here (the fixture by name: `from gpu_support import ctx  # noqa: F401`, one
-context per importing module), never from another test file.  tests/test_support_cpu.py holds Guarded, knobs, chunk_blocks,
+A test file imports what it needs from here (a fixture by name: `from gpu_support import ctx  # noqa: F401`, or
+`bwt_ctx as ctx` for the block sort in both rank forms; one context per importing module), never from another test file.  tests/test_support_cpu.py holds Guarded, knobs, chunk_blocks,
 shape_edges and the two comparisons to their contracts on CPU tensors.  Nothing here reads /root/reference.
 """
 import contextlib
@@ -56,6 +56,19 @@ def ctx():
     c = rcx.Context(0)
     yield c
     c.close()
+
+
+@pytest.fixture(scope="module", params=["ballot", "atomic"])
+def bwt_ctx(request):
+    """The block-sort tests' context (`from gpu_support import bwt_ctx as ctx  # noqa: F401`): every test that takes it runs
+    in both forms of the counting pass's rank (csrc/rcx_bwt.hpp): with ballots -- the default, documented behaviour only
+    -- and with one returning LDS atomic per key, which a caller opts into with RCX_BWT_MATCH=atomic (read at the
+    context's first block-sort call, so it stays set while the context lives)."""
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    with knobs({"RCX_BWT_MATCH": request.param}):
+        c = rcx.Context(0)
+        yield c
+        c.close()
 
 
 # ---- guarded buffers ---------------------------------------------------------------------------------------------------

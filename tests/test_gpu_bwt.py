@@ -11,26 +11,13 @@ import pytest
 import bwt_cases
 import oracle_lib
 from cpprcoder_amd import workloads
-from gpu_support import knobs
+from gpu_support import bwt_ctx as ctx  # noqa: F401  (both rank forms)
 from oracle_lib import sha
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
 BLOCK, ENCODED = bwt_cases.BLOCK, bwt_cases.ENCODED
-
-
-@pytest.fixture(scope="module", params=["ballot", "atomic"])
-def ctx(request):
-    """Every test of this file runs in both forms of the counting pass's rank (csrc/rcx_bwt.hpp): with ballots -- the
-    default, documented behaviour only -- and with one returning LDS atomic per key, which a caller opts into with
-    RCX_BWT_MATCH=atomic (read at the context's first block-sort call, so it stays set while the context lives)."""
-    from cpprcoder_amd import rcx
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    with knobs({"RCX_BWT_MATCH": request.param}):
-        c = rcx.Context(0)
-        yield c
-        c.close()
 
 
 @pytest.fixture(scope="module")

@@ -9,6 +9,7 @@ import pytest
 
 import agreement_cases
 import bwt_cases
+import bwt_inverse_cases
 from cpprcoder_amd import workloads
 from oracle_lib import sha
 
@@ -81,3 +82,18 @@ def test_reference_build_agrees(reference, oracle, inputs):
     live = reference is not None and reference.bwt is not None
     agreement_cases.agree(agreement_cases.stored("bwt"), agreement_cases.bwt(oracle, inputs),
                           agreement_cases.bwt(reference, inputs) if live else None)
+
+
+def test_reference_build_walks_the_inverse_cases_as_the_oracle_does(reference, oracle):
+    """BlkSort::decode on the blocks of tests/bwt_inverse_cases.py -- short cycles, fixed points, one piece of 31 745 rows,
+    every row below 32768 -- where oracle/_ref/libblksort_ref.so is present: the oracle's inverse is the reference's on
+    these too, not only on the arbitrary bytes and transforms above."""
+    if reference is None or reference.bwt is None:
+        pytest.skip("the reference build (oracle/_ref/libblksort_ref.so) is not here")
+    for family, items in bwt_inverse_cases.all_cases().items():
+        enc = np.concatenate([blk for _, blk in items])
+        assert all(bwt_inverse_cases.split(blk)[1] < bwt_cases.BLOCK for _, blk in items), family
+        mine, theirs = oracle.bwt_decode(enc, threads=4), reference.bwt_decode(enc, threads=4)
+        for i, (name, _) in enumerate(items):
+            at = slice(i * bwt_cases.BLOCK, (i + 1) * bwt_cases.BLOCK)
+            assert np.array_equal(mine[at], theirs[at]), name
