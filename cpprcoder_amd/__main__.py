@@ -1,6 +1,6 @@
 """python -m cpprcoder_amd c|d|t ...  -- compress / decompress / test files with the MI355X block coder.
 
-    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag]] [--crc]
+    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag|auto]] [--crc]
                               [--static | --coder adaptive|static|rans|rans8] IN OUT
                                                                IN -> RCXB container (cpprcoder_amd/container.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
@@ -12,6 +12,9 @@
                                                                timestamps, samples): each becomes its difference to the
                                                                one in front first, zigzag for differences of both signs
                                                                (include/rcx_predict.h); unsorted data gets worse by it;
+                                                               auto: the one that the order-0 cost of the split text says
+                                                               pays off by 1/64 or more, else none (include/rcx_stats.h);
+                                                               the line printed names the choice;
                                                                --crc: a CRC-32 per block goes into the container
     python -m cpprcoder_amd d [--no-verify] IN OUT             container (RCXB or RCXT, told apart by the magic; an RCXI
                                                                container holds items, not a file) -> original bytes.
@@ -19,7 +22,7 @@
                                                                is verified: on a mismatch the bad block is named on
                                                                stderr, the exit status is 1 and OUT is not written
                                                                (--no-verify: write what the decoder produced)
-    python -m cpprcoder_amd t [--crc] [--planes W [--predict delta|zigzag]] FILE...
+    python -m cpprcoder_amd t [--crc] [--planes W [--predict delta|zigzag|auto]] FILE...
                                                                the reference harness's row per file
                                                                (|file|ratio|encode|decode|, test/main.cpp:346-356):
                                                                pack, unpack, compare, times incl. PCIe copies
@@ -30,7 +33,7 @@ import time
 
 
 CODERS = ("adaptive", "static", "rans", "rans8")  # include/rcx.h: RCX_CODER_*
-PREDICTORS = ("delta", "zigzag")                  # include/rcx_predict.h: RCX_PRED_DELTA, RCX_PRED_ZIGZAG
+PREDICTORS = ("delta", "zigzag", "auto")          # include/rcx_predict.h: RCX_PRED_DELTA, RCX_PRED_ZIGZAG; auto: container.pick_predictor
 
 
 class _Parser(argparse.ArgumentParser):
@@ -92,12 +95,18 @@ def main(argv=None) -> int:
             raise container.ContainerError("an RCXI container holds items, not one file: container.unpack_items()")
         return container.unpack(blob, ctx, verify=verify)
 
+    def chosen(blob):
+        """What --predict auto took, for the line printed: the container itself does not say that it was measured."""
+        if getattr(a, "predict", None) != "auto":
+            return ""
+        return " predict=" + ("none", "delta", "zigzag")[container.parse_typed(blob)["pred"]]
+
     try:
         if a.cmd == "c":
             data = open(a.src, "rb").read()
             blob = pack(data)
             open(a.dst, "wb").write(blob)
-            print(f"{a.src}: {len(data)} -> {len(blob)} bytes ({len(blob) / max(len(data), 1):.6f})")
+            print(f"{a.src}: {len(data)} -> {len(blob)} bytes ({len(blob) / max(len(data), 1):.6f})" + chosen(blob))
         elif a.cmd == "d":
             try:
                 out = unpack(open(a.src, "rb").read(), verify=not a.no_verify)
@@ -119,7 +128,7 @@ def main(argv=None) -> int:
                 t2 = time.perf_counter()
                 ok = back == data
                 bad += not ok
-                print(f"|{path}|{len(blob) / max(len(data), 1):.6f}|{(t1 - t0) * 1e6:.0f}|{(t2 - t1) * 1e6:.0f}|" + ("" if ok else " MISMATCH"))
+                print(f"|{path}|{len(blob) / max(len(data), 1):.6f}|{(t1 - t0) * 1e6:.0f}|{(t2 - t1) * 1e6:.0f}|" + chosen(blob) + ("" if ok else " MISMATCH"))
             return 1 if bad else 0
     finally:
         ctx.close()

@@ -69,6 +69,13 @@ unpack_typed_range(blob, start, stop) decodes the blocks of the superblocks that
 as a buffer of its own: the transform of a span from one superblock border to another, or to n, is the transform of the
 span taken alone.  A predictor (pack_typed(..., predict="delta" | "zigzag"): for integers whose differences are small) is
 opt-in and restarts in every superblock, so all of that holds with it; without one a container is byte for byte version 1.
+
+pack_typed(..., predict="auto") measures instead of asking (include/rcx_stats.h; cpprcoder_amd/stats.py).  For each of none,
+delta and zigzag the split text's order-0 cost is C_p = the sum of the blocks' costs -- what an order-0 coder with one model a
+block will make of it, to within a few percent.  The rule (pick_predictor): a predictor is a candidate only if it earns at
+least 1/64, 64 * C_p < 63 * C_none; the cheaper candidate is taken, delta on a tie; without a candidate, none.  The margin
+keeps data that no predictor helps on version 1: uniform bytes at 4 KiB blocks would otherwise take delta for 0.002 %.  The
+container is byte for byte what predict=<the choice> writes, and nothing in it records that the choice was measured.
 """
 import struct
 
@@ -88,6 +95,7 @@ TYPED_MAGIC = b"RCXT"
 TYPED_VERSION = 1
 TYPED_VERSION_PRED = 2  # the same layout + the predictor at byte 29; only with a predictor
 PREDICTORS = {None: 0, "delta": 1, "zigzag": 2}  # include/rcx_predict.h: RCX_PRED_*
+AUTO = "auto"  # pack_typed(predict=AUTO): measured, see pick_predictor; never in a container
 _TYPED_FIXED = struct.Struct("<4sBBHIQQB7s")
 WIDTHS = (2, 4, 8)
 
@@ -484,15 +492,43 @@ def _typed_source(data, width):
     return src, width
 
 
+def pick_predictor(c_none: int, c_delta: int, c_zigzag: int):
+    """The rule of predict="auto" on the three costs (any one unit) -> None, "delta" or "zigzag": the cheaper of the
+    predictors that earn at least 1/64 of the cost without one, delta on a tie; None if neither does."""
+    best = None
+    for name, c in (("delta", int(c_delta)), ("zigzag", int(c_zigzag))):
+        if 64 * c < 63 * int(c_none) and (best is None or c < best[1]):
+            best = (name, c)
+    return best[0] if best else None
+
+
+def _measured_predictor(ctx, d_src, width: int, block: int, nblocks: int, d_split):
+    """-> (the rule's pick, the predictor whose split text d_split holds now).  Three splits into d_split, a statistics pass
+    over each (costs only), three sums in one download."""
+    import torch
+    from . import predict as predictor, stats
+    d_cost = torch.empty(3 * nblocks, dtype=torch.int64, device="cuda")
+    for pred in (0, 1, 2):
+        predictor.split_device(ctx, d_src, width, block, pred, d_split)
+        stats.blocks_device(ctx, d_split, block, None, d_cost[pred * nblocks: (pred + 1) * nblocks])
+    totals = [int(v) for v in d_cost.view(3, nblocks).sum(dim=1).cpu()]  # (a block's cost is below 2^45)
+    return pick_predictor(*totals), 2
+
+
 def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False, predict=None) -> bytes:
     """data: bytes, a numpy array or a contiguous torch tensor (CPU or GPU) -> an RCXT container.  width=None: the
     element size of the array or tensor.  predict=None, "delta" or "zigzag": the predictor of include/rcx_predict.h in front of
-    the filter, for integers whose differences are small (never chosen for the caller: unsorted data gets worse by it).  One
-    upload (none for a GPU tensor), then split, encode and, with checksum=True, the CRC-32 of every block of the split text,
-    all with the device calls."""
-    if not (predict is None or isinstance(predict, str)) or predict not in PREDICTORS:
-        raise ContainerError(f"a predictor is None, 'delta' or 'zigzag', not {predict!r}")
-    pred = PREDICTORS[predict]
+    the filter, for integers whose differences are small (unsorted data gets worse by it).  predict="auto": the one the
+    rule in this module's docstring picks from the measured order-0 costs, or none; the container is the one that choice
+    given by name writes.  That costs up to four splits and three statistics passes where a named choice costs one split:
+    measured on a GiB of sorted int64 keys at 64 KiB blocks, 2.33 ms for the decision beside 4.86 ms for the adaptive
+    encode that follows, 48 % of it (profiles/r08_stats_rate.jsonl).  One upload (none for a GPU
+    tensor), then split, encode and, with checksum=True, the CRC-32 of every block of the split text, all with the device
+    calls."""
+    auto = isinstance(predict, str) and predict == AUTO
+    if not auto and (not (predict is None or isinstance(predict, str)) or predict not in PREDICTORS):
+        raise ContainerError(f"a predictor is None, 'delta', 'zigzag' or 'auto', not {predict!r}")
+    pred = 0 if auto else PREDICTORS[predict]  # (nothing to measure in an empty buffer: none, version 1)
     src, width = _typed_source(data, width)
     import torch
     from . import predict as predictor, rcx
@@ -507,7 +543,12 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
         d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
         d_dst = torch.empty(rcx.encode_bound(n, block, coder), dtype=torch.uint8, device="cuda")
         d_offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
-        predictor.split_device(ctx, d_src, width, block, pred, d_split)  # (no predictor: the plane filter's own kernel)
+        held = None  # the predictor whose split text d_split holds
+        if auto:
+            choice, held = _measured_predictor(ctx, d_src, width, block, nblocks, d_split)
+            pred = PREDICTORS[choice]
+        if held != pred:
+            predictor.split_device(ctx, d_src, width, block, pred, d_split)  # (no predictor: the plane filter's own kernel)
         ctx.encode_blocks_device(d_split, block, d_dst, d_offs, coder=coder)
         crcs = None
         if checksum:

@@ -12,6 +12,7 @@
 //   rcx_mc.hpp           the multi-wave range encoders' machinery + the adaptive one
 //   rcx_static.hpp, rcx_rans.hpp, rcx_bwt.hpp   the static range coder, the rANS coders, the block sort
 //   rcx_crc.hpp          CRC-32 per block or item, stored or verified
+//   rcx_stats.hpp        byte counts and order-0 cost per block or item
 //   rcx_planes.hpp       the byte-plane filter for typed data, split and join
 //
 // Roofline class: HBM-bound integer/byte work, no MFMA.  What actually bounds the
@@ -135,4 +136,5 @@ __global__ __launch_bounds__(256) void rcx_scatter_k(const u8* __restrict__ slot
 #include "rcx_rans.hpp"
 #include "rcx_bwt.hpp"
 #include "rcx_crc.hpp"
+#include "rcx_stats.hpp"
 #include "rcx_planes.hpp"
