@@ -61,6 +61,16 @@ __device__ __forceinline__ u32 rcx_oct_excl_scan(u32 x, u32 m1, u32 m2, u32 m4)
 //   round 2 is the same over the node's 16 counts, and the unsigned maximum of the x over the
 //   quad is the (wrapped) distance to the smallest bound above, so the new range count*t is
 //   min - max (mod 2^32): cum(c+1)*t - cum(c)*t, no multiply, no select of the count.
+//   The counts are negated in LDS too (-1 at the start).  With P = minus the counts of the node's symbols in lower lanes,
+//   D = {rem, 0} + P*t and Y_k = Y_(k-1) + l_k*t (Y_0 = D, l_k the lane's k-th negated count) are five more
+//   v_mad_i64_i32: the low words are the y of old, the high words their borrows.  For a node row every partial sum Q is
+//   0 <= Q <= the node's total and total*t <= range < 2^32, so in the lane that owns the symbol and in those below it
+//   (D >= 0) every high word is 0 or -1: the symbol is the lane's last one plus three of them, and ~h_D & h_e is the
+//   owner word, -1 in the owning lane and 0 elsewhere (above it D < 0, h_e is -1 or -2 and h_D = -1 masks it).  That word
+//   is what ds_add puts on the count and what masks the output byte.  The scratch row's "counts" are arbitrary, and so are
+//   the symbol and the owner word then: the symbol reaches memory only as (sym & 3) * 4 + the lane's 16 bytes of the
+//   row round 1 chose (0 .. 16) and as an output byte of a block that is marked and decoded again, the owner word only as
+//   the ds_add's operand into that scratch row.
 // A target at or past the total (corrupt input only) leaves no borrow in round 1 and "node 16",
 // whose counts are a scratch area behind the block's table.  Such a block is detected, not
 // decoded: it is marked in `redo` and decoded again by rcx_dec_adaptive_k, which has the
@@ -398,12 +408,12 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     __shared__ __attribute__((aligned(256))) u8 lds_all[WAVES * RCX_QUAD_LDS_BYTES];
     RCX_QUAD_SEAT(seat, WAVES, quads_used, lds_all, g, nblocks, n, block);
 
-    // model: cpprcoder.h:1094-1132, every count 1
+    // model: cpprcoder.h:1094-1132, every count 1 -- kept negated in LDS, as the bounds are in registers: round 2 below
     {
         U4 v;
-        v.x = v.y = v.z = v.w = 1;
+        v.x = v.y = v.z = v.w = ~0u;
 #pragma unroll
-        for (u32 q = 0; q < 17; ++q) seat.leaves[q * 16] = v; // 16 nodes + the scratch row
+        for (u32 q = 0; q < 17; ++q) seat.leaves[q * 16] = v; // 16 nodes + the scratch row (which holds counts for nobody)
     }
     u32 nU1 = 0u - (64u * seat.j + 16), nU2 = nU1 - 16, nU3 = nU1 - 32, nU4 = nU1 - 48; // the bounds, negated
     const u32 T0 = 4u * seat.j;
@@ -465,21 +475,42 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #define RCX_QUAD_STAMP(i)
 #define RCX_QUAD_NO_STAMP
 #endif
-// What a symbol leaves for the one behind it (below): its number (valid in the lane that owns it), that lane's mask, and
-// the LDS address of the lane's four counts of the node.
-    u32 p_sym_ = 0, p_la_ = leaves_lds;
-    u64 p_own_ = 0;
+// What a symbol leaves for the one behind it (below): its number (valid in the lane that owns it), that lane's word (-1
+// there, 0 in the quad's other lanes), and the LDS address of the lane's four counts of the node.
+    u32 p_sym_ = 0, p_la_ = leaves_lds, p_own_ = 0;
 // One symbol.  Its byte and the +1 on its count are NOT made here but by the next symbol (HP = 1: PWORD, PSHIFT are that
 // earlier symbol's word and bit position) or by RCX_QUAD_DEC_FINISH: nothing the coder state needs depends on them, so
 // they fill the slots the node index's steps across the quad need anyway (the ds_add still comes before the next leaf
 // read: LDS serves a wave's operations in order) and the wait for the leaf read.
+// The counts are kept negated (a symbol seen c times: -c), so the +1 is a ds_add of the owner word as it is, and the byte
+// is the symbol ANDed with it; the first byte of an output word (PSHIFT == 0) IS the word.
 #define RCX_QD_PREV_A_0 "s_nop 1\n\t"
-#define RCX_QD_PREV_A_1 "v_cndmask_b32_e64 %[pown], 0, 1, %[pc]\n\t"                                                \
-                        "v_and_b32 %[pad], 3, %[psym]\n\t"                                                         \
+#define RCX_QD_PREV_A_1 "v_and_b32 %[pad], 3, %[psym]\n\t"                                                         \
                         "v_lshl_add_u32 %[pad], %[pad], 2, %[pla]\n\t" /* LDS address of the earlier symbol's count */
-#define RCX_QD_PREV_S_0
-#define RCX_QD_PREV_S_1 "\n\tv_cndmask_b32_e64 %[pye], 0, %[psym], %[pc]\n\t"                                       \
-                        "v_lshl_or_b32 %[pword], %[pye], %[psh], %[pword]"
+#define RCX_QD_PREV_S_FIRST "v_and_b32 %[pword], %[psym], %[pown]\n\t"
+#define RCX_QD_PREV_S_NEXT "v_and_b32 %[pye], %[psym], %[pown]\n\t"                                                 \
+                           "v_lshl_or_b32 %[pword], %[pye], %[psh], %[pword]\n\t"
+#define RCX_QP3 "quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+/* behind the leaf read: the remainder (round 1's other result) across the quad, and as the pair {rem, 0} round 2 adds to; \
+   cpprcoder.h:1134-1177, +1 on every cumulative sum above the node -- the bounds whose subtraction borrowed in round 1  \
+   (bound above low <=> its node number above the symbol's node; a target past the total leaves no borrow and raises    \
+   none, as find()'s fall-through needs it): the negated bound takes its high word, 0 or -1; the earlier symbol's byte */ \
+#define RCX_QD_REM(PREV, PSHIFT, ...)                                                                      \
+        asm volatile("v_min3_u32 %[rm], %[x1], %[x2], %[x3]\n\t"                                           \
+                     "v_min3_u32 %[rm], %[rm], %[x4], %[low]\n\t"                                          \
+                     "v_add_u32 %[u1], %[u1], %[h1]\n\t"                                                   \
+                     "v_add_u32 %[u2], %[u2], %[h2]\n\t"                                                   \
+                     "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP1                                          \
+                     "v_add_u32 %[u3], %[u3], %[h3]\n\t"                                                   \
+                     "v_add_u32 %[u4], %[u4], %[h4]\n\t"                                                   \
+                     "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP2                                          \
+                     PREV                                                                                  \
+                     "v_mad_u64_u32 %[R], %[cr], %[rm], 1, 0"                                              \
+                     : [u1] "+v"(nU1), [u2] "+v"(nU2), [u3] "+v"(nU3), [u4] "+v"(nU4), [rm] "=&v"(rem_),    \
+                       [R] "=&v"(R_), [cr] "=&s"(cr_) __VA_ARGS__                                           \
+                     : [low] "v"(in.low), [x1] "v"(x1_), [x2] "v"(x2_),                                    \
+                       [x3] "v"(x3_), [x4] "v"(x4_), [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_), \
+                       [pown] "v"(p_own_), [psym] "v"(p_sym_), [psh] "n"(PSHIFT))
 #define RCX_QUAD_DEC_SYMBOL(MUL, INC, SH, HP, PWORD, PSHIFT)                                               \
     {                                                                                                      \
         /* cpprcoder.h:926-940 (in.n4 = the next four stream bytes, ready since the previous symbol) */    \
@@ -493,8 +524,8 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
            multiply-add per bound: {low, 0} - U_k * t has low - U_k * t in its low word and the borrow, 0 or -1, in   \
            its high word (its carry-out goes to a mask register nothing reads) */                          \
         const u64 lowp_ = in.low;                                                                          \
-        u32 node_, rem_, ro_, la_, pown_, pad_, pye_;                                                      \
-        u64 X1_, X2_, X3_, X4_, c1_, c2_, c3_, cz_;                                                        \
+        u32 node_, rem_, ro_, la_, pad_, pye_;                                                             \
+        u64 X1_, X2_, X3_, X4_, R_, cz_, cr_, cy_;                                                         \
         asm volatile("v_mad_i64_i32 %[X1], %[cz], %[n1], %[t], %[lp]\n\t"                                  \
                      "v_mad_i64_i32 %[X2], %[cz], %[n2], %[t], %[lp]\n\t"                                  \
                      "v_mad_i64_i32 %[X3], %[cz], %[n3], %[t], %[lp]\n\t"                                  \
@@ -511,10 +542,10 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
         asm volatile("v_add3_u32 %[nd], %[h1], %[h2], %[h3]\n\t"                                           \
                      "v_add3_u32 %[nd], %[nd], %[h4], 4\n\t" /* 4 - the lane's borrows (they stay: the update below) */ \
                      RCX_QD_PREV_A_##HP                                                                    \
-                     : [nd] "=&v"(node_), [pown] "=&v"(pown_), [pad] "=&v"(pad_)                            \
+                     : [nd] "=&v"(node_), [pad] "=&v"(pad_)                                                 \
                      : [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_),                         \
-                       [pc] "s"(p_own_), [psym] "v"(p_sym_), [pla] "v"(p_la_));                            \
-        if (HP) (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), pown_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916, the earlier symbol's */ \
+                       [psym] "v"(p_sym_), [pla] "v"(p_la_));                                              \
+        if (HP) (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), p_own_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916, the earlier symbol's: -1 on its negated count */ \
         asm volatile("v_add_u32_dpp %[nd], %[nd], %[nd] " RCX_QP1                                          \
                      "v_bfe_u32 %[ro], %[bp], 5, 5\n\t"  /* ring slot of the next pair ... */               \
                      "v_lshl_add_u32 %[ro], %[ro], 2, %[rb]" /* ... and its LDS address (formed here: a vector instruction right \
@@ -535,79 +566,78 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
         RCX_QUAD_STAMP(0);                                                                                 \
         const RcxV4 l_ = *reinterpret_cast<const RcxLdsV4*>(la_);                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                 \
-        /* behind the read: the remainder (round 1's other result) across the quad; cpprcoder.h:1134-1177, +1 on every \
-           cumulative sum above the node -- the bounds whose subtraction borrowed in round 1 (bound above low <=> its \
-           node number above the symbol's node; a target past the total leaves no borrow and raises none, as find()'s \
-           fall-through needs it): the negated bound takes its high word, 0 or -1; the earlier symbol's byte */ \
-        u32 sb_;                                                                                           \
-        asm volatile("v_min3_u32 %[rm], %[x1], %[x2], %[x3]\n\t"                                           \
-                     "v_min3_u32 %[rm], %[rm], %[x4], %[low]\n\t"                                          \
-                     "v_add_u32 %[u1], %[u1], %[h1]\n\t"                                                   \
-                     "v_add_u32 %[u2], %[u2], %[h2]\n\t"                                                   \
-                     "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP1                                          \
-                     "v_add_u32 %[u3], %[u3], %[h3]\n\t"                                                   \
-                     "v_add_u32 %[u4], %[u4], %[h4]\n\t"                                                   \
-                     "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP2                                          \
-                     "v_lshl_add_u32 %[sb], %[n], 4, %[t0p3]" /* symbol, if none of the lane's bounds is above */ \
-                     RCX_QD_PREV_S_##HP                                                                    \
-                     : [u1] "+v"(nU1), [u2] "+v"(nU2), [u3] "+v"(nU3), [u4] "+v"(nU4), [rm] "=&v"(rem_),    \
-                       [sb] "=&v"(sb_), [pye] "=&v"(pye_), [pword] "+v"(PWORD)                              \
-                     : [n] "v"(node_), [t0p3] "v"(T0p3), [low] "v"(in.low), [x1] "v"(x1_), [x2] "v"(x2_),  \
-                       [x3] "v"(x3_), [x4] "v"(x4_), [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_), \
-                       [pc] "s"(p_own_), [psym] "v"(p_sym_), [psh] "n"(PSHIFT));                           \
-        u32 lo_, rg_, qa_, qb_, qc_, qe_, tot_, pre_, o2_, d2_, ya_, yb_, yc_, ye_, hi_;                   \
-        asm volatile("v_mul_u32_u24 %[qa], %[lx], %[t]\n\t"      /* the lane's four inclusive sums, scaled: every */ \
-                     "v_mad_u32_u24 %[qb], %[ly], %[t], %[qa]\n\t" /* sum is below total x t <= range < 2^32 */      \
-                     "v_mad_u32_u24 %[qc], %[lz], %[t], %[qb]\n\t"                                         \
-                     "v_mad_u32_u24 %[qe], %[lw], %[t], %[qc]\n\t"                                         \
+        if (!(HP)) RCX_QD_REM("", 0);                                                                      \
+        else if ((PSHIFT) == 0) RCX_QD_REM(RCX_QD_PREV_S_FIRST, 0, , [pword] "=&v"(PWORD));                \
+        else RCX_QD_REM(RCX_QD_PREV_S_NEXT, PSHIFT, , [pye] "=&v"(pye_), [pword] "+v"(PWORD));             \
+        /* The lane's four counts l are negative.  P = the counts of the node's symbols in lower lanes (negated, from the \
+           lanes' unscaled sums across the quad), D = {rem, 0} + P x t, and Y_k = Y_(k-1) + l_k x t from Y_0 = D: the low \
+           words are rem - t x (the counts up to and including the lane's k-th), the high words their borrows.  In the \
+           lane that owns the symbol and below it D >= 0 and every high word is 0 or -1; above it D < 0, -1 or -2. */ \
+        u32 qe_, pre_, o2_, o3_;                                                                           \
+        u64 D_, Ya_, Yb_, Yc_, Ye_;                                                                        \
+        asm volatile("v_add3_u32 %[qe], %[lx], %[ly], %[lz]\n\t"                                           \
+                     "v_add_u32 %[qe], %[qe], %[lw]\n\t"                                                   \
                      "v_alignbit_b32 %[n4], %[w1], %[w0], %[bp]\n\t" /* (the next symbol's 4 stream bytes at bp8 ... */ \
                      "v_perm_b32 %[n4], %[n4], %[n4], %[swap]\n\t" /* ... first one on top: here they separate qe from its use across the quad) */ \
-                     "v_add_u32_dpp %[tot], %[qe], %[qe] " RCX_QP1 /* the lanes' sums are scanned scaled: (a+b)t = at+bt */ \
-                     "v_and_b32_dpp %[pre], %[qe], %[m1] " RCX_QP1                                         \
-                     "v_sub_u32 %[d2], %[rem], %[pre]\n\t"                                                 \
-                     "v_and_b32_dpp %[o2], %[tot], %[m2] " RCX_QP2                                         \
-                     "v_sub_u32 %[d2], %[d2], %[o2]\n\t"     /* rem - t x the counts of the node's symbols in lower lanes */ \
-                     "v_sub_co_u32_e64 %[ya], %[c1], %[d2], %[qa]\n\t"                                     \
-                     "v_sub_co_u32_e64 %[yb], %[c2], %[d2], %[qb]\n\t"                                     \
-                     "v_sub_co_u32_e64 %[yc], %[c3], %[d2], %[qc]\n\t"                                     \
-                     "v_sub_co_u32_e64 %[ye], %[own], %[d2], %[qe]\n\t" /* borrows in the lane that owns the symbol */ \
-                     "v_min3_u32 %[lo], %[d2], %[ya], %[yb]\n\t"                                           \
+                     "v_and_b32_dpp %[pre], %[qe], %[m1] " RCX_QP1 /* all three steps read the lane's own sum: no wait between them */ \
+                     "v_and_b32_dpp %[o2], %[qe], %[m2] " RCX_QP2                                          \
+                     "v_and_b32_dpp %[o3], %[qe], %[m2] " RCX_QP3                                          \
+                     "v_add3_u32 %[qe], %[pre], %[o2], %[o3]\n\t" /* P */                                        \
+                     "v_mad_i64_i32 %[D], %[cy], %[qe], %[t], %[R]\n\t"                                    \
+                     "v_mad_i64_i32 %[Ya], %[cy], %[lx], %[t], %[D]\n\t"                                   \
+                     "v_mad_i64_i32 %[Yb], %[cy], %[ly], %[t], %[Ya]\n\t"                                  \
+                     "v_mad_i64_i32 %[Yc], %[cy], %[lz], %[t], %[Yb]\n\t"                                  \
+                     "v_mad_i64_i32 %[Ye], %[cy], %[lw], %[t], %[Yc]"                                      \
+                     : [n4] "=&v"(in.n4), [qe] "=&v"(qe_), [pre] "=&v"(pre_), [o2] "=&v"(o2_), [o3] "=&v"(o3_), \
+                       [D] "=&v"(D_), [Ya] "=&v"(Ya_), [Yb] "=&v"(Yb_), [Yc] "=&v"(Yc_),    \
+                       [Ye] "=&v"(Ye_), [cy] "=&s"(cy_)                                                     \
+                     : [lx] "v"(l_.x), [ly] "v"(l_.y), [lz] "v"(l_.z), [lw] "v"(l_.w), [t] "v"(t_),        \
+                       [R] "v"(R_), [m1] "v"(m1), [m2] "v"(m2),                                            \
+                       [w0] "v"(in.w0), [w1] "v"(in.w1), [bp] "v"(in.bp8), [swap] "s"(0x00010203u));       \
+        /* (as in round 1, something of the compiler's between the pairs and the statement that reads their words: the \
+           symbol, if none of the lane's counts borrows.  It costs an s_nop itself if it lands in a register the      \
+           sequence above wrote, so that one's scratch registers stay taken until the next: its last four operands) */ \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        const u32 sb_ = (node_ << 4) + T0p3;                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        const u32 d2_ = (u32)D_, ya_ = (u32)Ya_, yb_ = (u32)Yb_, yc_ = (u32)Yc_, ye_ = (u32)Ye_;           \
+        const u32 hd_ = (u32)(D_ >> 32), ha_ = (u32)(Ya_ >> 32), hb_ = (u32)(Yb_ >> 32), hc_ = (u32)(Yc_ >> 32), \
+                  he_ = (u32)(Ye_ >> 32);                                                                  \
+        u32 lo_, rg_, hi_;                                                                                 \
+        asm volatile("v_min3_u32 %[lo], %[d2], %[ya], %[yb]\n\t"                                           \
                      "v_max3_u32 %[hi], %[ya], %[yb], %[yc]\n\t"                                           \
                      "v_min_u32 %[lo], %[lo], %[yc]\n\t"                                                   \
                      "v_max_u32 %[hi], %[hi], %[ye]\n\t"                                                   \
-                     "v_subb_co_u32_e64 %[sym], %[c1], %[sb], 0, %[c1]\n\t"                                \
+                     "v_add3_u32 %[sym], %[sb], %[ha], %[hb]\n\t"                                          \
                      "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP1                                          \
-                     "v_subb_co_u32_e64 %[sym], %[c2], %[sym], 0, %[c2]\n\t"                               \
+                     "v_add_u32 %[sym], %[sym], %[hc]\n\t"                                                 \
                      "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP1                                          \
-                     "v_subb_co_u32_e64 %[sym], %[c3], %[sym], 0, %[c3]\n\t"                               \
+                     "v_bfi_b32 %[own], %[hd], 0, %[he]\n\t" /* ~h_D & h_e: -1 in the lane that owns the symbol, 0 elsewhere */ \
                      "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP2                                          \
                      "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP2                                          \
                      "v_sub_u32 %[rg], %[lo], %[hi]"                                                       \
-                     : [lo] "=&v"(lo_), [rg] "=&v"(rg_), [sym] "=&v"(p_sym_), [own] "=&s"(p_own_), [n4] "=&v"(in.n4), \
-                       [qa] "=&v"(qa_), [qb] "=&v"(qb_), [qc] "=&v"(qc_),                                   \
-                       [qe] "=&v"(qe_), [tot] "=&v"(tot_), [pre] "=&v"(pre_), [o2] "=&v"(o2_), [d2] "=&v"(d2_), \
-                       [ya] "=&v"(ya_), [yb] "=&v"(yb_), [yc] "=&v"(yc_), [ye] "=&v"(ye_), [hi] "=&v"(hi_),  \
-                       [c1] "=&s"(c1_), [c2] "=&s"(c2_), [c3] "=&s"(c3_)                                   \
-                     : [lx] "v"(l_.x), [ly] "v"(l_.y), [lz] "v"(l_.z), [lw] "v"(l_.w), [t] "v"(t_),        \
-                       [rem] "v"(rem_), [m1] "v"(m1), [m2] "v"(m2), [sb] "v"(sb_),                         \
-                       [w0] "v"(in.w0), [w1] "v"(in.w1), [bp] "v"(in.bp8), [swap] "s"(0x00010203u));       \
+                     : [lo] "=&v"(lo_), [rg] "=&v"(rg_), [sym] "=&v"(p_sym_), [own] "=&v"(p_own_), [hi] "=&v"(hi_) \
+                     : [d2] "v"(d2_), [ya] "v"(ya_), [yb] "v"(yb_), [yc] "v"(yc_), [ye] "v"(ye_), [sb] "v"(sb_), \
+                       [hd] "v"(hd_), [ha] "v"(ha_), [hb] "v"(hb_), [hc] "v"(hc_), [he] "v"(he_),          \
+                       "v"(qe_), "v"(pre_), "v"(o2_), "v"(o3_));                                            \
         RCX_QUAD_STAMP(1);                                                                                 \
         in.low = lo_;   /* :906 */                                                                         \
         in.range = rg_; /* :907 */                                                                         \
         p_la_ = la_;                                                                                       \
     }
 // The byte and the count of the last symbol decoded (no symbol follows that would make them): into WORD at bit SHIFT.
+#define RCX_QD_FINISH(BYTE, SHIFT, ...)                                                                    \
+        asm volatile("v_and_b32 %[pad], 3, %[psym]\n\t"                                                    \
+                     BYTE                                                                                  \
+                     "v_lshl_add_u32 %[pad], %[pad], 2, %[pla]"                                            \
+                     : [pad] "=&v"(pad_) __VA_ARGS__                                                        \
+                     : [pown] "v"(p_own_), [psym] "v"(p_sym_), [pla] "v"(p_la_), [psh] "n"(SHIFT))
 #define RCX_QUAD_DEC_FINISH(WORD, SHIFT)                                                                    \
     {                                                                                                      \
-        u32 pown_, pad_, pye_;                                                                             \
-        asm volatile("v_cndmask_b32_e64 %[pown], 0, 1, %[pc]\n\t"                                          \
-                     "v_and_b32 %[pad], 3, %[psym]\n\t"                                                    \
-                     "v_cndmask_b32_e64 %[pye], 0, %[psym], %[pc]\n\t"                                     \
-                     "v_lshl_add_u32 %[pad], %[pad], 2, %[pla]\n\t"                                        \
-                     "v_lshl_or_b32 %[pword], %[pye], %[psh], %[pword]"                                    \
-                     : [pown] "=&v"(pown_), [pad] "=&v"(pad_), [pye] "=&v"(pye_), [pword] "+v"(WORD)        \
-                     : [pc] "s"(p_own_), [psym] "v"(p_sym_), [pla] "v"(p_la_), [psh] "n"(SHIFT));          \
-        (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), pown_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916 */ \
+        u32 pad_, pye_;                                                                                    \
+        if ((SHIFT) == 0) RCX_QD_FINISH(RCX_QD_PREV_S_FIRST, 0, , [pword] "=&v"(WORD));                    \
+        else RCX_QD_FINISH(RCX_QD_PREV_S_NEXT, SHIFT, , [pye] "=&v"(pye_), [pword] "+v"(WORD));            \
+        (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), p_own_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916 */ \
     }
 
     // The divisors of the fast loop: a quarter group -- multipliers and increments of 4 symbols -- sits in two 16-byte
@@ -709,8 +739,11 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #undef RCX_QUAD_DEC_FINISH
 #undef RCX_QD_PREV_A_0
 #undef RCX_QD_PREV_A_1
-#undef RCX_QD_PREV_S_0
-#undef RCX_QD_PREV_S_1
+#undef RCX_QD_PREV_S_FIRST
+#undef RCX_QD_PREV_S_NEXT
+#undef RCX_QD_REM
+#undef RCX_QD_FINISH
+#undef RCX_QP3
 #undef RCX_QUAD_DIVQ_LOAD
 #undef RCX_QUAD_DIVQ_ENTRY
 #undef RCX_QUAD_U4_AT
