@@ -1,6 +1,6 @@
 """python -m cpprcoder_amd c|d|t ...  -- compress / decompress / test files with the MI355X block coder.
 
-    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag|auto]] [--crc]
+    python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag|auto]] [--crc] [--stored [FRACTION]]
                               [--static | --coder adaptive|static|rans|rans8] IN OUT
                                                                IN -> RCXB container (cpprcoder_amd/container.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
@@ -15,14 +15,20 @@
                                                                auto: the one that the order-0 cost of the split text says
                                                                pays off by 1/64 or more, else none (include/rcx_stats.h);
                                                                the line printed names the choice;
-                                                               --crc: a CRC-32 per block goes into the container
+                                                               --crc: a CRC-32 per block goes into the container;
+                                                               --stored [FRACTION]: a block whose stream does not shrink, or
+                                                               by less than FRACTION (0 <= FRACTION < 1) of the block, is
+                                                               kept as its raw bytes and decoded by copy
+                                                               (include/rcx_stored.h): the container never grows past its
+                                                               input, and the line printed says "stored K/N" blocks.  In
+                                                               front of IN write --stored=FRACTION, or another option behind it
     python -m cpprcoder_amd d [--no-verify] IN OUT             container (RCXB or RCXT, told apart by the magic; an RCXI
                                                                container holds items, not a file) -> original bytes.
                                                                A container with checksums
                                                                is verified: on a mismatch the bad block is named on
                                                                stderr, the exit status is 1 and OUT is not written
                                                                (--no-verify: write what the decoder produced)
-    python -m cpprcoder_amd t [--crc] [--planes W [--predict delta|zigzag|auto]] FILE...
+    python -m cpprcoder_amd t [--crc] [--stored [FRACTION]] [--planes W [--predict delta|zigzag|auto]] FILE...
                                                                the reference harness's row per file
                                                                (|file|ratio|encode|decode|, test/main.cpp:346-356):
                                                                pack, unpack, compare, times incl. PCIe copies
@@ -34,6 +40,14 @@ import time
 
 CODERS = ("adaptive", "static", "rans", "rans8")  # include/rcx.h: RCX_CODER_*
 PREDICTORS = ("delta", "zigzag", "auto")          # include/rcx_predict.h: RCX_PRED_DELTA, RCX_PRED_ZIGZAG; auto: container.pick_predictor
+
+
+def _fraction(text: str) -> float:
+    """--stored's value: a fraction of the block, 0 <= g < 1."""
+    g = float(text)
+    if not 0 <= g < 1:
+        raise argparse.ArgumentTypeError("a fraction of the block, 0 <= FRACTION < 1")
+    return g
 
 
 class _Parser(argparse.ArgumentParser):
@@ -58,6 +72,7 @@ def parser() -> argparse.ArgumentParser:
     first.add_argument("--planes", type=int, choices=(2, 4, 8), default=None, metavar="W")
     c.add_argument("--predict", choices=PREDICTORS, default=None)
     c.add_argument("--crc", action="store_true")
+    c.add_argument("--stored", nargs="?", type=_fraction, const=True, default=None, metavar="FRACTION")
     c.add_argument("src")
     c.add_argument("dst")
     d = sub.add_parser("d")
@@ -73,6 +88,7 @@ def parser() -> argparse.ArgumentParser:
     first.add_argument("--planes", type=int, choices=(2, 4, 8), default=None, metavar="W")
     t.add_argument("--predict", choices=PREDICTORS, default=None)
     t.add_argument("--crc", action="store_true")
+    t.add_argument("--stored", nargs="?", type=_fraction, const=True, default=None, metavar="FRACTION")
     t.add_argument("files", nargs="+")
     return ap
 
@@ -85,8 +101,8 @@ def main(argv=None) -> int:
 
     def pack(data):
         if a.planes:
-            return container.pack_typed(data, a.planes, a.block, coder, ctx, checksum=a.crc, predict=a.predict)
-        return container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc)
+            return container.pack_typed(data, a.planes, a.block, coder, ctx, checksum=a.crc, predict=a.predict, stored=a.stored)
+        return container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc, stored=a.stored)
 
     def unpack(blob, verify=True):
         if bytes(blob[:4]) == container.TYPED_MAGIC:
@@ -96,10 +112,16 @@ def main(argv=None) -> int:
         return container.unpack(blob, ctx, verify=verify)
 
     def chosen(blob):
-        """What --predict auto took, for the line printed: the container itself does not say that it was measured."""
-        if getattr(a, "predict", None) != "auto":
-            return ""
-        return " predict=" + ("none", "delta", "zigzag")[container.parse_typed(blob)["pred"]]
+        """What --stored kept raw and what --predict auto took, for the line printed: the container itself does not say that
+        either was asked for."""
+        typed = bytes(blob[:4]) == container.TYPED_MAGIC
+        out = ""
+        if getattr(a, "stored", None) is not None:
+            c = container.parse_typed(blob) if typed else container.parse(blob)
+            out += f" stored {0 if c['stored'] is None else int(c['stored'].sum())}/{c['nblocks']}"
+        if getattr(a, "predict", None) == "auto":
+            out += " predict=" + ("none", "delta", "zigzag")[container.parse_typed(blob)["pred"]]
+        return out
 
     try:
         if a.cmd == "c":

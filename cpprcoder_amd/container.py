@@ -70,6 +70,20 @@ as a buffer of its own: the transform of a span from one superblock border to an
 span taken alone.  A predictor (pack_typed(..., predict="delta" | "zigzag"): for integers whose differences are small) is
 opt-in and restarts in every superblock, so all of that holds with it; without one a container is byte for byte version 1.
 
+Stored blocks (pack(..., stored=True | fraction), pack_typed(..., stored=...); include/rcx_stored.h, cpprcoder_amd/stored.py): a
+block whose stream did not shrink -- coded_b + floor(len_b * gain / 65536) >= len_b, gain = 0 for True, min(65535, int(g * 65536))
+for a fraction 0 <= g < 1 -- is kept as its len_b raw bytes and decoded by copy, so a payload never exceeds what the coder
+saw.  Such a container is version 3 of either layout, and flag bit 2 (FLAG_STORED) is set; the two only ever appear together:
+    RCXB version 3: the fixed part as above, flags bit 2 set (bits 0 and 1 as above); offsets; the bitmap; with bit 1 the CRC
+        table; payload
+    RCXT version 3: the fixed part as above, flags bit 2 set (bit 1 as above), byte 29 = the predictor, 0, 1 or 2; offsets;
+        the bitmap; with bit 1 the CRC table; payload
+    the bitmap: ceil(nblocks / 8) bytes, block b is bit b & 7 of byte b >> 3, padding bits zero, at least one bit set; a
+        stored block's two offsets are len_b apart
+The CRC stays the CRC of what the coder saw.  If no block ends up stored the container is, byte for byte, the one written
+without the option.  With the option the pack path is the device path of the checked containers: one upload, encode, mix
+(and CRC), one download.  An item container has no stored items.
+
 pack_typed(..., predict="auto") measures instead of asking (include/rcx_stats.h; cpprcoder_amd/stats.py).  For each of none,
 delta and zigzag the split text's order-0 cost is C_p = the sum of the blocks' costs -- what an order-0 coder with one model a
 block will make of it, to within a few percent.  The rule (pick_predictor): a predictor is a candidate only if it earns at
@@ -84,8 +98,10 @@ import numpy as np
 MAGIC = b"RCXB"
 VERSION = 1
 VERSION_CRC = 2  # the same layout + the CRC table; always with FLAG_CRC32
+VERSION_STORED = 3  # + the bitmap of the stored blocks behind the offsets; always with FLAG_STORED (RCXB and RCXT)
 FLAG_BLKSORT = 1
 FLAG_CRC32 = 2
+FLAG_STORED = 4
 _FIXED = struct.Struct("<4sBBHIQQ")
 ITEM_MAGIC = b"RCXI"
 ITEM_VERSION = 1
@@ -94,6 +110,7 @@ MAX_ITEM = (1 << 24) - 256  # RCX_MAX_BLOCK
 TYPED_MAGIC = b"RCXT"
 TYPED_VERSION = 1
 TYPED_VERSION_PRED = 2  # the same layout + the predictor at byte 29; only with a predictor
+TYPED_VERSION_STORED = VERSION_STORED  # + the bitmap; byte 29 names the predictor, none included
 PREDICTORS = {None: 0, "delta": 1, "zigzag": 2}  # include/rcx_predict.h: RCX_PRED_*
 AUTO = "auto"  # pack_typed(predict=AUTO): measured, see pick_predictor; never in a container
 _TYPED_FIXED = struct.Struct("<4sBBHIQQB7s")
@@ -139,17 +156,63 @@ def _check_version(version: int, flags: int, known: int) -> bool:
     raise ContainerError("unsupported container version, coder or flags")
 
 
-def header_bytes(coder: int, block: int, n: int, offsets, flags: int = 0, crcs=None) -> bytes:
+def _block_lengths(m: int, block: int, nblocks: int) -> np.ndarray:
+    lengths = np.full(nblocks, block, dtype=np.int64)
+    if nblocks:
+        lengths[-1] = m - (nblocks - 1) * block
+    return lengths
+
+
+def _stored_must_fit(stored, offsets, m: int, block: int) -> None:
+    """A stored block's stream is the block: its two offsets are len_b apart."""
+    sizes = np.diff(np.asarray(offsets).astype(np.int64))
+    if np.any(sizes[stored] != _block_lengths(m, block, len(sizes))[stored]):
+        raise ContainerError("a stored block is not as long as its bytes")
+
+
+def _bitmap_bytes(stored, offsets, m: int, block: int) -> bytes:
+    """The bitmap of a version 3 header, b"" if no block is stored (then the header is the one without the option)."""
+    if stored is None:
+        return b""
+    stored = np.asarray(stored) != 0
+    if len(stored) != len(offsets) - 1:
+        raise ContainerError("one stored flag per block")
+    if not stored.any():
+        return b""
+    _stored_must_fit(stored, offsets, m, block)
+    return np.packbits(stored, bitorder="little").tobytes()
+
+
+def _parse_bitmap(buf, end: int, nblocks: int):
+    """-> (stored bool[nblocks], where the bitmap ends)"""
+    size = (nblocks + 7) // 8
+    if nblocks > len(buf) or len(buf) < end + size:
+        raise ContainerError("truncated bitmap")
+    bits = np.unpackbits(np.frombuffer(bytes(buf[end: end + size]), dtype=np.uint8), bitorder="little")
+    if bits[nblocks:].any():
+        raise ContainerError("a padding bit of the bitmap is set")
+    if not bits[:nblocks].any():
+        raise ContainerError("version 3 without a stored block")
+    return bits[:nblocks].astype(bool), end + size
+
+
+def header_bytes(coder: int, block: int, n: int, offsets, flags: int = 0, crcs=None, stored=None) -> bytes:
     offsets = np.ascontiguousarray(offsets, dtype="<u8")
     nblocks = len(offsets) - 1
+    if flags & FLAG_STORED:
+        raise ContainerError("the stored flag comes with the bitmap")
     if nblocks != (coded_size(n, flags) + block - 1) // block:
         raise ContainerError("offsets do not match n and the block size")
+    bitmap = _bitmap_bytes(stored, offsets, coded_size(n, flags), block)
     version, flags, table = _version_and_flags(flags, crcs, nblocks)
-    return _FIXED.pack(MAGIC, version, coder, flags, block, n, nblocks) + offsets.tobytes() + table
+    if bitmap:
+        version, flags = VERSION_STORED, flags | FLAG_STORED
+    return _FIXED.pack(MAGIC, version, coder, flags, block, n, nblocks) + offsets.tobytes() + bitmap + table
 
 
 def parse(blob):
-    """-> dict(coder, flags, block, n, nblocks, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, payload uint8 view)"""
+    """-> dict(coder, flags, block, n, nblocks, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, stored bool[nblocks] or None,
+    payload uint8 view)"""
     buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
     if len(buf) < _FIXED.size:
         raise ContainerError("shorter than a header")
@@ -158,13 +221,21 @@ def parse(blob):
         raise ContainerError("not an RCXB container")
     if coder not in (0, 1, 2, 3):
         raise ContainerError("unsupported container version, coder or flags")
-    checked = _check_version(version, flags, FLAG_BLKSORT)
+    if version == VERSION_STORED:  # always with its flag; bits 0 and 1 as in the versions before
+        if not flags & FLAG_STORED or flags & ~(FLAG_BLKSORT | FLAG_CRC32 | FLAG_STORED):
+            raise ContainerError("unsupported container version, coder or flags")
+        checked = bool(flags & FLAG_CRC32)
+    else:
+        checked = _check_version(version, flags, FLAG_BLKSORT)
     if block < 16 or block > (1 << 24) - 256 or nblocks != (coded_size(n, flags) + block - 1) // block:
         raise ContainerError("inconsistent header")
     end = _FIXED.size + 8 * (nblocks + 1)
     if len(buf) < end:
         raise ContainerError("truncated offset table")
     offsets = np.frombuffer(bytes(buf[_FIXED.size:end]), dtype="<u8").astype(np.uint64)
+    stored = None
+    if version == VERSION_STORED:
+        stored, end = _parse_bitmap(buf, end, nblocks)
     crcs = None
     if checked:
         if nblocks > len(buf) or len(buf) < end + 4 * nblocks:
@@ -173,7 +244,10 @@ def parse(blob):
         end += 4 * nblocks
     if offsets[0] != 0 or np.any(np.diff(offsets.astype(np.int64)) < 0) or end + int(offsets[-1]) != len(buf):
         raise ContainerError("offset table does not match the payload")
-    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "offsets": offsets, "crcs": crcs, "payload": buf[end:]}
+    if stored is not None:
+        _stored_must_fit(stored, offsets, coded_size(n, flags), block)
+    return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "offsets": offsets, "crcs": crcs, "stored": stored,
+            "payload": buf[end:]}
 
 
 # ---- the checked paths: one upload, the device calls, one download ------------------------------------------------
@@ -187,8 +261,32 @@ def _crcs_of(t) -> np.ndarray:
     return t.cpu().numpy().view(np.uint32).copy()
 
 
-def _pack_checked(ctx, src: np.ndarray, block: int, coder: int, blksort: bool):
-    """-> (payload, offsets, crcs): block sort (if asked for), encode and CRC-32 of the coder's input, all on the device."""
+def _gain(stored):
+    """The option stored=None | True | fraction of pack and pack_typed -> None, or the gain of include/rcx_stored.h."""
+    if stored is None or stored is False:
+        return None
+    from . import stored as calls
+    try:
+        return calls.gain_q16(stored)
+    except ValueError as e:
+        raise ContainerError(f"stored is None, True or a fraction 0 <= g < 1 of the block, not {stored!r}") from e
+
+
+def _mix_device(ctx, d_src, block: int, d_dst, d_offs, gain: int):
+    """Behind the encode call on d_src: the mix of include/rcx_stored.h -> (mixed streams, their table, the flags), on the device."""
+    import torch
+    from . import rcx, stored as calls
+    nblocks = rcx.block_count(d_src.numel(), block)
+    d_mixed = torch.empty(d_src.numel(), dtype=torch.uint8, device="cuda")  # a mixed payload is never longer than the text
+    d_moffs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
+    d_flags = torch.zeros(nblocks, dtype=torch.uint8, device="cuda")
+    calls.mix_device(ctx, d_src, block, d_dst, d_dst.numel(), d_offs, gain, d_mixed, d_moffs, d_flags)
+    return d_mixed, d_moffs, d_flags
+
+
+def _pack_device(ctx, src: np.ndarray, block: int, coder: int, blksort: bool, checksum: bool = True, gain=None):
+    """-> (payload, offsets, crcs or None, stored flags or None): block sort (if asked for), encode, the mix of the stored blocks
+    (if asked for) and CRC-32 of the coder's input (if asked for), all on the device."""
     import torch
     from . import rcx
     d_src = _cuda(src)
@@ -202,10 +300,15 @@ def _pack_checked(ctx, src: np.ndarray, block: int, coder: int, blksort: bool):
     d_offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
     d_crc = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
     ctx.encode_blocks_device(d_src, block, d_dst, d_offs, coder=coder)
-    ctx.crc32_blocks_device(d_src, block, d_crc)
+    d_flags = None
+    if gain is not None:
+        d_dst, d_offs, d_flags = _mix_device(ctx, d_src, block, d_dst, d_offs, gain)
+    if checksum:
+        ctx.crc32_blocks_device(d_src, block, d_crc)
     ctx.sync_status()
     offsets = d_offs.cpu().numpy().astype(np.uint64)
-    return d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc)
+    return (d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc) if checksum else None,
+            None if d_flags is None else d_flags.cpu().numpy())
 
 
 def _sync_checked(ctx, kind: str, name=lambda k: k):
@@ -218,14 +321,25 @@ def _sync_checked(ctx, kind: str, name=lambda k: k):
         raise rcx.RcxError(st, f"{kind} {bad}")
 
 
-def _unpack_checked(ctx, c) -> bytes:
+def _decode_all_device(ctx, c, m: int, d_out) -> None:
+    """Every block of a container to d_out: through the block call, or with stored blocks through the call that copies them."""
+    if c.get("stored") is None:
+        ctx.decode_blocks_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), m, c["block"], d_out, coder=c["coder"])
+    else:
+        from . import stored as calls
+        doffs = np.minimum(np.arange(c["nblocks"] + 1, dtype=np.uint64) * np.uint64(c["block"]), np.uint64(m))
+        calls.decode_device(ctx, _cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), c["stored"], doffs, d_out, coder=c["coder"])
+    ctx.sync_status()  # (the decoder's own failures first: a stream that runs dry is an RcxError, as without checksums)
+
+
+def _unpack_device(ctx, c, verify: bool = True) -> bytes:
     import torch
     m = coded_size(c["n"], c["flags"])
     d_out = torch.empty(m, dtype=torch.uint8, device="cuda")
-    ctx.decode_blocks_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), m, c["block"], d_out, coder=c["coder"])
-    ctx.sync_status()  # (the decoder's own failures first: a stream that runs dry is an RcxError, as without checksums)
-    ctx.verify_blocks_device(d_out, c["block"], _cuda(c["crcs"]))
-    _sync_checked(ctx, "block")
+    _decode_all_device(ctx, c, m, d_out)
+    if verify and c["crcs"] is not None:
+        ctx.verify_blocks_device(d_out, c["block"], _cuda(c["crcs"]))
+        _sync_checked(ctx, "block")
     if c["flags"] & FLAG_BLKSORT:
         d_text = torch.empty(max(c["n"], 1), dtype=torch.uint8, device="cuda")
         ctx.bwt_decode_device(d_out, m, d_text)
@@ -242,7 +356,11 @@ def _decode_picked_device(ctx, c, lengths, pick, kind: str, checked: bool):
     pick = np.asarray(pick, dtype=np.uint64)
     doffs = rcx.item_offsets(np.asarray(lengths, dtype=np.uint64)[pick.astype(np.int64)])
     d_out = torch.empty(max(int(doffs[-1]), 1), dtype=torch.uint8, device="cuda")
-    ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), doffs, d_out, pick=pick, coder=c["coder"])
+    if c.get("stored") is None:
+        ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), doffs, d_out, pick=pick, coder=c["coder"])
+    else:
+        from . import stored as calls
+        calls.decode_device(ctx, _cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), c["stored"], doffs, d_out, pick=pick, coder=c["coder"])
     ctx.sync_status()
     if checked:
         ctx.verify_items_device(d_out, doffs, _cuda(c["crcs"][pick.astype(np.int64)]))
@@ -257,8 +375,11 @@ def _decode_picked_checked(ctx, c, lengths, pick, kind: str) -> list:
     return [out[int(doffs[k]): int(doffs[k + 1])] for k in range(len(pick))]
 
 
-def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = False, checksum: bool = False) -> bytes:
+def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = False, checksum: bool = False, stored=None) -> bytes:
+    """stored=True | fraction: blocks that do not shrink (by that fraction of their length) are kept raw, see the module's
+    docstring; the container is version 3 if there is such a block, else the one written without the option."""
     from . import rcx
+    gain = _gain(stored)
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
@@ -266,9 +387,9 @@ def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = Fal
         flags = FLAG_BLKSORT if blksort else 0
         if len(src) == 0:
             return header_bytes(coder, block, 0, np.zeros(1, np.uint64), flags, np.zeros(0, np.uint32) if checksum else None)
-        if checksum:
-            payload, offsets, crcs = _pack_checked(ctx, src, block, coder, blksort)
-            return header_bytes(coder, block, len(src), offsets, flags, crcs) + payload.tobytes()
+        if checksum or gain is not None:
+            payload, offsets, crcs, raw = _pack_device(ctx, src, block, coder, blksort, checksum, gain)
+            return header_bytes(coder, block, len(src), offsets, flags, crcs, raw) + payload.tobytes()
         payload, offsets = ctx.encode_blocks(ctx.bwt_encode(src) if blksort else src, block, coder=coder)
         return header_bytes(coder, block, len(src), offsets, flags) + payload.tobytes()
     finally:
@@ -284,8 +405,8 @@ def unpack(blob, ctx=None, verify: bool = True) -> bytes:
     own = ctx is None
     ctx = ctx or rcx.Context(0)
     try:
-        if verify and c["crcs"] is not None:
-            return _unpack_checked(ctx, c)
+        if (verify and c["crcs"] is not None) or c["stored"] is not None:
+            return _unpack_device(ctx, c, verify)
         m = coded_size(c["n"], c["flags"])
         out = ctx.decode_blocks(c["payload"], c["offsets"], c["block"], capacity=m, coder=c["coder"])
         if len(out) != m:
@@ -319,6 +440,9 @@ def unpack_range(blob, start: int, stop: int, ctx=None, verify: bool = True) -> 
     try:
         if verify and c["crcs"] is not None:
             parts = _decode_picked_checked(ctx, c, lengths, pick, "block")
+        elif c["stored"] is not None:
+            d_out, doffs = _decode_picked_device(ctx, c, lengths, pick, "block", False)
+            parts = [d_out[: int(doffs[-1])].cpu().numpy()]
         else:
             parts = ctx.decode_items(c["payload"], c["offsets"], lengths, pick=pick, coder=c["coder"])
     finally:
@@ -420,7 +544,7 @@ def unpack_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
 
 
 # ---- the typed container: the byte-plane filter in front of the coder ---------------------------------------------------
-def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs=None, pred: int = 0) -> bytes:
+def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs=None, pred: int = 0, stored=None) -> bytes:
     offsets = np.ascontiguousarray(offsets, dtype="<u8")
     nblocks = len(offsets) - 1
     if width not in WIDTHS:
@@ -436,22 +560,29 @@ def typed_header_bytes(coder: int, block: int, n: int, width: int, offsets, crcs
             raise ContainerError("one checksum per block or item")
         flags, table = FLAG_CRC32, crcs.tobytes()
     version = TYPED_VERSION_PRED if pred else TYPED_VERSION  # version 2 only with a predictor
-    return _TYPED_FIXED.pack(TYPED_MAGIC, version, coder, flags, block, n, nblocks, width, bytes([pred]) + bytes(6)) + offsets.tobytes() + table
+    bitmap = _bitmap_bytes(stored, offsets, n, block)
+    if bitmap:  # version 3 only with a stored block
+        version, flags = TYPED_VERSION_STORED, flags | FLAG_STORED
+    return (_TYPED_FIXED.pack(TYPED_MAGIC, version, coder, flags, block, n, nblocks, width, bytes([pred]) + bytes(6)) + offsets.tobytes() + bitmap
+            + table)
 
 
 def parse_typed(blob):
-    """-> dict(coder, flags, block, n, nblocks, width, pred, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, payload uint8 view);
-    pred is 0 for a version 1 container"""
+    """-> dict(coder, flags, block, n, nblocks, width, pred, offsets uint64[nblocks+1], crcs uint32[nblocks] or None, stored bool[nblocks]
+    or None, payload uint8 view); pred is 0 for a version 1 container"""
     buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
     if len(buf) < _TYPED_FIXED.size:
         raise ContainerError("shorter than a header")
     magic, version, coder, flags, block, n, nblocks, width, reserved = _TYPED_FIXED.unpack(bytes(buf[: _TYPED_FIXED.size]))
     if magic != TYPED_MAGIC:
         raise ContainerError("not an RCXT container")
-    if version not in (TYPED_VERSION, TYPED_VERSION_PRED) or coder not in (0, 1, 2, 3) or flags & ~FLAG_CRC32:
+    known = FLAG_CRC32 | (FLAG_STORED if version == TYPED_VERSION_STORED else 0)  # bit 2 in version 3, and always there
+    if (version not in (TYPED_VERSION, TYPED_VERSION_PRED, TYPED_VERSION_STORED) or coder not in (0, 1, 2, 3) or flags & ~known
+            or (version == TYPED_VERSION_STORED and not flags & FLAG_STORED)):
         raise ContainerError("unsupported container version, coder or flags")
     pred = reserved[0]
-    if width not in WIDTHS or reserved[1:] != bytes(6) or (pred not in (1, 2) if version == TYPED_VERSION_PRED else pred != 0):
+    pred_ok = pred in (1, 2) if version == TYPED_VERSION_PRED else pred in (0, 1, 2) if version == TYPED_VERSION_STORED else pred == 0
+    if width not in WIDTHS or reserved[1:] != bytes(6) or not pred_ok:
         raise ContainerError("an element is 2, 4 or 8 bytes wide, version 2 names its predictor, and the reserved bytes are zero")
     if block < 16 or block > (1 << 24) - 256 or nblocks != (n + block - 1) // block:
         raise ContainerError("inconsistent header")
@@ -459,6 +590,9 @@ def parse_typed(blob):
     if nblocks > len(buf) or len(buf) < end:
         raise ContainerError("truncated offset table")
     offsets = np.frombuffer(bytes(buf[_TYPED_FIXED.size:end]), dtype="<u8").astype(np.uint64)
+    stored = None
+    if version == TYPED_VERSION_STORED:
+        stored, end = _parse_bitmap(buf, end, nblocks)
     crcs = None
     if flags & FLAG_CRC32:
         if len(buf) < end + 4 * nblocks:
@@ -467,8 +601,10 @@ def parse_typed(blob):
         end += 4 * nblocks
     if offsets[0] != 0 or np.any(np.diff(offsets.astype(np.int64)) < 0) or end + int(offsets[-1]) != len(buf):
         raise ContainerError("offset table does not match the payload")
+    if stored is not None:
+        _stored_must_fit(stored, offsets, n, block)
     return {"coder": coder, "flags": flags, "block": block, "n": n, "nblocks": nblocks, "width": width, "pred": pred, "offsets": offsets,
-            "crcs": crcs, "payload": buf[end:]}
+            "crcs": crcs, "stored": stored, "payload": buf[end:]}
 
 
 def _typed_source(data, width):
@@ -515,7 +651,7 @@ def _measured_predictor(ctx, d_src, width: int, block: int, nblocks: int, d_spli
     return pick_predictor(*totals), 2
 
 
-def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False, predict=None) -> bytes:
+def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False, predict=None, stored=None) -> bytes:
     """data: bytes, a numpy array or a contiguous torch tensor (CPU or GPU) -> an RCXT container.  width=None: the
     element size of the array or tensor.  predict=None, "delta" or "zigzag": the predictor of include/rcx_predict.h in front of
     the filter, for integers whose differences are small (unsorted data gets worse by it).  predict="auto": the one the
@@ -524,7 +660,9 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
     measured on a GiB of sorted int64 keys at 64 KiB blocks, 2.33 ms for the decision beside 4.86 ms for the adaptive
     encode that follows, 48 % of it (profiles/r08_stats_rate.jsonl).  One upload (none for a GPU
     tensor), then split, encode and, with checksum=True, the CRC-32 of every block of the split text, all with the device
-    calls."""
+    calls.  stored=True | fraction: blocks of the split text that do not shrink (by that fraction) are kept raw -- the low
+    mantissa planes of floating-point data -- and the container is version 3 if there is one (the module's docstring)."""
+    gain = _gain(stored)
     auto = isinstance(predict, str) and predict == AUTO
     if not auto and (not (predict is None or isinstance(predict, str)) or predict not in PREDICTORS):
         raise ContainerError(f"a predictor is None, 'delta', 'zigzag' or 'auto', not {predict!r}")
@@ -550,6 +688,9 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
         if held != pred:
             predictor.split_device(ctx, d_src, width, block, pred, d_split)  # (no predictor: the plane filter's own kernel)
         ctx.encode_blocks_device(d_split, block, d_dst, d_offs, coder=coder)
+        d_flags = None
+        if gain is not None:
+            d_dst, d_offs, d_flags = _mix_device(ctx, d_split, block, d_dst, d_offs, gain)
         crcs = None
         if checksum:
             d_crc = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
@@ -558,7 +699,8 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
         if checksum:
             crcs = _crcs_of(d_crc)
         offsets = d_offs.cpu().numpy().astype(np.uint64)
-        return typed_header_bytes(coder, block, n, width, offsets, crcs, pred) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
+        raw = None if d_flags is None else d_flags.cpu().numpy()
+        return typed_header_bytes(coder, block, n, width, offsets, crcs, pred, raw) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
     finally:
         if own:
             ctx.close()
@@ -576,8 +718,7 @@ def unpack_typed(blob, ctx=None, verify: bool = True) -> bytes:
     ctx = ctx or rcx.Context(0)
     try:
         d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
-        ctx.decode_blocks_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), n, c["block"], d_split, coder=c["coder"])
-        ctx.sync_status()
+        _decode_all_device(ctx, c, n, d_split)
         if verify and c["crcs"] is not None:
             ctx.verify_blocks_device(d_split, c["block"], _cuda(c["crcs"]))
             _sync_checked(ctx, "block")

@@ -14,6 +14,7 @@
 //   rcx_crc.hpp          CRC-32 per block or item, stored or verified
 //   rcx_stats.hpp        byte counts and order-0 cost per block or item
 //   rcx_planes.hpp       the byte-plane filter for typed data, split and join
+//   rcx_stored.hpp       stored blocks: the rule per block, and the copy of raw and kept streams
 //
 // Roofline class: HBM-bound integer/byte work, no MFMA.  What actually bounds the
 // coder kernels is the serial dependency chain of one symbol (divide -> multiply ->
@@ -138,3 +139,4 @@ __global__ __launch_bounds__(256) void rcx_scatter_k(const u8* __restrict__ slot
 #include "rcx_crc.hpp"
 #include "rcx_stats.hpp"
 #include "rcx_planes.hpp"
+#include "rcx_stored.hpp"
