@@ -90,6 +90,31 @@ block will make of it, to within a few percent.  The rule (pick_predictor): a pr
 least 1/64, 64 * C_p < 63 * C_none; the cheaper candidate is taken, delta on a tie; without a candidate, none.  The margin
 keeps data that no predictor helps on version 1: uniform bytes at 4 KiB blocks would otherwise take delta for 0.002 %.  The
 container is byte for byte what predict=<the choice> writes, and nothing in it records that the choice was measured.
+
+The typed item container holds many buffers of differing sizes, each with an element width (1, 2, 4 or 8) and a predictor
+of its own (include/rcx_typed_items.h; cpprcoder_amd/typed_items.py): typed item i is transformed as one superblock of
+m_i = len_i // w_i elements, and its w_i planes -- the last one with the len_i % w_i tail bytes -- are the coder's items, the
+SUB-ITEMS, nsub = the sum of the widths; a sub-item of length 0 has no stream.  A fourth magic:
+    0   4  magic  b"RCXJ"
+    4   1  version (1)
+    5   1  coder
+    6   2  flags: bit 1 = checksums (FLAG_CRC32); every other bit 0
+    8   8  nitems
+    16  8  nsub
+    24  8  dlen, the bytes of the directory
+    32  8 * nitems      the items' lengths
+    ..  nitems          their widths
+    ..  nitems          their predictors (include/rcx_predict.h: 0 none, 1 delta, 2 delta + zigzag; 0 with width 1)
+    ..  8 * (nsub + 1)  offsets of the sub-item streams in the payload
+    ..  with bit 1: 4 * nsub  the CRC-32 of each sub-item of the SPLIT text (0 for an empty one)
+    ..  dlen            the directory: the caller's bytes, carried and not interpreted (may be empty)
+    ..  payload: the sub-item streams back to back
+unpack_typed_items(blob, pick) decodes the picked items' sub-items and no others, verifies those, and joins them as a call of
+its own with re-based offsets: every item is a superblock of its own, so any subset is exact.  predict="auto" decides PER
+ITEM with pick_predictor on the sum of its sub-items' order-0 costs under the three candidates.  There are no stored
+sub-items and no command-line subcommand.  pack_tensors / unpack_tensors put tensors with names on top of it and nothing
+else: every tensor is cut into typed items of element_size * block bytes -- its superblocks, so its sub-items are the blocks
+pack_typed would code -- and the directory is JSON: a list of {"name", "dtype" (torch's name), "shape", "first", "count"}.
 """
 import struct
 
@@ -761,3 +786,373 @@ def unpack_typed_range(blob, start: int, stop: int, ctx=None, verify: bool = Tru
         if own:
             ctx.close()
     return out[start - first * superblock: stop - first * superblock].tobytes()
+
+
+# ---- the typed item container: a width and a predictor per buffer, in front of the item calls ---------------------------
+TYPED_ITEMS_MAGIC = b"RCXJ"
+TYPED_ITEMS_VERSION = 1
+_TYPED_ITEMS_FIXED = struct.Struct("<4sBBHQQQ")
+ITEM_WIDTHS = (1, 2, 4, 8)
+
+
+def _sub_lengths(lengths, widths) -> np.ndarray:
+    """The sub-items' lengths (int64): item i gives widths[i] of len // width bytes, the last with the len % width tail."""
+    lengths, widths = np.asarray(lengths).astype(np.int64), np.asarray(widths).astype(np.int64)
+    m = lengths // np.maximum(widths, 1)
+    sub = np.repeat(m, widths)
+    if len(widths):
+        sub[np.cumsum(widths) - 1] += lengths - m * widths
+    return sub
+
+
+def _typed_items_tables(lengths, widths, preds):
+    lengths = np.ascontiguousarray(lengths, dtype="<u8")
+    widths = np.ascontiguousarray(widths, dtype=np.uint8)
+    preds = np.zeros(len(widths), np.uint8) if preds is None else np.ascontiguousarray(preds, dtype=np.uint8)
+    if len(widths) != len(lengths) or len(preds) != len(lengths):
+        raise ContainerError("one length, one width and one predictor per item")
+    if np.any(~np.isin(widths, ITEM_WIDTHS)):
+        raise ContainerError("an element is 1, 2, 4 or 8 bytes wide")
+    if np.any(preds > 2) or np.any((widths == 1) & (preds != 0)):
+        raise ContainerError("a predictor is 0 (none), 1 (delta) or 2 (zigzag), and 0 for width 1")
+    sub = _sub_lengths(lengths, widths)
+    if len(sub) and int(sub.max()) > MAX_ITEM:
+        raise ContainerError("a sub-item is longer than the coder takes")
+    return lengths, widths, preds, sub
+
+
+def typed_items_header_bytes(coder: int, lengths, widths, preds, offsets, crcs=None, directory: bytes = b"") -> bytes:
+    lengths, widths, preds, sub = _typed_items_tables(lengths, widths, preds)
+    offsets = np.ascontiguousarray(offsets, dtype="<u8")
+    if len(offsets) != len(sub) + 1:
+        raise ContainerError("offsets do not match the number of sub-items")
+    flags, table = 0, b""
+    if crcs is not None:
+        crcs = np.ascontiguousarray(crcs, dtype="<u4")
+        if len(crcs) != len(sub):
+            raise ContainerError("one checksum per sub-item")
+        flags, table = FLAG_CRC32, crcs.tobytes()
+    directory = bytes(directory)
+    return (_TYPED_ITEMS_FIXED.pack(TYPED_ITEMS_MAGIC, TYPED_ITEMS_VERSION, coder, flags, len(lengths), len(sub), len(directory)) + lengths.tobytes()
+            + widths.tobytes() + preds.tobytes() + offsets.tobytes() + table + directory)
+
+
+def parse_typed_items(blob):
+    """-> dict(coder, flags, nitems, nsub, lengths uint64[nitems], widths uint8[nitems], preds uint8[nitems], sub_first int64[nitems + 1],
+    sub_lengths uint64[nsub], offsets uint64[nsub + 1], crcs uint32[nsub] or None, directory bytes, payload uint8 view)"""
+    buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+    if len(buf) < _TYPED_ITEMS_FIXED.size:
+        raise ContainerError("shorter than a header")
+    magic, version, coder, flags, nitems, nsub, dlen = _TYPED_ITEMS_FIXED.unpack(bytes(buf[: _TYPED_ITEMS_FIXED.size]))
+    if magic != TYPED_ITEMS_MAGIC:
+        raise ContainerError("not an RCXJ container")
+    if version != TYPED_ITEMS_VERSION or coder not in (0, 1, 2, 3) or flags & ~FLAG_CRC32:
+        raise ContainerError("unsupported container version, coder or flags")
+    at = _TYPED_ITEMS_FIXED.size
+    if nitems > len(buf) or nsub > len(buf) or dlen > len(buf) or len(buf) < at + 10 * nitems + 8 * (nsub + 1):
+        raise ContainerError("truncated tables")
+    lengths = np.frombuffer(bytes(buf[at: at + 8 * nitems]), dtype="<u8").astype(np.uint64)
+    at += 8 * nitems
+    widths = np.array(buf[at: at + nitems], dtype=np.uint8)
+    preds = np.array(buf[at + nitems: at + 2 * nitems], dtype=np.uint8)
+    at += 2 * nitems
+    _, _, _, sub = _typed_items_tables(lengths, widths, preds)  # (refuses bad widths and predictors, and sub-items that are too long)
+    if len(sub) != nsub:
+        raise ContainerError("the widths do not add up to the number of sub-items")
+    offsets = np.frombuffer(bytes(buf[at: at + 8 * (nsub + 1)]), dtype="<u8").astype(np.uint64)
+    at += 8 * (nsub + 1)
+    crcs = None
+    if flags & FLAG_CRC32:
+        if len(buf) < at + 4 * nsub:
+            raise ContainerError("truncated checksum table")
+        crcs = np.frombuffer(bytes(buf[at: at + 4 * nsub]), dtype="<u4").astype(np.uint32)
+        at += 4 * nsub
+    if len(buf) < at + dlen:
+        raise ContainerError("truncated directory")
+    directory = bytes(buf[at: at + dlen])
+    at += dlen
+    sizes = np.diff(offsets.astype(np.int64))
+    if offsets[0] != 0 or np.any(sizes < 0) or at + int(offsets[-1]) != len(buf):
+        raise ContainerError("offset table does not match the payload")
+    if np.any((sub == 0) != (sizes == 0)):
+        raise ContainerError("a sub-item of length 0 has no stream, and only such a sub-item")
+    sub_first = np.concatenate([[0], np.cumsum(widths.astype(np.int64))])
+    return {"coder": coder, "flags": flags, "nitems": nitems, "nsub": nsub, "lengths": lengths, "widths": widths, "preds": preds, "sub_first": sub_first,
+            "sub_lengths": sub.astype(np.uint64), "offsets": offsets, "crcs": crcs, "directory": directory, "payload": buf[at:]}
+
+
+def _item_source(x):
+    """One item -> (its bytes: a uint8 cuda tensor if it lies on the GPU, else a uint8 numpy array; its element size or None)"""
+    if type(x).__module__.split(".")[0] == "torch":
+        import torch
+        if not x.is_contiguous():
+            raise ContainerError("a tensor must be contiguous")
+        flat = x.detach().reshape(-1).view(torch.uint8)
+        return (flat if flat.is_cuda else flat.numpy()), x.element_size()
+    if isinstance(x, np.ndarray):
+        return np.ascontiguousarray(x).reshape(-1).view(np.uint8), x.dtype.itemsize
+    return np.frombuffer(x, dtype=np.uint8), None
+
+
+def _gather_device(parts):
+    """The items' bytes back to back on the device: no upload if all of them lie there, else one."""
+    import torch
+    if not parts:
+        return torch.empty(0, dtype=torch.uint8, device="cuda")
+    if all(hasattr(x, "is_cuda") for x in parts):
+        return torch.cat(parts) if len(parts) > 1 else parts[0]
+    return _cuda(np.concatenate([x.cpu().numpy() if hasattr(x, "is_cuda") else x for x in parts]))
+
+
+def _item_predictors(predict, widths):
+    """predict: None, a name, AUTO or one entry per item -> (preds uint8[nitems] with 0 where it is measured, auto bool[nitems])"""
+    nitems = len(widths)
+    entries = list(predict) if isinstance(predict, (list, tuple)) else [predict] * nitems
+    if len(entries) != nitems:
+        raise ContainerError("one predictor per item")
+    preds, auto = np.zeros(nitems, np.uint8), np.zeros(nitems, bool)
+    for i, e in enumerate(entries):
+        if isinstance(e, str) and e == AUTO:
+            auto[i] = widths[i] > 1  # (a width-1 item is never predicted)
+        elif (e is None or isinstance(e, str)) and e in PREDICTORS:
+            if e is not None and widths[i] == 1:
+                if isinstance(predict, (list, tuple)):
+                    raise ContainerError("an item of width 1 takes no predictor")
+            else:
+                preds[i] = PREDICTORS[e]
+        else:
+            raise ContainerError(f"a predictor is None, 'delta', 'zigzag' or 'auto', not {e!r}")
+    return preds, auto
+
+
+def _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d_split):
+    """The items marked in `auto` get pick_predictor's choice on the sums of their sub-items' order-0 costs under none, delta and
+    zigzag: three segmented splits into d_split, a statistics pass over each (costs only), one download of the sums."""
+    import torch
+    from . import stats, typed_items
+    nsub, nitems = len(sub_offs) - 1, len(widths)
+    d_cost = torch.zeros(3 * nsub, dtype=torch.int64, device="cuda")
+    for cand in (0, 1, 2):
+        typed_items.split_device(ctx, d_src, offs, widths, np.where(auto, cand, preds).astype(np.uint8), d_split)
+        stats.items_device(ctx, d_split, sub_offs, None, d_cost[cand * nsub: (cand + 1) * nsub])
+    # the sums per item: differences of the running sum at the items' sub-item borders (a sub-item's cost is below 2^45)
+    running = torch.cat([torch.zeros(3, 1, dtype=torch.int64, device="cuda"), torch.cumsum(d_cost.view(3, nsub), dim=1)], dim=1)
+    borders = torch.from_numpy(np.concatenate([[0], np.cumsum(widths.astype(np.int64))])).cuda()
+    sums = (running[:, borders[1:]] - running[:, borders[:-1]]).cpu().numpy()
+    out = preds.copy()
+    for i in np.flatnonzero(auto):
+        out[i] = PREDICTORS[pick_predictor(int(sums[0, i]), int(sums[1, i]), int(sums[2, i]))]
+    assert sums.shape == (3, nitems)
+    return out
+
+
+def _pack_typed_items_device(ctx, d_src, lengths, widths, preds, auto, coder: int, checksum: bool, directory: bytes) -> bytes:
+    """d_src: the items back to back on the device -> the container: split, encode over the sub-items, with checksum the CRC-32
+    of the sub-items of the split text, one download."""
+    import torch
+    from . import rcx, typed_items
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    _typed_items_tables(lengths, widths, preds)
+    nsub = int(widths.astype(np.int64).sum())
+    if int(lengths.sum()) == 0:  # nothing to code: no GPU
+        return typed_items_header_bytes(coder, lengths, widths, preds, np.zeros(nsub + 1, np.uint64), np.zeros(nsub, np.uint32) if checksum else None, directory)
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        offs = rcx.item_offsets(lengths)
+        sub_offs = typed_items.sub_offsets(offs, widths)
+        d_split = torch.empty(d_src.numel(), dtype=torch.uint8, device="cuda")
+        if auto.any():
+            preds = _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d_split)
+        typed_items.split_device(ctx, d_src, offs, widths, preds, d_split)
+        d_dst = torch.empty(max(rcx.encode_items_bound(sub_offs, coder), 1), dtype=torch.uint8, device="cuda")
+        d_offs = torch.zeros(nsub + 1, dtype=torch.int64, device="cuda")
+        ctx.encode_items_device(d_split, sub_offs, d_dst, d_offs, coder=coder)
+        crcs = None
+        if checksum:
+            d_crc = torch.zeros(nsub, dtype=torch.int32, device="cuda")
+            ctx.crc32_items_device(d_split, sub_offs, d_crc)
+        ctx.sync_status()
+        if checksum:
+            crcs = _crcs_of(d_crc)
+        offsets = d_offs.cpu().numpy().astype(np.uint64)
+        return typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory) + d_dst[: int(offsets[-1])].cpu().numpy().tobytes()
+    finally:
+        if own:
+            ctx.close()
+
+
+def pack_typed_items(items, widths=None, predict=None, coder: int = 0, ctx=None, checksum: bool = False, directory: bytes = b"") -> bytes:
+    """items: a list of buffers (bytes, numpy arrays, contiguous torch tensors on the CPU or the GPU) -> an RCXJ container.
+    widths=None: each array's or tensor's element size (plain bytes need a width); else one width for all, or one per item.
+    predict: None, "delta", "zigzag", "auto", or a list with one of these per item; "auto" decides per item from the measured
+    order-0 costs (the module's docstring), and a width-1 item is never predicted.  One upload (none if every item lies on the
+    GPU), then split, encode over the sub-items and, with checksum=True, their CRC-32, all with the device calls."""
+    sources = [_item_source(x) for x in items]
+    if widths is None:
+        each = [w for _, w in sources]
+        if any(w is None for w in each):
+            raise ContainerError("plain bytes have no element size: give the width")
+    else:
+        each = list(widths) if isinstance(widths, (list, tuple, np.ndarray)) else [widths] * len(sources)
+        if len(each) != len(sources):
+            raise ContainerError("one width per item")
+    if any(type(w) not in (int, np.uint8, np.int64, np.int32) or int(w) not in ITEM_WIDTHS for w in each):
+        raise ContainerError(f"an element is 1, 2, 4 or 8 bytes wide, not {each!r}")
+    w = np.array(each, dtype=np.uint8)
+    preds, auto = _item_predictors(predict, w)
+    parts = [x for x, _ in sources]
+    lengths = np.array([int(x.numel()) if hasattr(x, "numel") else len(x) for x in parts], dtype=np.uint64)
+    if int(lengths.sum()) == 0:
+        return _pack_typed_items_device(ctx, None, lengths, w, preds, auto, coder, checksum, directory)
+    return _pack_typed_items_device(ctx, _gather_device(parts), lengths, w, preds, auto, coder, checksum, directory)
+
+
+def _unpack_typed_items_device(ctx, c, pick, verify: bool):
+    """The picked items of a parsed RCXJ container, decoded, verified and joined on the device -> (the device buffer, the
+    table of where each pick lies in it).  Only the picks' sub-items are decoded and checked."""
+    import torch
+    from . import rcx, typed_items
+    pick = np.asarray(pick, dtype=np.int64)
+    widths, preds = c["widths"][pick], c["preds"][pick]
+    doffs = rcx.item_offsets(c["lengths"][pick])
+    n = int(doffs[-1])
+    d_out = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+    if n == 0:
+        return d_out, doffs
+    # the picks' sub-items, in order: back to back they are the split text of the picks back to back
+    subs = np.concatenate([np.arange(c["sub_first"][k], c["sub_first"][k + 1], dtype=np.int64) for k in pick])
+    owner = np.repeat(pick, widths.astype(np.int64))
+    soffs = typed_items.sub_offsets(doffs, widths)
+    d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
+    ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), soffs, d_split, pick=subs.astype(np.uint64), coder=c["coder"])
+    ctx.sync_status()
+    if verify and c["crcs"] is not None:
+        ctx.verify_items_device(d_split, soffs, _cuda(c["crcs"][subs]))
+        _sync_checked(ctx, "item", lambda k: int(owner[k]))
+    typed_items.join_device(ctx, d_split, doffs, widths, preds, d_out)
+    return d_out, doffs
+
+
+def unpack_typed_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
+    """-> the list of the picked items' bytes (all of them, in order, if pick is None); picks may repeat or be empty.  Only the
+    picked items' sub-items are decoded, and in a container with checksums only they are verified: a mismatch raises
+    ChecksumError naming the item."""
+    from . import rcx
+    c = parse_typed_items(blob)
+    if pick is not None and any(not 0 <= int(k) < c["nitems"] for k in pick):
+        raise ContainerError("no such item")
+    picked = np.arange(c["nitems"], dtype=np.int64) if pick is None else np.array([int(k) for k in pick], dtype=np.int64)
+    if len(picked) == 0:
+        return []
+    if int(c["lengths"][picked].sum()) == 0:
+        return [b""] * len(picked)
+    own = ctx is None
+    ctx = ctx or rcx.Context(0)
+    try:
+        d_out, doffs = _unpack_typed_items_device(ctx, c, picked, verify)
+        out = d_out.cpu().numpy()
+        return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
+    finally:
+        if own:
+            ctx.close()
+
+
+# ---- tensors with names, on top of the typed item container ---------------------------------------------------------------
+def tensor_directory_bytes(entries) -> bytes:
+    """entries: a list of dict(name, dtype, shape, first, count) -> the JSON directory of pack_tensors."""
+    import json
+    return json.dumps([{"name": str(e["name"]), "dtype": str(e["dtype"]), "shape": [int(d) for d in e["shape"]], "first": int(e["first"]),
+                        "count": int(e["count"])} for e in entries], separators=(",", ":")).encode()
+
+
+def parse_tensor_directory(directory: bytes, nitems: int) -> list:
+    import json
+    try:
+        entries = json.loads(bytes(directory).decode())
+        if not isinstance(entries, list):
+            raise TypeError("not a list")
+        out = [{"name": str(e["name"]), "dtype": str(e["dtype"]), "shape": tuple(int(d) for d in e["shape"]), "first": int(e["first"]),
+                "count": int(e["count"])} for e in entries]
+    except (ValueError, KeyError, TypeError) as err:
+        raise ContainerError("the directory is not a tensor directory") from err
+    if any(e["first"] < 0 or e["count"] < 0 or e["first"] + e["count"] > nitems or any(d < 0 for d in e["shape"]) for e in out):
+        raise ContainerError("the directory names items the container does not have")
+    if len({e["name"] for e in out}) != len(out):
+        raise ContainerError("a name occurs twice in the directory")
+    return out
+
+
+def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=None, checksum: bool = False) -> bytes:
+    """named: a dict of names -> numpy arrays or contiguous torch tensors (CPU or GPU) -> an RCXJ container whose directory
+    names them.  Every tensor is cut into typed items of element_size * block bytes, its superblocks.  predict: None, a
+    name or "auto" for all tensors, or a dict of names -> those (a name it lacks: none); tensors of 1-byte elements are never
+    predicted.  An element size outside 1, 2, 4, 8 raises ContainerError."""
+    import torch
+    if not 16 <= block <= MAX_ITEM:
+        raise ContainerError("a block is 16 bytes to RCX_MAX_BLOCK")
+    parts, lengths, widths, entry_preds, entries = [], [], [], [], []
+    for name, t in named.items():
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(t if t.flags.c_contiguous else np.ascontiguousarray(t))
+        if type(t).__module__.split(".")[0] != "torch":
+            raise ContainerError(f"{name!r} is neither a numpy array nor a torch tensor")
+        src, width = _item_source(t)
+        if width not in ITEM_WIDTHS:
+            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
+        nbytes = int(src.numel()) if hasattr(src, "numel") else len(src)
+        count = -(-nbytes // (width * block))
+        entries.append({"name": name, "dtype": str(t.dtype).replace("torch.", ""), "shape": tuple(t.shape), "first": len(lengths), "count": count})
+        each = predict.get(name) if isinstance(predict, dict) else predict
+        if nbytes:
+            parts.append(src)
+            lengths += [width * block] * (count - 1) + [nbytes - (count - 1) * width * block]
+            widths += [width] * count
+            entry_preds += [None if width == 1 else each] * count
+    w = np.array(widths, dtype=np.uint8)
+    preds, auto = _item_predictors(entry_preds, w)
+    lengths = np.array(lengths, dtype=np.uint64)
+    directory = tensor_directory_bytes(entries)
+    d_src = _gather_device(parts) if int(lengths.sum()) else None
+    return _pack_typed_items_device(ctx, d_src, lengths, w, preds, auto, coder, checksum, directory)
+
+
+def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool = True) -> dict:
+    """-> a dict of torch tensors of the recorded dtype and shape, on `device` ("cuda": no download).  names: only those
+    tensors, and only their items are decoded (and verified)."""
+    import torch
+    from . import rcx
+    c = parse_typed_items(blob)
+    entries = parse_tensor_directory(c["directory"], c["nitems"])
+    by_name = {e["name"]: e for e in entries}
+    wanted = [e["name"] for e in entries] if names is None else list(names)
+    if any(n not in by_name for n in wanted):
+        raise ContainerError("no such tensor")
+    for n in wanted:
+        if not isinstance(getattr(torch, by_name[n]["dtype"], None), torch.dtype):
+            raise ContainerError(f"{by_name[n]['dtype']!r} is no torch dtype")
+    pick = np.concatenate([np.arange(by_name[n]["first"], by_name[n]["first"] + by_name[n]["count"], dtype=np.int64) for n in wanted] + [np.zeros(0, np.int64)])
+    out, at = {}, 0
+    flat, doffs = None, rcx.item_offsets(c["lengths"][pick])
+    if int(doffs[-1]):
+        own = ctx is None
+        ctx = ctx or rcx.Context(0)
+        try:
+            flat, _ = _unpack_typed_items_device(ctx, c, pick, verify)
+            flat = flat if device == "cuda" else flat.cpu()
+        finally:
+            if own:
+                ctx.close()
+    for n in wanted:
+        e = by_name[n]
+        dtype = getattr(torch, e["dtype"])
+        a, b = int(doffs[at]), int(doffs[at + e["count"]])
+        at += e["count"]
+        count = int(np.prod(e["shape"], dtype=np.int64)) if len(e["shape"]) else 1
+        if b - a != count * torch.empty(0, dtype=dtype).element_size():
+            raise ContainerError(f"{n!r}: the items do not hold the tensor the directory describes")
+        if b == a:
+            out[n] = torch.empty(e["shape"], dtype=dtype, device=device)
+        else:  # (a copy: a tensor begins where the one before ends, at any alignment)
+            out[n] = flat[a:b].clone().view(dtype).reshape(e["shape"])
+    return out
