@@ -2,7 +2,7 @@
 
     python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag|auto]] [--crc] [--stored [FRACTION]]
                               [--static | --coder adaptive|static|rans|rans8] IN OUT
-                                                               IN -> RCXB container (cpprcoder_amd/container.py);
+                                                               IN -> RCXB container (cpprcoder_amd/layout.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
                                                                --planes W: IN is elements of W = 2, 4 or 8 bytes (bf16,
                                                                fp32, int64 ...), taken apart into byte planes first

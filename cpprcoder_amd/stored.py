@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import rcx
+from .layout import block_lengths  # noqa: F401 (len_b of every block: one rule for the containers and the mirror here)
 
 # every symbol include/rcx_stored.h declares
 EXPORTS = ("rcx_stored_mix_device", "rcx_stored_decode_device", "rcx_stored_mix", "rcx_stored_decode")
@@ -60,15 +61,6 @@ def is_stored(coded, length, gain: int):
         return int(coded) + ((int(length) * int(gain)) >> 16) >= int(length)
     coded, length = np.asarray(coded, dtype=np.uint64), np.asarray(length, dtype=np.uint64)
     return coded + ((length * np.uint64(gain)) >> np.uint64(16)) >= length  # (below 2^64: length < 2^24, gain < 2^16)
-
-
-def block_lengths(n: int, block: int) -> np.ndarray:
-    """len_b of every block of n bytes cut into blocks of `block`: all whole but the last."""
-    nblocks = (n + block - 1) // block
-    lengths = np.full(nblocks, block, dtype=np.uint64)
-    if nblocks:
-        lengths[-1] = n - (nblocks - 1) * block
-    return lengths
 
 
 def mix_numpy(src, block: int, payload, offsets, gain: int = 0):
