@@ -44,13 +44,19 @@ ITEM with pick_predictor on the sum of its sub-items' order-0 costs under the th
 subcommand.  pack_tensors / unpack_tensors put tensors with names on top of it and nothing else: every tensor is cut into
 typed items of element_size * block bytes -- its superblocks, so its sub-items are the blocks pack_typed would code -- and the
 directory names them (layout.py).
+
+Stored sub-items (pack_typed_items(..., stored=...), pack_tensors(..., stored=...); include/rcx_stored_items.h,
+cpprcoder_amd/stored_items.py): the same option with the sub-item in the block's place -- the mix runs behind the item encode call,
+an empty sub-item is never stored, and unpack goes through the decode call that copies.  The container is RCXJ version 2 if a
+sub-item ends up stored, else byte for byte the one written without the option.  RCXI has no such version:
+pack_typed_items(items, widths=1, stored=True) is the stored item container.
 """
 import contextlib
 
 import numpy as np
 
 from .layout import (FLAG_BLKSORT, FLAG_CRC32, FLAG_STORED, ITEM_MAGIC, ITEM_VERSION, ITEM_WIDTHS, MAGIC, MAX_ITEM, PREDICTORS,  # noqa: F401
-                     TYPED_ITEMS_MAGIC, TYPED_ITEMS_VERSION, TYPED_MAGIC, TYPED_VERSION, TYPED_VERSION_PRED, TYPED_VERSION_STORED, VERSION,
+                     TYPED_ITEMS_MAGIC, TYPED_ITEMS_VERSION, TYPED_ITEMS_VERSION_STORED, TYPED_MAGIC, TYPED_VERSION, TYPED_VERSION_PRED, TYPED_VERSION_STORED, VERSION,
                      VERSION_CRC, VERSION_STORED, WIDTHS, ChecksumError, ContainerError, _typed_items_tables, block_lengths, coded_size,
                      header_bytes, item_header_bytes, parse, parse_items, parse_tensor_directory, parse_typed, parse_typed_items,
                      tensor_directory_bytes, typed_header_bytes, typed_items_header_bytes)
@@ -144,19 +150,36 @@ def _encode_blocks(ctx, d_src, block: int, coder: int, checksum: bool, gain):
             None if d_flags is None else d_flags.cpu().numpy())
 
 
-def _encode_items(ctx, d_src, soffs, coder: int, checksum: bool):
-    """The item twin: the items of d_src at soffs -> (payload, offsets, crcs or None)."""
+def _mix_items_device(ctx, d_src, soffs, d_dst, d_offs, gain: int):
+    """Behind the item encode call on d_src: the mix of include/rcx_stored_items.h -> (mixed streams, their table, the flags), on the device."""
+    import torch
+    from . import stored_items as calls
+    nitems = len(soffs) - 1
+    d_mixed = torch.empty(max(int(soffs[-1] - soffs[0]), 1), dtype=torch.uint8, device="cuda")  # a mixed payload is never longer than the items
+    d_moffs = torch.zeros(nitems + 1, dtype=torch.int64, device="cuda")
+    d_flags = torch.zeros(max(nitems, 1), dtype=torch.uint8, device="cuda")
+    calls.mix_items_device(ctx, d_src, soffs, d_dst, d_dst.numel(), d_offs, gain, d_mixed, d_moffs, d_flags)
+    return d_mixed, d_moffs, d_flags[:nitems]
+
+
+def _encode_items(ctx, d_src, soffs, coder: int, checksum: bool, gain=None):
+    """The item twin: the items of d_src at soffs -> (payload, offsets, crcs or None, stored flags or None): encode, the mix of
+    the stored items (if asked for), the CRC-32 of every item of d_src (if asked for), one sync, the downloads."""
     import torch
     from . import rcx
     d_dst = torch.empty(max(rcx.encode_items_bound(soffs, coder), 1), dtype=torch.uint8, device="cuda")
     d_offs = torch.zeros(len(soffs), dtype=torch.int64, device="cuda")
     ctx.encode_items_device(d_src, soffs, d_dst, d_offs, coder=coder)
+    d_flags = None
+    if gain is not None:
+        d_dst, d_offs, d_flags = _mix_items_device(ctx, d_src, soffs, d_dst, d_offs, gain)
     if checksum:
         d_crc = torch.zeros(len(soffs) - 1, dtype=torch.int32, device="cuda")
         ctx.crc32_items_device(d_src, soffs, d_crc)
     ctx.sync_status()
     offsets = d_offs.cpu().numpy().astype(np.uint64)
-    return d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc) if checksum else None
+    return (d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc) if checksum else None,
+            None if d_flags is None else d_flags.cpu().numpy())
 
 
 def _sync_checked(ctx, kind: str, name=lambda k: k):
@@ -293,14 +316,15 @@ def unpack_range(blob, start: int, stop: int, ctx=None, verify: bool = True) -> 
 
 
 def pack_items(items, coder: int = 0, ctx=None, checksum: bool = False) -> bytes:
-    """items: a list of buffers -> an RCXI container."""
+    """items: a list of buffers -> an RCXI container.  It has no stored items: pack_typed_items(items, widths=1, stored=...) is
+    the stored item container (a typed item of width 1 is a copy whose one sub-item is the item), and never exceeds its items."""
     with _scope(ctx) as ctx:
         parts = [_source(x)[0] for x in items]
         lengths = [len(x) for x in parts]
         if checksum:
             from . import rcx
             d_src = _cuda(np.concatenate(parts) if parts else np.zeros(0, np.uint8))
-            payload, offsets, crcs = _encode_items(ctx, d_src, rcx.item_offsets(lengths), coder, True)
+            payload, offsets, crcs, _ = _encode_items(ctx, d_src, rcx.item_offsets(lengths), coder, True)
             return item_header_bytes(coder, lengths, offsets, crcs) + payload.tobytes()
         payload, offsets = ctx.encode_items(parts, coder=coder)
         return item_header_bytes(coder, lengths, offsets) + payload.tobytes()
@@ -479,9 +503,10 @@ def _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d
     return out
 
 
-def _pack_typed_items_device(ctx, parts, lengths, widths, preds, auto, coder: int, checksum: bool, directory: bytes) -> bytes:
+def _pack_typed_items_device(ctx, parts, lengths, widths, preds, auto, coder: int, checksum: bool, directory: bytes, gain=None) -> bytes:
     """parts: the items that have bytes -> the container: one gather (an upload unless all lie on the device), split, encode over
-    the sub-items, with checksum the CRC-32 of the sub-items of the split text, one download."""
+    the sub-items, with a gain the mix of the stored sub-items behind it (the rule is applied to what was coded, after predict="auto"
+    has decided), with checksum the CRC-32 of the sub-items of the split text, one download."""
     lengths = np.asarray(lengths, dtype=np.uint64)
     _typed_items_tables(lengths, widths, preds)
     nsub = int(widths.astype(np.int64).sum())
@@ -497,16 +522,20 @@ def _pack_typed_items_device(ctx, parts, lengths, widths, preds, auto, coder: in
         if auto.any():
             preds = _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d_split)
         typed_items.split_device(ctx, d_src, offs, widths, preds, d_split)
-        payload, offsets, crcs = _encode_items(ctx, d_split, sub_offs, coder, checksum)
-        return typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory) + payload.tobytes()
+        payload, offsets, crcs, raw = _encode_items(ctx, d_split, sub_offs, coder, checksum, gain)
+        return typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory, raw) + payload.tobytes()
 
 
-def pack_typed_items(items, widths=None, predict=None, coder: int = 0, ctx=None, checksum: bool = False, directory: bytes = b"") -> bytes:
+def pack_typed_items(items, widths=None, predict=None, coder: int = 0, ctx=None, checksum: bool = False, directory: bytes = b"", stored=None) -> bytes:
     """items: a list of buffers (bytes, numpy arrays, contiguous torch tensors on the CPU or the GPU) -> an RCXJ container.
     widths=None: each array's or tensor's element size (plain bytes need a width); else one width for all, or one per item.
     predict: None, "delta", "zigzag", "auto", or a list with one of these per item; "auto" decides per item from the measured
     order-0 costs (the module's docstring), and a width-1 item is never predicted.  One upload (none if every item lies on the
-    GPU), then split, encode over the sub-items and, with checksum=True, their CRC-32, all with the device calls."""
+    GPU), then split, encode over the sub-items and, with checksum=True, their CRC-32, all with the device calls.
+    stored=True | fraction: sub-items of the split text that do not shrink (by that fraction of their length) are kept raw and
+    decoded by copy, so the payload never exceeds the items; the container is version 2 if there is such a sub-item, else the one
+    written without the option.  With widths=1 that is the stored item container (pack_items has none)."""
+    gain = _gain(stored)
     sources = [_source(x) for x in items]
     if widths is None:
         each = [w for _, w in sources]
@@ -522,7 +551,7 @@ def pack_typed_items(items, widths=None, predict=None, coder: int = 0, ctx=None,
     preds, auto = _item_predictors(predict, w)
     parts = [x for x, _ in sources]
     lengths = np.array([_size(x) for x in parts], dtype=np.uint64)
-    return _pack_typed_items_device(ctx, parts, lengths, w, preds, auto, coder, checksum, directory)
+    return _pack_typed_items_device(ctx, parts, lengths, w, preds, auto, coder, checksum, directory, gain)
 
 
 def _unpack_typed_items_device(ctx, c, pick, verify: bool):
@@ -542,7 +571,12 @@ def _unpack_typed_items_device(ctx, c, pick, verify: bool):
     owner = np.repeat(pick, widths.astype(np.int64))
     soffs = typed_items.sub_offsets(doffs, widths)
     d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
-    ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), soffs, d_split, pick=subs.astype(np.uint64), coder=c["coder"])
+    if c.get("stored") is None:
+        ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), soffs, d_split, pick=subs.astype(np.uint64), coder=c["coder"])
+    else:  # version 2: the stored sub-items are copied
+        from . import stored as calls
+        calls.decode_device(ctx, _cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), c["stored"], soffs, d_split, pick=subs.astype(np.uint64),
+                            coder=c["coder"])
     ctx.sync_status()
     if verify and c["crcs"] is not None:
         ctx.verify_items_device(d_split, soffs, _cuda(c["crcs"][subs]))
@@ -570,11 +604,13 @@ def unpack_typed_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
 
 
 # ---- tensors with names, on top of the typed item container ---------------------------------------------------------------
-def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=None, checksum: bool = False) -> bytes:
+def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=None, checksum: bool = False, stored=None) -> bytes:
     """named: a dict of names -> numpy arrays or contiguous torch tensors (CPU or GPU) -> an RCXJ container whose directory
     names them.  Every tensor is cut into typed items of element_size * block bytes, its superblocks.  predict: None, a
     name or "auto" for all tensors, or a dict of names -> those (a name it lacks: none); tensors of 1-byte elements are never
-    predicted.  An element size outside 1, 2, 4, 8 raises ContainerError."""
+    predicted.  An element size outside 1, 2, 4, 8 raises ContainerError.  stored=True | fraction: as in pack_typed_items -- the
+    sub-items are the blocks pack_typed(..., stored=...) would keep raw, the low mantissa planes of floating-point tensors."""
+    gain = _gain(stored)
     import torch
     if not 16 <= block <= MAX_ITEM:
         raise ContainerError("a block is 16 bytes to RCX_MAX_BLOCK")
@@ -598,7 +634,7 @@ def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=No
             entry_preds += [None if width == 1 else each] * count
     w = np.array(widths, dtype=np.uint8)
     preds, auto = _item_predictors(entry_preds, w)
-    return _pack_typed_items_device(ctx, parts, np.array(lengths, dtype=np.uint64), w, preds, auto, coder, checksum, tensor_directory_bytes(entries))
+    return _pack_typed_items_device(ctx, parts, np.array(lengths, dtype=np.uint64), w, preds, auto, coder, checksum, tensor_directory_bytes(entries), gain)
 
 
 def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool = True) -> dict:

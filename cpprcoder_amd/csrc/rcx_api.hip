@@ -14,6 +14,7 @@
 #include "rcx_crc_api.hpp"  // CRC-32 per block or item
 #include "rcx_stats_api.hpp" // byte counts and order-0 cost per block or item (include/rcx_stats.h)
 #include "rcx_stored_api.hpp" // stored blocks: mix behind the block encode call, decode of any picks (include/rcx_stored.h)
+#include "rcx_stored_items_api.hpp" // stored items: the mix behind the item encode call (include/rcx_stored_items.h)
 #include "rcx_typed_api.hpp" // the byte-plane filter and the delta predictor in front of it (include/rcx_planes.h, rcx_predict.h)
 #include "rcx_typed_items_api.hpp" // the same per item: a width and a predictor of its own for every buffer (include/rcx_typed_items.h)
 

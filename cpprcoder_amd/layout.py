@@ -59,16 +59,17 @@ bytes.  Such a container is version 3 of either layout, and flag bit 2 (FLAG_STO
     the bitmap: ceil(nblocks / 8) bytes, block b is bit b & 7 of byte b >> 3, padding bits zero, at least one bit set; a
         stored block's two offsets are len_b apart
 The CRC stays the CRC of what the coder saw.  If no block ends up stored the container is, byte for byte, the one written
-without the option.  An item container has no stored items.
+without the option.  An item container (RCXI) has no stored items and no version 3: a typed item of width 1 is a copy whose one
+sub-item is the item, so the typed item container below, written with widths=1, IS the stored item container.
 
 The typed item container holds many buffers of differing sizes, each with an element width (1, 2, 4 or 8) and a predictor
 of its own (include/rcx_typed_items.h; cpprcoder_amd/typed_items.py): typed item i is transformed as one superblock of
 m_i = len_i // w_i elements, and its w_i planes -- the last one with the len_i % w_i tail bytes -- are the coder's items, the
 SUB-ITEMS, nsub = the sum of the widths; a sub-item of length 0 has no stream.  A fourth magic:
     0   4  magic  b"RCXJ"
-    4   1  version (1)
+    4   1  version (1; 2 with stored sub-items)
     5   1  coder
-    6   2  flags: bit 1 = checksums (FLAG_CRC32); every other bit 0
+    6   2  flags: bit 1 = checksums (FLAG_CRC32); bit 2 = stored sub-items (FLAG_STORED: version 2, and only there); other bits 0
     8   8  nitems
     16  8  nsub
     24  8  dlen, the bytes of the directory
@@ -76,10 +77,15 @@ SUB-ITEMS, nsub = the sum of the widths; a sub-item of length 0 has no stream.  
     ..  nitems          their widths
     ..  nitems          their predictors (include/rcx_predict.h: 0 none, 1 delta, 2 delta + zigzag; 0 with width 1)
     ..  8 * (nsub + 1)  offsets of the sub-item streams in the payload
+    ..  version 2: ceil(nsub / 8)  the bitmap of the stored sub-items, in the format above: sub-item s is bit s & 7 of byte
+        s >> 3, padding bits zero, at least one bit set
     ..  with bit 1: 4 * nsub  the CRC-32 of each sub-item of the SPLIT text (0 for an empty one)
     ..  dlen            the directory: the caller's bytes, carried and not interpreted (may be empty)
     ..  payload: the sub-item streams back to back
-There are no stored sub-items.  The tensor directory of pack_tensors is JSON: a list of {"name", "dtype" (torch's name),
+Stored sub-items (include/rcx_stored_items.h, cpprcoder_amd/stored_items.py): a sub-item whose stream did not shrink is kept as
+its raw bytes of the split text, its two offsets exactly its length apart; an empty sub-item is never stored.  Version 2 and
+bit 2 only ever appear together, and only if at least one sub-item is stored: else the container is, byte for byte, the one
+written without the option.  The CRC stays the CRC of the split text.  The tensor directory of pack_tensors is JSON: a list of {"name", "dtype" (torch's name),
 "shape", "first", "count"}, where the tensor is the typed items first .. first + count - 1.
 """
 import json
@@ -108,6 +114,7 @@ _TYPED_FIXED = struct.Struct("<4sBBHIQQB7s")
 WIDTHS = (2, 4, 8)
 TYPED_ITEMS_MAGIC = b"RCXJ"
 TYPED_ITEMS_VERSION = 1
+TYPED_ITEMS_VERSION_STORED = 2  # + the bitmap of the stored sub-items behind the offsets; always with FLAG_STORED
 _TYPED_ITEMS_FIXED = struct.Struct("<4sBBHQQQ")
 ITEM_WIDTHS = (1, 2, 4, 8)
 
@@ -170,13 +177,13 @@ class _Cursor:
     def crcs(self, checked: bool, count: int):
         return self.take(count, "<u4", "checksum table") if checked else None
 
-    def bitmap(self, nblocks: int) -> np.ndarray:
+    def bitmap(self, nblocks: int, none: str = "version 3 without a stored block") -> np.ndarray:
         """-> stored bool[nblocks]"""
         bits = np.unpackbits(self.take((nblocks + 7) // 8, np.uint8, "bitmap"), bitorder="little")
         if bits[nblocks:].any():
             raise ContainerError("a padding bit of the bitmap is set")
         if not bits[:nblocks].any():
-            raise ContainerError("version 3 without a stored block")
+            raise ContainerError(none)
         return bits[:nblocks].astype(bool)
 
     def payload(self, offsets, lengths=None, what: str = "an item") -> np.ndarray:
@@ -370,23 +377,44 @@ def _typed_items_tables(lengths, widths, preds):
     return lengths, widths, preds, sub
 
 
-def typed_items_header_bytes(coder: int, lengths, widths, preds, offsets, crcs=None, directory: bytes = b"") -> bytes:
+def _stored_subs_must_fit(stored, offsets, sub) -> None:
+    """A stored sub-item's stream is the sub-item: its two offsets are its length apart, and it has bytes."""
+    sizes = np.diff(np.asarray(offsets).astype(np.int64))
+    if np.any(np.asarray(sub)[stored] == 0):
+        raise ContainerError("an empty sub-item is never stored")
+    if np.any(sizes[stored] != np.asarray(sub).astype(np.int64)[stored]):
+        raise ContainerError("a stored sub-item is not as long as its bytes")
+
+
+def typed_items_header_bytes(coder: int, lengths, widths, preds, offsets, crcs=None, directory: bytes = b"", stored=None) -> bytes:
+    """stored: one flag per sub-item, or None; version 2 if one is set, else the header without the option."""
     lengths, widths, preds, sub = _typed_items_tables(lengths, widths, preds)
     offsets = np.ascontiguousarray(offsets, dtype="<u8")
     if len(offsets) != len(sub) + 1:
         raise ContainerError("offsets do not match the number of sub-items")
     flags, table = _with_crcs(0, crcs, len(sub), "sub-item")
+    version, bitmap = TYPED_ITEMS_VERSION, b""
+    if stored is not None:
+        stored = np.asarray(stored) != 0
+        if len(stored) != len(sub):
+            raise ContainerError("one stored flag per sub-item")
+        if stored.any():
+            _stored_subs_must_fit(stored, offsets, sub)
+            version, flags, bitmap = TYPED_ITEMS_VERSION_STORED, flags | FLAG_STORED, np.packbits(stored, bitorder="little").tobytes()
     directory = bytes(directory)
-    return (_TYPED_ITEMS_FIXED.pack(TYPED_ITEMS_MAGIC, TYPED_ITEMS_VERSION, coder, flags, len(lengths), len(sub), len(directory)) + lengths.tobytes()
-            + widths.tobytes() + preds.tobytes() + offsets.tobytes() + table + directory)
+    return (_TYPED_ITEMS_FIXED.pack(TYPED_ITEMS_MAGIC, version, coder, flags, len(lengths), len(sub), len(directory)) + lengths.tobytes()
+            + widths.tobytes() + preds.tobytes() + offsets.tobytes() + bitmap + table + directory)
 
 
 def parse_typed_items(blob):
     """-> dict(coder, flags, nitems, nsub, lengths uint64[nitems], widths uint8[nitems], preds uint8[nitems], sub_first int64[nitems + 1],
-    sub_lengths uint64[nsub], offsets uint64[nsub + 1], crcs uint32[nsub] or None, directory bytes, payload uint8 view)"""
+    sub_lengths uint64[nsub], offsets uint64[nsub + 1], crcs uint32[nsub] or None, directory bytes, payload uint8 view); a
+    version 2 container has one key more, stored bool[nsub] -- .get("stored") is None for version 1, whose result is what it always was"""
     cur = _Cursor(blob, _TYPED_ITEMS_FIXED, TYPED_ITEMS_MAGIC)
     _, version, coder, flags, nitems, nsub, dlen = cur.fields
-    if version != TYPED_ITEMS_VERSION or flags & ~FLAG_CRC32:
+    has_bitmap = version == TYPED_ITEMS_VERSION_STORED  # bit 2 in version 2, and always there
+    if version not in (TYPED_ITEMS_VERSION, TYPED_ITEMS_VERSION_STORED) or flags & ~(FLAG_CRC32 | (FLAG_STORED if has_bitmap else 0)) or (
+            has_bitmap and not flags & FLAG_STORED):
         raise ContainerError("unsupported container version, coder or flags")
     if dlen > len(cur.buf):
         raise ContainerError("truncated tables")
@@ -398,12 +426,18 @@ def parse_typed_items(blob):
     if len(sub) != nsub:
         raise ContainerError("the widths do not add up to the number of sub-items")
     offsets = cur.take(nsub + 1, "<u8", "tables")
+    stored = cur.bitmap(nsub, "version 2 without a stored sub-item") if has_bitmap else None
     crcs = cur.crcs(bool(flags & FLAG_CRC32), nsub)
     directory = bytes(cur.take(dlen, np.uint8, "directory"))
     payload = cur.payload(offsets, sub, "a sub-item")
+    if stored is not None:
+        _stored_subs_must_fit(stored, offsets, sub)
     sub_first = np.concatenate([[0], np.cumsum(widths.astype(np.int64))])
-    return {"coder": coder, "flags": flags, "nitems": nitems, "nsub": nsub, "lengths": lengths, "widths": widths, "preds": preds, "sub_first": sub_first,
-            "sub_lengths": sub.astype(np.uint64), "offsets": offsets, "crcs": crcs, "directory": directory, "payload": payload}
+    out = {"coder": coder, "flags": flags, "nitems": nitems, "nsub": nsub, "lengths": lengths, "widths": widths, "preds": preds, "sub_first": sub_first,
+           "sub_lengths": sub.astype(np.uint64), "offsets": offsets, "crcs": crcs, "directory": directory, "payload": payload}
+    if stored is not None:  # (a version 1 container parses to exactly what it always did: read the key with .get("stored"))
+        out["stored"] = stored
+    return out
 
 
 # ---- the tensor directory ------------------------------------------------------------------------------------------------------
