@@ -88,7 +88,8 @@ __device__ __forceinline__ u32 rcx_oct_excl_scan(u32 x, u32 m1, u32 m2, u32 m4)
 //   group: row n (256 bytes) holds node n of all four, block s in quarter s; whatever nodes the four quads
 //   ask for, they read different quarters.  (One table per block: 16 of the 36 LDS cycles per symbol were
 //   bank conflicts.)  Row 16 is scratch ("node 16"): per block three 16-byte groups of decoded output
-//   waiting for the fourth, then 16 bytes where skipped ring writes go.
+//   waiting for the fourth (the loops of 16 symbols; the adaptive decoder's pass of 64 keeps its four groups in
+//   registers and puts nothing there), then 16 bytes where skipped ring writes go.
 //   A ring is 32 dwords + slot 32 (repeats slot 0) + 12 spare bytes; 36 dwords apart, the rings of the 8
 //   quads of a half-wave start 4 banks apart.
 #define RCX_QUAD_GROUP_BYTES 4352
@@ -436,9 +437,9 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 
     const u32 maxlen = rcx_wave_max(len);
     u8* out = dst + at;
-    // The fast loop (16 symbols at a go, no per-symbol length test, 16-byte stores) runs as far as every block of the
-    // wave has whole groups of 16 and its output is 16-byte aligned; the rest -- the ragged end of a buffer's last
-    // block, the whole wave if an output is unaligned -- is decoded symbol by symbol behind it.
+    // The fast loops (a pass of 64 symbols, then 16 symbols at a go; no per-symbol length test, 16-byte stores) run as
+    // far as every block of the wave has whole groups of 16 and its output is 16-byte aligned; the rest -- the ragged
+    // end of a buffer's last block, the whole wave if an output is unaligned -- is decoded symbol by symbol behind them.
     // The item geometry keeps the fast loop whatever the outputs' alignment (an item begins where the one before it
     // ends): all quads stay at the same symbol index, and the 16-byte stores go to byte addresses (rcx_store16).
     u32 fast_end;
@@ -667,14 +668,11 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #endif
         U4 dm0, dm1, dm2, dm3, di0, di1, di2, di3;
         RCX_QUAD_DIVQ_LOAD(0u, 0) RCX_QUAD_DIVQ_LOAD(0u, 1) RCX_QUAD_DIVQ_LOAD(0u, 2) RCX_QUAD_DIVQ_LOAD(0u, 3)
-        for (u32 i0 = 0; i0 < fast_end; i0 += 16) {
-            in.topup();
-            RCX_QUAD_PARKED_FLUSH(i0, seat.parked, o_last, G::items)
-            u32 w0_ = 0, w1_ = 0, w2_ = 0, w3_ = 0;
-            const u32 sh_ = 31u - (u32)__builtin_clz(256u + i0); // floor(log2(total)), the group's shift
-            const u32 gn_ = (i0 >> 4) + 1u;                      // the next group
+        // These eight are waited for here, once, by a statement that reads them.  Left pending into the loops, the order the
+        // compiler gave them (the first quarter last) decides what the loop's first vmcnt wait allows for every pass, not
+        // only the first: vmcnt(1), which waits for the stores in front of it and for the piece just requested.
+        asm volatile("" ::"v"(dm0.x), "v"(di0.x), "v"(dm1.x), "v"(di1.x), "v"(dm2.x), "v"(di2.x), "v"(dm3.x), "v"(di3.x));
 #if defined(RCX_STAMP_DEC)
-            unsigned long long stamp_t_[4] = {0, 0, 0, 0};
 #define RCX_QUAD_STEP(S, Q, HP, PW)                                                                           \
     {                                                                                                        \
         const bool stamp_now_ = (S) == 8 || (S) == 9;                                                        \
@@ -686,30 +684,79 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #define RCX_QUAD_STEP(S, Q, HP, PW)                                                                           \
     RCX_QUAD_DEC_SYMBOL(RCX_QUAD_U4_AT(dm##Q, (S) & 3), RCX_QUAD_U4_AT(di##Q, (S) & 3), sh_, HP, PW, (8 * (((S) + 3) & 3)));
 #endif
-            // (a step makes the byte of the step before it: RCX_QUAD_DEC_SYMBOL)
-            RCX_QUAD_STEP(0, 0, 0, w0_) RCX_QUAD_STEP(1, 0, 1, w0_) RCX_QUAD_STEP(2, 0, 1, w0_) RCX_QUAD_STEP(3, 0, 1, w0_)
-            RCX_QUAD_DIVQ_LOAD(gn_, 0)
-            RCX_QUAD_STEP(4, 1, 1, w0_) RCX_QUAD_STEP(5, 1, 1, w1_) RCX_QUAD_STEP(6, 1, 1, w1_) RCX_QUAD_STEP(7, 1, 1, w1_)
-            RCX_QUAD_DIVQ_LOAD(gn_, 1)
-            RCX_QUAD_STEP(8, 2, 1, w1_) RCX_QUAD_STEP(9, 2, 1, w2_) RCX_QUAD_STEP(10, 2, 1, w2_) RCX_QUAD_STEP(11, 2, 1, w2_)
-            RCX_QUAD_DIVQ_LOAD(gn_, 2)
-            RCX_QUAD_STEP(12, 3, 1, w2_) RCX_QUAD_STEP(13, 3, 1, w3_) RCX_QUAD_STEP(14, 3, 1, w3_) RCX_QUAD_STEP(15, 3, 1, w3_)
-            RCX_QUAD_DIVQ_LOAD(gn_, 3)
-            RCX_QUAD_DEC_FINISH(w3_, 24)
-#undef RCX_QUAD_STEP
+// A group: 16 symbols with the shift sh_, the divisors of group GN loaded behind each quarter, the quad's 16 bytes into O
+// (a step makes the byte of the step before it: RCX_QUAD_DEC_SYMBOL)
+#define RCX_QUAD_GROUP(GN, O)                                                                                 \
+    {                                                                                                        \
+        u32 w0_ = 0, w1_ = 0, w2_ = 0, w3_ = 0;                                                              \
+        RCX_QUAD_STEP(0, 0, 0, w0_) RCX_QUAD_STEP(1, 0, 1, w0_) RCX_QUAD_STEP(2, 0, 1, w0_) RCX_QUAD_STEP(3, 0, 1, w0_) \
+        RCX_QUAD_DIVQ_LOAD(GN, 0)                                                                            \
+        RCX_QUAD_STEP(4, 1, 1, w0_) RCX_QUAD_STEP(5, 1, 1, w1_) RCX_QUAD_STEP(6, 1, 1, w1_) RCX_QUAD_STEP(7, 1, 1, w1_) \
+        RCX_QUAD_DIVQ_LOAD(GN, 1)                                                                            \
+        RCX_QUAD_STEP(8, 2, 1, w1_) RCX_QUAD_STEP(9, 2, 1, w2_) RCX_QUAD_STEP(10, 2, 1, w2_) RCX_QUAD_STEP(11, 2, 1, w2_) \
+        RCX_QUAD_DIVQ_LOAD(GN, 2)                                                                            \
+        RCX_QUAD_STEP(12, 3, 1, w2_) RCX_QUAD_STEP(13, 3, 1, w3_) RCX_QUAD_STEP(14, 3, 1, w3_) RCX_QUAD_STEP(15, 3, 1, w3_) \
+        RCX_QUAD_DIVQ_LOAD(GN, 3)                                                                            \
+        RCX_QUAD_DEC_FINISH(w3_, 24)                                                                         \
+        (O).x = rcx_quad_or(w0_);                                                                            \
+        (O).y = rcx_quad_or(w1_);                                                                            \
+        (O).z = rcx_quad_or(w2_);                                                                            \
+        (O).w = rcx_quad_or(w3_);                                                                            \
+    }
+        u32 i0 = 0;
+#if !defined(RCX_STAMP_DEC) /* (the diagnostic build times symbols of the loop of 16 below, so there that loop runs alone) */
+        // The pass: 64 symbols, four groups with their top-ups, while every block of the wave has them.  Which of the four
+        // a group is, is known when the kernel is compiled, so the 64 bytes wait in registers -- the scratch row takes none
+        // of them --, they leave as four stores behind the NEXT pass's first top-up (the rule above), and the shift (the
+        // powers of two from 256 up are multiples of 64), the test for the stores and the loop's own instructions are
+        // issued once per 64 symbols where the loop of 16 issues them four times.
+        {
+            U4 o_p0 = o_last, o_p1 = o_last, o_p2 = o_last;
+            for (; i0 + 64 <= fast_end; i0 += 64) {
+                in.topup();
+                if (i0 != 0 && leader) {
+                    u8* o4 = out + (i0 - 64);
+                    rcx_store16<G::items>(o4, o_p0);
+                    rcx_store16<G::items>(o4 + 16, o_p1);
+                    rcx_store16<G::items>(o4 + 32, o_p2);
+                    rcx_store16<G::items>(o4 + 48, o_last);
+                }
+                const u32 sh_ = 31u - (u32)__builtin_clz(256u + i0); // floor(log2(total)), the same for the four groups
+                const u32 gn_ = (i0 >> 4) + 1u;
+                RCX_QUAD_GROUP(gn_, o_p0)
+                in.topup();
+                RCX_QUAD_GROUP(gn_ + 1u, o_p1)
+                in.topup();
+                RCX_QUAD_GROUP(gn_ + 2u, o_p2)
+                in.topup();
+                RCX_QUAD_GROUP(gn_ + 3u, o_last)
+            }
+            // The last pass's 64 bytes go where the loop of 16 keeps its own: it starts at a multiple of 64 and sends them
+            // off behind its first top-up, or RCX_QUAD_PARKED_END does.
+            if (i0 != 0) seat.parked[0] = o_p0, seat.parked[1] = o_p1, seat.parked[2] = o_p2;
+        }
+#endif
+        // The whole groups that are left (fewer than four behind the pass), their output parked as the macros above say.
+        for (; i0 < fast_end; i0 += 16) {
+            in.topup();
+            RCX_QUAD_PARKED_FLUSH(i0, seat.parked, o_last, G::items)
+            const u32 sh_ = 31u - (u32)__builtin_clz(256u + i0); // floor(log2(total)), the group's shift
+            const u32 gn_ = (i0 >> 4) + 1u;                      // the next group
+#if defined(RCX_STAMP_DEC)
+            unsigned long long stamp_t_[4] = {0, 0, 0, 0};
+#endif
+            U4 o;
+            RCX_QUAD_GROUP(gn_, o)
 #if defined(RCX_STAMP_DEC)
             stamp_sum_[0] += stamp_t_[1] - stamp_t_[0]; // symbol 8: leaf read issued -> round 2 done
             stamp_sum_[1] += stamp_t_[2] - stamp_t_[1]; // -> leaf read of symbol 9 issued
             stamp_sum_[2] += stamp_t_[3] - stamp_t_[2]; // symbol 9: leaf read issued -> round 2 done
             stamp_sum_[3] += 1;
 #endif
-            U4 o;
-            o.x = rcx_quad_or(w0_);
-            o.y = rcx_quad_or(w1_);
-            o.z = rcx_quad_or(w2_);
-            o.w = rcx_quad_or(w3_);
             RCX_QUAD_PARKED_PUT(o, seat.parked, o_last);
         }
+#undef RCX_QUAD_GROUP
+#undef RCX_QUAD_STEP
 #if defined(RCX_STAMP_DEC)
         if (blockIdx.x == 7 && threadIdx.x == 0)
             for (int i_ = 0; i_ < 4; ++i_) rcx_dec_stamp_out[i_] = stamp_sum_[i_];
