@@ -1,7 +1,7 @@
 """python -m cpprcoder_amd c|d|t ...  -- compress / decompress / test files with the MI355X block coder.
 
     python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag|auto]] [--crc] [--stored [FRACTION]]
-                              [--static | --coder adaptive|static|rans|rans8] IN OUT
+                              [--base FILE [--base-op xor|sub|subzz]] [--static | --coder adaptive|static|rans|rans8] IN OUT
                                                                IN -> RCXB container (cpprcoder_amd/layout.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
                                                                --planes W: IN is elements of W = 2, 4 or 8 bytes (bf16,
@@ -21,17 +21,32 @@
                                                                kept as its raw bytes and decoded by copy
                                                                (include/rcx_stored.h): the container never grows past its
                                                                input, and the line printed says "stored K/N" blocks.  In
-                                                               front of IN write --stored=FRACTION, or another option behind it
-    python -m cpprcoder_amd d [--no-verify] IN OUT             container (RCXB or RCXT, told apart by the magic; an RCXI
+                                                               front of IN write --stored=FRACTION, or another option behind it;
+                                                               --base FILE: IN differs a little from FILE, which has the same
+                                                               size and which the reader holds as well (the checkpoint before,
+                                                               the base model, the last snapshot): every element becomes its
+                                                               residual against FILE's element first (include/rcx_base.h;
+                                                               --base-op: xor, sub, or subzz, the default, the zigzagged
+                                                               difference) -> RCXD container, which carries a CRC-32 per
+                                                               block of FILE.  With --planes W the elements are W bytes wide,
+                                                               without it 1 byte (fp8, bytes); not with --blksort or
+                                                               --predict.  Against an unrelated FILE the container grows
+    python -m cpprcoder_amd d [--no-verify] [--base FILE] IN OUT
+                                                               container (RCXB, RCXT or RCXD, told apart by the magic; an RCXI
                                                                container holds items, not a file) -> original bytes.
+                                                               An RCXD container needs --base FILE, the file it was packed
+                                                               against: without it, or with a FILE of another size or
+                                                               content, the problem is named on stderr, the exit status is 1
+                                                               and OUT is not written.
                                                                A container with checksums
                                                                is verified: on a mismatch the bad block is named on
                                                                stderr, the exit status is 1 and OUT is not written
                                                                (--no-verify: write what the decoder produced)
-    python -m cpprcoder_amd t [--crc] [--stored [FRACTION]] [--planes W [--predict delta|zigzag|auto]] FILE...
+    python -m cpprcoder_amd t [--crc] [--stored [FRACTION]] [--planes W [--predict delta|zigzag|auto]] [--base BASE [--base-op OP]] FILE...
                                                                the reference harness's row per file
                                                                (|file|ratio|encode|decode|, test/main.cpp:346-356):
-                                                               pack, unpack, compare, times incl. PCIe copies
+                                                               pack, unpack, compare, times incl. PCIe copies;
+                                                               --base BASE: each FILE against BASE, as with c and d
 """
 import argparse
 import sys
@@ -39,6 +54,7 @@ import time
 
 
 CODERS = ("adaptive", "static", "rans", "rans8")  # include/rcx.h: RCX_CODER_*
+BASE_OPS = ("xor", "sub", "subzz")                # include/rcx_base.h: RCX_BASE_XOR, RCX_BASE_SUB, RCX_BASE_SUBZZ
 PREDICTORS = ("delta", "zigzag", "auto")          # include/rcx_predict.h: RCX_PRED_DELTA, RCX_PRED_ZIGZAG; auto: container.pick_predictor
 
 
@@ -51,12 +67,17 @@ def _fraction(text: str) -> float:
 
 
 class _Parser(argparse.ArgumentParser):
-    """One rule argparse has no word for: --predict without --planes is an argument error."""
+    """Rules argparse has no word for: --predict without --planes is an argument error, and so is --base with --blksort or
+    --predict, or --base-op without --base."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
         if getattr(a, "predict", None) and not a.planes:
             self.error("--predict needs --planes W: the predictor works on elements")
+        if getattr(a, "base", None) and (getattr(a, "blksort", False) or getattr(a, "predict", None)):
+            self.error("--base goes with --planes W or alone (width 1), not with --blksort or --predict")
+        if getattr(a, "base_op", None) and not a.base:
+            self.error("--base-op needs --base FILE")
         return a
 
 
@@ -73,10 +94,13 @@ def parser() -> argparse.ArgumentParser:
     c.add_argument("--predict", choices=PREDICTORS, default=None)
     c.add_argument("--crc", action="store_true")
     c.add_argument("--stored", nargs="?", type=_fraction, const=True, default=None, metavar="FRACTION")
+    c.add_argument("--base", default=None, metavar="FILE")
+    c.add_argument("--base-op", choices=BASE_OPS, default=None)
     c.add_argument("src")
     c.add_argument("dst")
     d = sub.add_parser("d")
     d.add_argument("--no-verify", action="store_true")
+    d.add_argument("--base", default=None, metavar="FILE")
     d.add_argument("src")
     d.add_argument("dst")
     t = sub.add_parser("t")
@@ -89,6 +113,8 @@ def parser() -> argparse.ArgumentParser:
     t.add_argument("--predict", choices=PREDICTORS, default=None)
     t.add_argument("--crc", action="store_true")
     t.add_argument("--stored", nargs="?", type=_fraction, const=True, default=None, metavar="FRACTION")
+    t.add_argument("--base", default=None, metavar="FILE")
+    t.add_argument("--base-op", choices=BASE_OPS, default=None)
     t.add_argument("files", nargs="+")
     return ap
 
@@ -99,12 +125,20 @@ def main(argv=None) -> int:
     coder = CODERS.index(a.coder) if getattr(a, "coder", None) else (1 if getattr(a, "static", False) else 0)
     ctx = rcx.Context(0)
 
+    base = open(a.base, "rb").read() if getattr(a, "base", None) else None
+
     def pack(data):
+        if base is not None:
+            return container.pack_delta(data, base, a.planes or 1, a.block, coder, ctx, checksum=a.crc, stored=a.stored, op=a.base_op or "subzz")
         if a.planes:
             return container.pack_typed(data, a.planes, a.block, coder, ctx, checksum=a.crc, predict=a.predict, stored=a.stored)
         return container.pack(data, a.block, coder, ctx, blksort=a.blksort, checksum=a.crc, stored=a.stored)
 
     def unpack(blob, verify=True):
+        if bytes(blob[:4]) == container.DELTA_MAGIC:
+            if base is None:
+                raise container.ContainerError("an RCXD container holds a residual: give the file it was packed against with --base FILE")
+            return container.unpack_delta(blob, base, ctx, verify=verify)
         if bytes(blob[:4]) == container.TYPED_MAGIC:
             return container.unpack_typed(blob, ctx, verify=verify)
         if bytes(blob[:4]) == container.ITEM_MAGIC:
@@ -117,7 +151,7 @@ def main(argv=None) -> int:
         typed = bytes(blob[:4]) == container.TYPED_MAGIC
         out = ""
         if getattr(a, "stored", None) is not None:
-            c = container.parse_typed(blob) if typed else container.parse(blob)
+            c = container.parse_delta(blob)["inner"] if bytes(blob[:4]) == container.DELTA_MAGIC else container.parse_typed(blob) if typed else container.parse(blob)
             out += f" stored {0 if c['stored'] is None else int(c['stored'].sum())}/{c['nblocks']}"
         if getattr(a, "predict", None) == "auto":
             out += " predict=" + ("none", "delta", "zigzag")[container.parse_typed(blob)["pred"]]
@@ -131,9 +165,15 @@ def main(argv=None) -> int:
             print(f"{a.src}: {len(data)} -> {len(blob)} bytes ({len(blob) / max(len(data), 1):.6f})" + chosen(blob))
         elif a.cmd == "d":
             try:
-                out = unpack(open(a.src, "rb").read(), verify=not a.no_verify)
+                blob = open(a.src, "rb").read()
+                out = unpack(blob, verify=not a.no_verify)
             except container.ChecksumError as e:
                 print(f"{a.src}: {e}; nothing written", file=sys.stderr)
+                return 1
+            except container.ContainerError as e:
+                if bytes(blob[:4]) != container.DELTA_MAGIC:
+                    raise
+                print(f"{a.src}: {e}; nothing written", file=sys.stderr)  # no base, or one of another size or content
                 return 1
             open(a.dst, "wb").write(out)
             print(f"{a.src}: {len(out)} bytes")

@@ -5,7 +5,7 @@ block engine needs to be usable on files.  Every block's stream inside is bit-ex
 AdaptiveRangeEncoder (or RangeEncoder, coder = 1; rANS::encode, coder = 2; rANS::encode_simd, coder = 3) emits
 for that block, so a reader with only the reference can decode a container block by block.
 
-The four layouts -- RCXB blocks, RCXI items, RCXT typed blocks, RCXJ typed items -- their header writers and parsers are
+The five layouts -- RCXB blocks, RCXI items, RCXT typed blocks, RCXJ typed items, RCXD residuals -- their header writers and parsers are
 cpprcoder_amd/layout.py, plain Python, and every public name of it is a name of this module too.  pack()/unpack() and
 their kin here go through the HIP library (there is no CPU coder: without librcx.so and a GPU they raise), except where there
 is nothing to code or decode.
@@ -50,16 +50,30 @@ cpprcoder_amd/stored_items.py): the same option with the sub-item in the block's
 an empty sub-item is never stored, and unpack goes through the decode call that copies.  The container is RCXJ version 2 if a
 sub-item ends up stored, else byte for byte the one written without the option.  RCXI has no such version:
 pack_typed_items(items, widths=1, stored=True) is the stored item container.
+
+Residuals against a base (pack_delta(data, base, ...); include/rcx_base.h, cpprcoder_amd/base.py): for a buffer that differs a
+little from one the reader already has -- a checkpoint against the one before, a fine-tuned model against its base model, a
+counter table against its last snapshot.  Every element becomes its residual against the base's element at the same place
+(op="xor", "sub" or "subzz", the zigzagged difference), and the residuals' split text is coded as pack_typed codes it (width 1:
+as pack codes it), so checksum=, stored= and every coder come with it.  The container is RCXD: a prefix and that inner container
+(layout.py).  Against an unrelated base the payload grows by some 5 %, so the option is never chosen for the caller.  The
+residual decodes correctly whatever the base is, so the inner checksums cannot catch a wrong base: with base_check (the
+default) the prefix carries the CRC-32 of every block of the base, and unpack_delta and unpack_delta_range verify the base they
+are given against it, on the device, before anything is decoded -- BaseMismatchError names the first bad block of the base.
+unpack_delta_range decodes the blocks of the superblocks that cover the range, verifies only those blocks of the base and joins
+the span against the same span of the base: the transform is elementwise.  Not here: tensors by name against a base
+(pack_tensors), an op chosen by measurement, chains of deltas, bases of another length.
 """
 import contextlib
 
 import numpy as np
 
-from .layout import (FLAG_BLKSORT, FLAG_CRC32, FLAG_STORED, ITEM_MAGIC, ITEM_VERSION, ITEM_WIDTHS, MAGIC, MAX_ITEM, PREDICTORS,  # noqa: F401
+from .layout import (BASE_OPS, DELTA_FLAG_BASE_CRC, DELTA_MAGIC, DELTA_VERSION, FLAG_BLKSORT, FLAG_CRC32, FLAG_STORED, ITEM_MAGIC, ITEM_VERSION,  # noqa: F401
+                     ITEM_WIDTHS, MAGIC, MAX_ITEM, PREDICTORS,
                      TYPED_ITEMS_MAGIC, TYPED_ITEMS_VERSION, TYPED_ITEMS_VERSION_STORED, TYPED_MAGIC, TYPED_VERSION, TYPED_VERSION_PRED, TYPED_VERSION_STORED, VERSION,
-                     VERSION_CRC, VERSION_STORED, WIDTHS, ChecksumError, ContainerError, _typed_items_tables, block_lengths, coded_size,
-                     header_bytes, item_header_bytes, parse, parse_items, parse_tensor_directory, parse_typed, parse_typed_items,
-                     tensor_directory_bytes, typed_header_bytes, typed_items_header_bytes)
+                     VERSION_CRC, VERSION_STORED, WIDTHS, BaseMismatchError, ChecksumError, ContainerError, _typed_items_tables, block_lengths, coded_size,
+                     delta_header_bytes, header_bytes, item_header_bytes, parse, parse_delta, parse_items, parse_tensor_directory, parse_typed,
+                     parse_typed_items, tensor_directory_bytes, typed_header_bytes, typed_items_header_bytes)
 
 AUTO = "auto"  # pack_typed(predict=AUTO): measured, see pick_predictor; never in a container
 
@@ -448,6 +462,122 @@ def unpack_typed_range(blob, start: int, stop: int, ctx=None, verify: bool = Tru
         predictor.join_device(ctx, d_split[:span], width, block, c["pred"], d_out)
         out = d_out.cpu().numpy()
     return out[start - first * superblock: stop - first * superblock].tobytes()
+
+
+# ---- RCXD: residuals against a base in front of the plane filter -------------------------------------------------------------------
+def _on_device(src):
+    return src if hasattr(src, "numel") else _cuda(src)
+
+
+def _verify_base_device(ctx, d_ref, block: int, crcs, first: int = 0) -> None:
+    """d_ref: the base's bytes from its block `first` on, on the device; crcs: the table's entries for them."""
+    from . import rcx
+    ctx.verify_blocks_device(d_ref, block, _cuda(crcs))
+    st, bad = ctx.sync_status(raise_on_error=False)
+    if st == rcx.E_CORRUPT:
+        raise BaseMismatchError(first + int(bad))
+    if st != rcx.OK:
+        raise rcx.RcxError(st, f"base block {bad}")
+
+
+def pack_delta(data, base, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False, stored=None, op: str = "subzz",
+               base_check: bool = True) -> bytes:
+    """data, base: each bytes, a numpy array or a contiguous torch tensor (CPU or GPU), of the same byte length -> an RCXD
+    container of data's residual against base.  width=None: the element size of `data` (plain bytes need a width; 1, 2, 4 or
+    8).  op: "xor", "sub" or "subzz" (include/rcx_base.h).  One upload each (none for GPU tensors), the residual and its planes in
+    one kernel, then encode, mix and CRC-32 of the split text exactly as pack_typed does them; checksum= and stored= are the
+    inner container's.  base_check: the CRC-32 of every block of the base goes into the prefix, the only guard against
+    unpacking with another base."""
+    gain = _gain(stored)
+    if not isinstance(op, str) or op not in BASE_OPS:
+        raise ContainerError(f"an op is 'xor', 'sub' or 'subzz', not {op!r}")
+    src, size = _source(data)
+    ref = _source(base)[0]
+    width = size if width is None else width
+    if width is None:
+        raise ContainerError("plain bytes have no element size: give the width")
+    if width not in ITEM_WIDTHS:
+        raise ContainerError(f"an element is 1, 2, 4 or 8 bytes wide, not {width}")
+    n = _size(src)
+    if _size(ref) != n:
+        raise ContainerError(f"the base has {_size(ref)} bytes, the data {n}: a base is as long as the data")
+
+    def inner(offsets, crcs, raw):
+        if width == 1:
+            return header_bytes(coder, block, n, offsets, 0, crcs, raw)
+        return typed_header_bytes(coder, block, n, width, offsets, crcs, 0, raw)
+
+    if n == 0:
+        none = np.zeros(0, np.uint32)
+        return delta_header_bytes(BASE_OPS[op], width, block, 0, none if base_check else None) + inner(np.zeros(1, np.uint64), none if checksum else None, None)
+    import torch
+    from . import base as calls, rcx
+    with _scope(ctx) as ctx:
+        d_src, d_ref = _on_device(src), _on_device(ref)
+        d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
+        calls.split_device(ctx, d_src, d_ref, width, block, BASE_OPS[op], d_split)
+        if base_check:
+            d_guard = torch.zeros(rcx.block_count(n, block), dtype=torch.int32, device="cuda")
+            ctx.crc32_blocks_device(d_ref, block, d_guard)
+        payload, offsets, crcs, raw = _encode_blocks(ctx, d_split, block, coder, checksum, gain)  # (one sync: the base's CRCs are there too)
+        return delta_header_bytes(BASE_OPS[op], width, block, n, _crcs_of(d_guard) if base_check else None) + inner(offsets, crcs, raw) + payload.tobytes()
+
+
+def _delta_base(c, base):
+    ref = _source(base)[0]
+    if _size(ref) != c["n"]:
+        raise ContainerError(f"the base has {_size(ref)} bytes, the container was packed against one of {c['n']}")
+    return ref
+
+
+def unpack_delta(blob, base, ctx=None, verify: bool = True) -> bytes:
+    """The base is verified against the prefix's table first (if it has one; verify=False skips that and the inner checksums),
+    then decode as unpack_typed / unpack do, then the join against the base."""
+    import torch
+    from . import base as calls
+    c = parse_delta(blob)
+    ref = _delta_base(c, base)
+    n = c["n"]
+    if n == 0:
+        return b""
+    with _scope(ctx) as ctx:
+        d_ref = _on_device(ref)
+        if verify and c["base_crcs"] is not None:
+            _verify_base_device(ctx, d_ref, c["block"], c["base_crcs"])
+        d_split = _decode_all_device(ctx, c["inner"], n, verify)
+        d_out = torch.empty(n, dtype=torch.uint8, device="cuda")
+        calls.join_device(ctx, d_split, d_ref, c["width"], c["block"], c["op"], d_out)
+        return d_out.cpu().numpy().tobytes()
+
+
+def unpack_delta_range(blob, base, start: int, stop: int, ctx=None, verify: bool = True) -> bytes:
+    """The bytes [start, stop) of the original: only the blocks of the superblocks that cover them are decoded (and, with
+    inner checksums, verified), only those blocks of the base are verified, and the span is joined against the same span of
+    the base as a buffer of its own."""
+    import torch
+    from . import base as calls
+    c = parse_delta(blob)
+    ref = _delta_base(c, base)
+    n, block, width, inner = c["n"], c["block"], c["width"], c["inner"]
+    if not 0 <= start <= stop <= n:
+        raise ContainerError("range outside the data")
+    if start == stop:
+        return b""
+    superblock = width * block
+    first, last = start // superblock, (stop - 1) // superblock
+    pick = np.arange(first * width, min(inner["nblocks"], (last + 1) * width), dtype=np.uint64)
+    lo, hi = first * superblock, min(n, (last + 1) * superblock)
+    with _scope(ctx) as ctx:
+        d_ref = _on_device(ref[lo:hi])
+        if verify and c["base_crcs"] is not None:  # a superblock is whole blocks of the base: its blocks first * width ..
+            _verify_base_device(ctx, d_ref, block, c["base_crcs"][first * width: first * width + (hi - lo + block - 1) // block], first * width)
+        d_split, doffs = _decode_picked_device(ctx, inner, block_lengths(n, block), pick, "block", verify and inner["crcs"] is not None)
+        if int(doffs[-1]) != hi - lo:
+            raise ContainerError("decoded size differs from the header")
+        d_out = torch.empty(hi - lo, dtype=torch.uint8, device="cuda")
+        calls.join_device(ctx, d_split[: hi - lo], d_ref, width, block, c["op"], d_out)
+        out = d_out.cpu().numpy()
+    return out[start - lo: stop - lo].tobytes()
 
 
 # ---- RCXJ: a width and a predictor per buffer, in front of the item calls -----------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The four on-disk layouts of cpprcoder_amd/container.py, and nothing else: header writers, parsers, the tensor directory.
+"""The five on-disk layouts of cpprcoder_amd/container.py, and nothing else: header writers, parsers, the tensor directory.
 Plain Python and numpy: no torch, no library, no GPU.  All integers little-endian.
 
 The block container, one buffer cut into blocks of one size:
@@ -87,6 +87,24 @@ its raw bytes of the split text, its two offsets exactly its length apart; an em
 bit 2 only ever appear together, and only if at least one sub-item is stored: else the container is, byte for byte, the one
 written without the option.  The CRC stays the CRC of the split text.  The tensor directory of pack_tensors is JSON: a list of {"name", "dtype" (torch's name),
 "shape", "first", "count"}, where the tensor is the typed items first .. first + count - 1.
+
+The delta container holds one buffer of 1-, 2-, 4- or 8-byte elements as its residual against a BASE, a second buffer of the
+same length that the reader holds as well (include/rcx_base.h; cpprcoder_amd/base.py): a prefix that names the transform and
+guards the base, and behind it a complete container of the residual's split text, written by the header writers above.  A
+fifth magic:
+    0   4  magic  b"RCXD"
+    4   1  version (1)
+    5   1  op: how an element and the base's element make a residual (include/rcx_base.h: 0 xor, 1 sub, 2 sub + zigzag)
+    6   1  width: bytes per element (1, 2, 4 or 8)
+    7   1  flags: bit 0 = the base's CRC table follows (DELTA_FLAG_BASE_CRC); every other bit 0
+    8   4  block size in bytes
+    12  4  zero
+    16  8  n
+    24  with bit 0: 4 * ceil(n / block)  the CRC-32 of every `block` bytes of the BASE in source order (the last one ragged):
+        the residual decodes correctly whatever the base is, so the inner checksums cannot catch a wrong base; this table can
+    ..  the inner container, to the end of the blob: for width 2, 4 or 8 an RCXT of that width without a predictor, for width 1
+        (no planes) an RCXB without block sort; n and block are the prefix's.  Whatever those carry -- checksums of the split
+        text, stored blocks, any coder -- they carry here, and an RCXT reader that skips the prefix gets the residual.
 """
 import json
 import struct
@@ -117,6 +135,11 @@ TYPED_ITEMS_VERSION = 1
 TYPED_ITEMS_VERSION_STORED = 2  # + the bitmap of the stored sub-items behind the offsets; always with FLAG_STORED
 _TYPED_ITEMS_FIXED = struct.Struct("<4sBBHQQQ")
 ITEM_WIDTHS = (1, 2, 4, 8)
+DELTA_MAGIC = b"RCXD"
+DELTA_VERSION = 1
+DELTA_FLAG_BASE_CRC = 1  # the CRC table of the base follows the fixed part
+BASE_OPS = {"xor": 0, "sub": 1, "subzz": 2}  # include/rcx_base.h: RCX_BASE_*
+_DELTA_FIXED = struct.Struct("<4sBBBBI4sQ")
 
 
 def coded_size(n: int, flags: int) -> int:
@@ -126,6 +149,15 @@ def coded_size(n: int, flags: int) -> int:
 
 class ContainerError(ValueError):
     pass
+
+
+class BaseMismatchError(ContainerError):
+    """A base whose CRC-32 differs from the delta container's table: `index` is the first such block of `block` bytes of the
+    base.  Raised before anything is decoded: against another base the residual would decode to wrong bytes and no error."""
+
+    def __init__(self, index: int):
+        self.index = int(index)
+        super().__init__(f"the base is not the one the container was packed against: base block {self.index} differs")
 
 
 class ChecksumError(ContainerError):
@@ -438,6 +470,69 @@ def parse_typed_items(blob):
     if stored is not None:  # (a version 1 container parses to exactly what it always did: read the key with .get("stored"))
         out["stored"] = stored
     return out
+
+
+# ---- RCXD ----------------------------------------------------------------------------------------------------------------------
+def delta_header_bytes(op: int, width: int, block: int, n: int, base_crcs=None) -> bytes:
+    """The prefix of a delta container; the inner container (typed_header_bytes with the same n, block and width and no
+    predictor, or header_bytes without block sort for width 1, and its payload) follows it.  base_crcs: the CRC-32 of every
+    `block` bytes of the base, or None for a container without that guard."""
+    if type(op) is not int or op not in BASE_OPS.values():
+        raise ContainerError("an op is 0 (xor), 1 (sub) or 2 (subzz)")
+    if width not in ITEM_WIDTHS:
+        raise ContainerError("an element is 1, 2, 4 or 8 bytes wide")
+    if block < 16 or block > (1 << 24) - 256 or n < 0:
+        raise ContainerError("inconsistent header")
+    flags, table = 0, b""
+    if base_crcs is not None:
+        base_crcs = np.ascontiguousarray(base_crcs, dtype="<u4")
+        if len(base_crcs) != (n + block - 1) // block:
+            raise ContainerError("one checksum per block of the base")
+        flags, table = DELTA_FLAG_BASE_CRC, base_crcs.tobytes()
+    return _DELTA_FIXED.pack(DELTA_MAGIC, DELTA_VERSION, op, width, flags, block, bytes(4), n) + table
+
+
+def parse_delta(blob):
+    """-> dict(op, width, flags, block, n, base_crcs uint32[ceil(n / block)] or None, kind "typed" or "blocks", inner: what
+    parse_typed or parse makes of the inner container, inner_at: where it begins in the blob)"""
+    buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+    if len(buf) < _DELTA_FIXED.size:
+        raise ContainerError("shorter than a header")
+    magic, version, op, width, flags, block, reserved, n = _DELTA_FIXED.unpack(bytes(buf[: _DELTA_FIXED.size]))
+    if magic != DELTA_MAGIC:
+        raise ContainerError("not an RCXD container")
+    if version != DELTA_VERSION or op not in BASE_OPS.values() or flags & ~DELTA_FLAG_BASE_CRC:
+        raise ContainerError("unsupported container version, op or flags")
+    if width not in ITEM_WIDTHS or reserved != bytes(4):
+        raise ContainerError("an element is 1, 2, 4 or 8 bytes wide, and the reserved bytes are zero")
+    if block < 16 or block > (1 << 24) - 256:
+        raise ContainerError("inconsistent header")
+    at, base_crcs = _DELTA_FIXED.size, None
+    if flags & DELTA_FLAG_BASE_CRC:
+        size = 4 * ((n + block - 1) // block)
+        if len(buf) < at + size:  # (Python integers: a count of 2^63 is merely too large)
+            raise ContainerError("truncated checksum table of the base")
+        base_crcs = np.frombuffer(bytes(buf[at: at + size]), dtype="<u4").astype(np.uint32)
+        at += size
+    rest = buf[at:]
+    if width == 1:
+        if bytes(rest[:4]) != MAGIC:
+            raise ContainerError("the residual of 1-byte elements lies in an RCXB container")
+        inner = parse(rest)
+        if inner["flags"] & FLAG_BLKSORT:
+            raise ContainerError("the residual is never block-sorted")
+    else:
+        if bytes(rest[:4]) != TYPED_MAGIC:
+            raise ContainerError("the residual of 2-, 4- or 8-byte elements lies in an RCXT container")
+        inner = parse_typed(rest)
+        if inner["pred"] != 0:
+            raise ContainerError("the residual takes no predictor")
+        if inner["width"] != width:
+            raise ContainerError("the inner container disagrees with the prefix")
+    if inner["n"] != n or inner["block"] != block:
+        raise ContainerError("the inner container disagrees with the prefix")
+    return {"op": op, "width": width, "flags": flags, "block": block, "n": n, "base_crcs": base_crcs, "kind": "blocks" if width == 1 else "typed",
+            "inner": inner, "inner_at": at}
 
 
 # ---- the tensor directory ------------------------------------------------------------------------------------------------------
