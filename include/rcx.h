@@ -85,7 +85,18 @@ int rcx_version(void);
 const char* rcx_status_string(int status);
 
 /* A context owns the device scratch (per-block slots, size table, divisor table)
- * of one GPU.  It is single-threaded; use one context per thread / stream. */
+ * of one GPU.  It is single-threaded; use one context per thread / stream.  That allows:
+ *   - any number of contexts may be used at the same time from different threads: their
+ *     scratch, their status words and their host-buffer pipelines are their own;
+ *   - one context, and every rcx_estream / rcx_dstream made from it, may be used by one
+ *     thread at a time.
+ * Every entry point that touches the device first reads and drops the CALLING THREAD's
+ * pending HIP error.  Since HIP 7 an error returned by any earlier runtime call of the
+ * thread stays until somebody reads it, and the launches are checked by reading it: an
+ * error another call of that thread left behind is neither reported by the library nor
+ * left for the caller to find afterwards.  Other threads' errors are not touched.
+ * The RCX_* environment variables are read during calls, not only when a context is
+ * created, so they must not be changed while a call of any thread runs. */
 int rcx_ctx_create(int device, rcx_ctx** out);
 void rcx_ctx_destroy(rcx_ctx* ctx);
 /* Pre-allocate scratch for buffers up to n bytes at this block size (otherwise the

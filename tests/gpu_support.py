@@ -1,14 +1,16 @@
 """What the GPU tests share: the launch-shape knobs and contexts made under them, the `ctx` fixture, guarded buffers and
 the device calls wrapped in them, the comparisons with the oracle that most tests make, the launch shapes restated with
-the block counts at which they change, and damaged streams.
+the block counts at which they change, damaged streams, and run_together: jobs on a host thread each, round by round.
 
 A test file imports what it needs from here (a fixture by name: `from gpu_support import ctx  # noqa: F401`, or
 `bwt_ctx as ctx` for the block sort in both rank forms; one context per importing module), never from another test file.  tests/test_support_cpu.py holds Guarded, knobs, chunk_blocks,
-shape_edges and the two comparisons to their contracts on CPU tensors.  Nothing here reads /root/reference.
+shape_edges, the two comparisons and run_together to their contracts on CPU tensors and sleeping jobs.  Nothing here reads /root/reference.
 """
 import contextlib
 import os
+import sys
 import threading
+import time
 
 import numpy as np
 import pytest
@@ -104,6 +106,23 @@ class Guarded:
 
 
 # ---- the device calls, every buffer guarded ----------------------------------------------------------------------------
+_calls = threading.local()  # .spans: where run_together collects the calling thread's library_call() spans of a round
+
+
+@contextlib.contextmanager
+def library_call():
+    """Around calls of the library, up to the return of the synchronisation behind them: time.perf_counter() at both
+    ends, kept for run_together, whose overlap measure counts only these spans -- not the allocation and filling of the
+    guarded buffers in front of a call or the comparisons behind it.  Outside run_together it does nothing."""
+    start = time.perf_counter()
+    try:
+        yield
+    finally:
+        spans = getattr(_calls, "spans", None)
+        if spans is not None:
+            spans.append((start, time.perf_counter()))
+
+
 def run_filter(ctx, call, what, x, src_offset=0, dst_offset=0):
     """One device call of a typed filter, call(src, dst), with both buffers guarded -> the n bytes written; the source is
     unchanged, and nothing but the n bytes of the destination is written.  `what` names the call in a failure."""
@@ -119,7 +138,7 @@ def run_filter(ctx, call, what, x, src_offset=0, dst_offset=0):
     return dst.view.cpu().numpy()
 
 
-def _encode(ctx, data, block, src_offset, coder, dst_offset, invert):
+def _encode(ctx, data, block, src_offset, coder, dst_offset, invert, before=None):
     """-> (dst, offs, offsets np.uint64): the guarded destination and table after the call and its checks."""
     data = np.ascontiguousarray(data, dtype=np.uint8)
     n = len(data)
@@ -127,8 +146,11 @@ def _encode(ctx, data, block, src_offset, coder, dst_offset, invert):
     src = Guarded(n, src_offset, data, salt=1, invert=invert)
     dst = Guarded(rcx.encode_bound(n, block, coder), dst_offset, salt=2, invert=invert)
     offs = Guarded(8 * (nblocks + 1), 0, salt=3, invert=invert)
-    ctx.encode_blocks_device(src.view, block, dst.view, offs.view.view(torch.int64), coder=coder)
-    ctx.sync_status()
+    with library_call():
+        if before is not None:
+            before()
+        ctx.encode_blocks_device(src.view, block, dst.view, offs.view.view(torch.int64), coder=coder)
+        ctx.sync_status()
     offsets = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
     src.check(0, "encode src")
     offs.check(8 * (nblocks + 1), "encode offsets")
@@ -136,24 +158,28 @@ def _encode(ctx, data, block, src_offset, coder, dst_offset, invert):
     return dst, offs, offsets
 
 
-def gpu_encode(ctx, data, block, src_offset=0, coder=0, dst_offset=0, invert=False):
+def gpu_encode(ctx, data, block, src_offset=0, coder=0, dst_offset=0, invert=False, before=None):
     """-> (payload np.uint8, offsets np.uint64, the device views) through the device-pointer entry points.  Every buffer is
-    guarded (Guarded): the source is not written, and nothing is written past offsets[nblocks] of dst or around the table."""
-    dst, offs, offsets = _encode(ctx, data, block, src_offset, coder, dst_offset, invert)
+    guarded (Guarded): the source is not written, and nothing is written past offsets[nblocks] of dst or around the table.
+    `before`, if given, is called once the buffers exist, right in front of the library call."""
+    dst, offs, offsets = _encode(ctx, data, block, src_offset, coder, dst_offset, invert, before)
     return dst.view[: int(offsets[-1])].cpu().numpy(), offsets, (dst.view, offs.view.view(torch.int64))
 
 
-def gpu_decode(ctx, payload, offsets, n, block, dst_offset=0, comp_offset=0, coder=0, invert=False):
+def gpu_decode(ctx, payload, offsets, n, block, dst_offset=0, comp_offset=0, coder=0, invert=False, before=None):
     """Decode through the device-pointer entry point -> (out np.uint8, status, first bad block).  The compressed bytes
     and the table are guarded inputs (not written; what lies behind comp_size is the guard pattern, not zeros), and
-    nothing is written outside the n output bytes."""
+    nothing is written outside the n output bytes.  `before` as in gpu_encode."""
     payload = np.ascontiguousarray(payload, dtype=np.uint8)
     comp = Guarded(len(payload), comp_offset, payload, salt=4, invert=invert)
     table = np.ascontiguousarray(np.asarray(offsets).astype(np.int64))
     offs = Guarded(8 * len(table), 0, table.view(np.uint8), salt=5, invert=invert)
     out = Guarded(n, dst_offset, salt=6, invert=invert)
-    ctx.decode_blocks_device(comp.view, len(payload), offs.view.view(torch.int64), n, block, out.view, coder=coder)
-    st, bad = ctx.sync_status(raise_on_error=False)
+    with library_call():
+        if before is not None:
+            before()
+        ctx.decode_blocks_device(comp.view, len(payload), offs.view.view(torch.int64), n, block, out.view, coder=coder)
+        st, bad = ctx.sync_status(raise_on_error=False)
     comp.check(0, "decode comp")
     offs.check(0, "decode offsets")
     out.check(n, "decode dst")
@@ -184,8 +210,9 @@ def encode_items(ctx, items, coder, src_offset=0, dst_offset=0, invert=False):
     src = Guarded(len(data), src_offset, data, salt=1, invert=invert)
     dst = Guarded(rcx.encode_items_bound(soffs, coder), dst_offset, salt=2, invert=invert)
     offs = Guarded(8 * len(soffs), 0, salt=3, invert=invert)
-    ctx.encode_items_device(src.view, soffs, dst.view, offs.view.view(torch.int64), coder=coder)
-    ctx.sync_status()
+    with library_call():
+        ctx.encode_items_device(src.view, soffs, dst.view, offs.view.view(torch.int64), coder=coder)
+        ctx.sync_status()
     table = offs.view.view(torch.int64).cpu().numpy().astype(np.uint64)
     src.check(0, "encode src")
     offs.check(8 * len(soffs), "encode table")
@@ -203,8 +230,9 @@ def decode_items(ctx, payload, comp_offsets, lengths, coder, pick=None, comp_off
     doffs = rcx.item_offsets(lengths)
     n = int(doffs[-1])
     out = Guarded(n, dst_offset, salt=6, invert=invert)
-    ctx.decode_items_device(comp.view, len(payload), offs.view.view(torch.int64), doffs, out.view, pick=pick, coder=coder)
-    st, bad = ctx.sync_status(raise_on_error=False)
+    with library_call():
+        ctx.decode_items_device(comp.view, len(payload), offs.view.view(torch.int64), doffs, out.view, pick=pick, coder=coder)
+        st, bad = ctx.sync_status(raise_on_error=False)
     comp.check(0, "decode comp")
     offs.check(0, "decode table")
     out.check(n, "decode dst")
@@ -508,3 +536,132 @@ def check_call(ctx, d, block, dst_offset, label):
     for b, w in want.items():
         got = back[b * block: b * block + len(w)]
         assert np.array_equal(got, w), (label, b, d.kind.get(b, "undamaged"))
+
+
+# ---- several contexts at once, one host thread each (tests/test_gpu_threads.py) ------------------------------------------
+def jobs_intersect(rows):
+    """rows: per job its list of (start, end) spans, None or empty for a job that did not run -> does a span of one job
+    intersect a span of another?"""
+    spans = sorted((start, end, i) for i, row in enumerate(rows) for start, end in row or ())
+    ends = {}  # job -> the latest end of its spans so far
+    for start, end, i in spans:
+        if any(start < e for j, e in ends.items() if j != i):
+            return True
+        ends[i] = max(end, ends.get(i, end))
+    return False
+
+
+def stuck_message(where, limit):
+    """What ends the session when threads did not come back: `where` = [(job index, what it was doing)]."""
+    jobs = ", ".join(f"job {i} ({what})" for i, what in where)
+    return (f"run_together: {jobs} not back after {limit} s: a call of the library hangs; nothing more is started on the "
+            "GPU in this session")
+
+
+def _end_the_session(message):
+    pytest.exit(message, returncode=3)
+
+
+def run_together(jobs, rounds, limit, stuck=_end_the_session, calls_only=False):
+    """Every job on a host thread of its own, `rounds` rounds, the calls of a round started together -> per round, whether
+    the intervals of at least two jobs intersected.  A job's intervals are the library_call() spans it went through in
+    the round: the time it spent in the library, from the call to the return of its synchronisation.  A job that went
+    through none counts with its whole round; with `calls_only` that is an error of the job instead, so that what the GPU
+    tests assert about overlap is never the set-up and the comparisons that all jobs do behind the same barrier.
+
+    A job is a callable job(round) -> None that owns its context, its torch.cuda.Stream() and its guarded buffers.  If it
+    has a setup() it makes them there, and a close() frees them: both run on the job's thread too, in front of the first
+    round and behind the last.  All threads wait at a threading.Barrier in front of every round, and each takes
+    time.perf_counter() around its round.  The first exception of any thread is raised again here, on the calling thread,
+    as an AssertionError that names the job's index and the round; the other threads stop at their next barrier.  However
+    a thread leaves, a job whose set-up succeeded is closed on that thread, so that no context is left to be destroyed
+    (a device synchronisation) whenever and wherever the garbage collector finds it.  Threads
+    that are not back `limit` seconds after the start are reported through `stuck` (stuck_message); by default that ends
+    the whole pytest session with pytest.exit, because a call that hangs in the library must not be followed by more GPU
+    work from later tests (the threads are daemons: they do not keep the process).
+
+    The binding loads the library with ctypes.CDLL, which drops the GIL for the duration of every call (a PyDLL would
+    keep it), and so do torch's copies and synchronisations: Python threads do overlap inside the library.  That the
+    rounds really ran side by side is what the returned list is for; a test asserts it."""
+    count = len(jobs)
+    barrier = threading.Barrier(count)
+    lock = threading.Lock()
+    spans = [[None] * count for _ in range(rounds)]
+    doing = ["set-up"] * count
+    errors = []  # (job index, what it was doing, the exception), the first one first
+
+    def work(i):
+        job, ready = jobs[i], False
+        try:
+            try:
+                if hasattr(job, "setup"):
+                    job.setup()
+                ready = True
+                for r in range(rounds):
+                    doing[i] = f"waiting for round {r}"
+                    barrier.wait()
+                    doing[i] = f"round {r}"
+                    calls = _calls.spans = []
+                    start = time.perf_counter()
+                    job(r)
+                    end = time.perf_counter()
+                    _calls.spans = None
+                    assert calls or not calls_only, "the job went through no library_call() in this round"
+                    spans[r][i] = calls or [(start, end)]
+            except threading.BrokenBarrierError:
+                pass  # another job failed or hangs: this one stops here
+            finally:
+                _calls.spans = None
+                if ready and hasattr(job, "close"):
+                    if sys.exc_info()[0] is None:  # (a round's exception keeps the round's name)
+                        doing[i] = "closing"
+                    job.close()
+            doing[i] = None
+        except BaseException as e:  # noqa: B036 (whatever it is, it is reported on the calling thread)
+            with lock:
+                errors.append((i, doing[i], e))
+            doing[i] = None
+            barrier.abort()
+
+    threads = [threading.Thread(target=work, args=(i,), daemon=True, name=f"run_together-{i}") for i in range(count)]
+    deadline = time.monotonic() + limit
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(max(deadline - time.monotonic(), 0))
+    alive = [(i, doing[i]) for i, t in enumerate(threads) if t.is_alive()]
+    if alive:
+        barrier.abort()
+        # (a job that waits at the barrier is kept there by one that is not back from its round: name the latter)
+        stuck(stuck_message([w for w in alive if not str(w[1]).startswith("waiting")] or alive, limit))
+    if errors:
+        i, what, e = errors[0]
+        raise AssertionError(f"job {i}, {what}: {type(e).__name__}: {e}") from e
+    return [jobs_intersect(row) for row in spans]
+
+
+def run_alone(jobs, rounds):
+    """The same jobs and rounds one after the other on the calling thread: what a scenario does first, so that a recipe
+    that is wrong without any concurrency fails here."""
+    for i, job in enumerate(jobs):
+        try:
+            if hasattr(job, "setup"):
+                job.setup()
+            for r in range(rounds):
+                job(r)
+            if hasattr(job, "close"):
+                job.close()
+        except Exception as e:
+            raise AssertionError(f"alone: job {i}: {type(e).__name__}: {e}") from e
+
+
+def hip_runtime():
+    """The HIP runtime the library links, as a ctypes handle with hipFree and hipGetLastError declared."""
+    import ctypes as C
+    rcx.lib()
+    path = next((line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line), None)
+    assert path, "the HIP runtime should be loaded by now"
+    hip = C.CDLL(path)
+    hip.hipFree.argtypes, hip.hipFree.restype = [C.c_void_p], C.c_int
+    hip.hipGetLastError.argtypes, hip.hipGetLastError.restype = [], C.c_int
+    return hip

@@ -23,6 +23,16 @@ def exe(tmp_path_factory):
     return out
 
 
+@pytest.fixture(scope="module")
+def exe_threads(tmp_path_factory):
+    """The same line with -pthread, for the mode that starts std::threads."""
+    out = str(tmp_path_factory.mktemp("facade_threads") / "facade_test")
+    lib = os.path.join(ROOT, "cpprcoder_amd")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "facade_test.cpp"),
+                    "-o", out, "-L", lib, "-lrcx", f"-Wl,-rpath,{lib}"], check=True)
+    return out
+
+
 def run(exe, tmp_path, mode, data, *args):
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
     src.write_bytes(bytes(data))
@@ -163,6 +173,48 @@ def test_facade_blksort(exe, tmp_path, oracle):
     bad[32769] |= 0x80  # row index past the block
     (ok, _, _), _ = run(exe, tmp_path, "bdec", bad, 0)
     assert ok == 0
+
+
+def test_facades_from_four_threads(exe_threads, tmp_path, oracle):
+    """Mode `threads` of tests/cpp/facade_test.cpp: four std::threads, each on its own slice, every facade twice over (the
+    second pass on the thread's warm thread_local contexts), thread 0 once more while the others' contexts are destroyed
+    with their threads.  Every thread's payload, offsets, streams and return values are the oracle's for its slice."""
+    T, size, block = 4, 4 * 65536 + 1001, 65536
+    data = workloads.canterbury_tiled(T * size)
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+    src.write_bytes(data.tobytes())
+    p = subprocess.run([exe_threads, "threads", str(src), str(dst), str(T), str(block)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, (p.returncode, p.stdout, p.stderr)
+    lines = sorted([int(x) for x in line.split()] for line in p.stdout.strip().split("\n"))
+    assert [line[0] for line in lines] == list(range(T)) and [line[1] for line in lines] == [3, 2, 2, 2]
+    out, at = dst.read_bytes(), 0
+
+    def take(count):
+        nonlocal at
+        at += count
+        return out[at - count: at]
+
+    for t, line in enumerate(lines):
+        s = data[t * size: (t + 1) * size]
+        failed, total, noff, est, erq, esize, dst_, drq, rsize, rret, rsize8, rret8, bsize, bok = line[2:]
+        assert failed == 0, t
+        slots, sizes = oracle.encode_blocks(s, block, threads=4)
+        payload, offsets = oracle.compact(slots, sizes)
+        assert total == len(payload) and noff == len(offsets), t
+        assert take(total) == payload.tobytes(), (t, "block payload")
+        assert take(8 * noff) == offsets.astype("<u8").tobytes(), (t, "offsets")
+        a = s[:20000].tobytes()
+        (rst, rrq), rout, rs = oracle.adaptive_encode(a, sink_capacity=len(a) + len(a) // 32 + 1024)
+        assert (est, erq, esize) == (rst, rrq, rs) == (0, 0, len(rout)) and (dst_, drq) == (0, 0), t
+        assert take(esize) == rout, (t, "adaptive stream")
+        v = s[:30000].tobytes()
+        for simd, got_size, got_ret in ((False, rsize, rret), (True, rsize8, rret8)):
+            ref = oracle.rans_encode(v, simd)
+            assert got_size == len(ref) and got_ret == (len(v) if simd else len(ref) - 1032), (t, simd)
+            assert take(got_size) == ref, (t, "rANS stream", simd)
+        ref = oracle.bwt_encode(s[: 3 * 32768])
+        assert bok == 1 and bsize == len(ref) and take(bsize) == ref.tobytes(), (t, "block sort")
+    assert at == len(out)
 
 
 def _goldens():

@@ -9,7 +9,7 @@ import pytest
 import bwt_cases
 import oracle_lib
 from cpprcoder_amd import workloads
-from gpu_support import chunk_blocks
+from gpu_support import chunk_blocks, hip_runtime
 
 pytestmark = pytest.mark.gpu
 
@@ -175,11 +175,7 @@ def test_an_error_left_behind_by_another_hip_call_is_not_reported(data):
     behind (here: a hipFree of nonsense) must not turn up as RCX_E_HIP of the next encode."""
     import ctypes as C
     from cpprcoder_amd import rcx
-    rcx.lib()
-    path = next((line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line), None)
-    assert path, "the HIP runtime should be loaded by now"
-    hip = C.CDLL(path)
-    hip.hipFree.argtypes, hip.hipFree.restype = [C.c_void_p], C.c_int
+    hip = hip_runtime()
     assert hip.hipFree(C.c_void_p(0x1234)) != 0  # an error that nobody reads
     ctx = rcx.Context(0)
     try:
@@ -195,7 +191,6 @@ def test_an_error_left_behind_by_another_hip_call_is_not_reported(data):
         assert hip.hipFree(C.c_void_p(0x1234)) != 0
         ctx.encode_blocks_device(src, BLOCK, out, offs)
         ctx.sync_status()
-        hip.hipGetLastError.restype = C.c_int
         hip.hipGetLastError()  # (nothing of ours should be there; whatever is, is not left for torch to find)
         total = int(offs[-1])
         assert total == size and np.array_equal(out[:total].cpu().numpy(), dst[:size])

@@ -1,13 +1,16 @@
 """The shared test support (tests/gpu_support.py) held to its contract, on CPU tensors: every "writes nothing outside
 its buffer" claim of the GPU tests rests on Guarded.check failing when it should, their launch shapes on knobs leaving the
-environment as it found it, and their parity claims on the two comparisons."""
+environment as it found it, their parity claims on the two comparisons, and the threaded scenarios of
+tests/test_gpu_threads.py on run_together (held here with sleeping jobs)."""
 import os
+import threading
+import time
 
 import numpy as np
 import pytest
 
 from gpu_support import (GUARD, SHAPE_EDGE_IDS, Guarded, assert_same_blocks, assert_same_items, chunk_blocks, decode_quads, encode_lanes,
-                         knobs, shape_edges)
+                         jobs_intersect, knobs, library_call, run_alone, run_together, shape_edges, stuck_message)
 
 SIZES, OFFSETS = (0, 1, 33), (0, 15)
 
@@ -224,3 +227,135 @@ def test_the_launch_loop_input_is_long_and_codes_small(oracle):
     assert [-(-rc.LOOP_N // cap) for cap in rc.LOOP_CAPS + (rc.LOOP_ONE_CALL,)] == [3, 3, 3, 2, 1]
     kinds = [(k, len(b)) for k, b, _ in rc.interleaved_inputs()]
     assert [k for k, _ in kinds] == ["dec", "enc", "dec", "enc"] and all(20_000 <= n <= 70_000 for _, n in kinds)
+
+
+# ---- run_together: what tests/test_gpu_threads.py takes for granted about its threads ---------------------------------------
+class Sleeper:
+    """A job that sleeps `naps[round]` seconds and notes when each round began and ended, and on which thread."""
+
+    def __init__(self, naps, fail_in=None):
+        self.naps, self.fail_in = naps, fail_in
+        self.began, self.ended, self.threads = [], [], set()
+
+    def setup(self):
+        self.threads.add(threading.get_ident())
+
+    def __call__(self, r):
+        self.threads.add(threading.get_ident())
+        self.began.append(time.perf_counter())
+        if r == self.fail_in:
+            raise Boom("went wrong")
+        time.sleep(self.naps[r])
+        self.ended.append(time.perf_counter())
+
+    def close(self):
+        self.threads.add(threading.get_ident())
+        self.closed = True
+
+
+def test_run_together_names_the_job_and_the_round_of_the_first_exception():
+    jobs = [Sleeper([0.01] * 3), Sleeper([0.01] * 3), Sleeper([0.01] * 3, fail_in=1)]
+    with pytest.raises(AssertionError, match=r"job 2, round 1: Boom: went wrong") as e:
+        run_together(jobs, 3, limit=30)
+    assert isinstance(e.value.__cause__, Boom)
+    # nobody went on into round 2; every job, the failing one too, was closed, and on its own thread
+    assert len(jobs[2].began) == 2 and all(len(j.began) <= 2 for j in jobs)
+    assert all(j.closed and len(j.threads) == 1 for j in jobs)
+    # an exception in the set-up step is named as such
+    class BadSetup(Sleeper):
+        def setup(self):
+            raise Boom("no context")
+    pair = [Sleeper([0.01]), BadSetup([0.01])]
+    with pytest.raises(AssertionError, match=r"job 1, set-up: Boom: no context"):
+        run_together(pair, 1, limit=30)
+    assert pair[0].closed and not hasattr(pair[1], "closed")  # (a job whose set-up failed has nothing to close)
+    with pytest.raises(AssertionError, match=r"alone: job 1: Boom: no context"):
+        run_alone([Sleeper([0.0]), BadSetup([0.0])], 1)
+
+
+def test_run_together_reports_a_job_that_is_not_back_in_time():
+    class Stuck(Exception):
+        pass
+
+    def stuck(message):
+        raise Stuck(message)
+
+    # (wide margins, for a loaded machine: round 0 has 2 s, and the nap of round 1 outlasts the limit by far; the
+    # sleeping thread is a daemon and is left behind)
+    jobs = [Sleeper([0.01, 0.01]), Sleeper([0.01, 20.0])]
+    with pytest.raises(Stuck, match=r"job 1 \(round 1\) not back after 2 s") as e:
+        run_together(jobs, 2, limit=2, stuck=stuck)
+    assert "job 0" not in str(e.value)  # (it was back from round 1, or waiting for nobody)
+    assert stuck_message([(0, "round 3"), (2, "set-up")], 120).startswith("run_together: job 0 (round 3), job 2 (set-up) not back after 120 s")
+    # by default the report ends the session: pytest.exit, not a failure that lets later tests start more GPU work
+    import gpu_support
+    import inspect
+    assert inspect.signature(run_together).parameters["stuck"].default is gpu_support._end_the_session
+    with pytest.raises(pytest.exit.Exception, match="hangs"):
+        gpu_support._end_the_session(stuck_message([(1, "round 0")], 120))
+
+
+def test_intersecting_and_disjoint_intervals_are_told_apart():
+    def intervals_intersect(spans):  # one span per job, None for a job that did not run
+        return jobs_intersect([s and [s] for s in spans])
+
+    assert intervals_intersect([(0.0, 1.0), (0.5, 2.0)])
+    assert intervals_intersect([(0.0, 5.0), (1.0, 2.0), (7.0, 8.0)])        # one inside another
+    assert intervals_intersect([(3.0, 4.0), (0.0, 1.0), (3.5, 3.6)])        # in any order
+    assert not intervals_intersect([(0.0, 1.0), (1.0, 2.0), (2.5, 3.0)])    # touching is not intersecting
+    assert not intervals_intersect([(0.0, 1.0)]) and not intervals_intersect([]) and not intervals_intersect([(0.0, 1.0), None])
+    assert intervals_intersect([(0.0, 10.0), (1.0, 2.0), (5.0, 6.0)])       # the long one reaches over both
+    # and through run_together: two sleepers side by side overlap in every round; a job alone never does
+    assert run_together([Sleeper([0.05] * 2), Sleeper([0.05] * 2)], 2, limit=30) == [True, True]
+    assert run_together([Sleeper([0.01] * 2)], 2, limit=30) == [False, False]
+
+
+class Caller(Sleeper):
+    """A job that spends `naps[round]` seconds outside any call and then, if `calls`, 0.05 s in library_call()."""
+
+    def __init__(self, naps, calls=True):
+        super().__init__(naps)
+        self.calls = calls
+
+    def __call__(self, r):
+        super().__call__(r)
+        if self.calls:
+            with library_call():
+                time.sleep(0.05)
+
+
+def test_only_the_time_inside_the_library_counts_as_overlap():
+    assert jobs_intersect([[(0.0, 1.0)], [(0.5, 2.0)]])
+    assert not jobs_intersect([[(0.0, 1.0), (0.5, 2.0)], None, []])                # two spans of ONE job
+    assert not jobs_intersect([[(0.0, 1.0), (4.0, 5.0)], [(1.0, 2.0), (3.0, 4.0)]])  # touching is not intersecting
+    assert jobs_intersect([[(0.0, 1.0), (4.0, 5.0)], [(2.0, 3.0), (4.5, 4.6)]])
+    assert jobs_intersect([[(0.0, 10.0)], [(1.0, 2.0)], [(5.0, 6.0)]]) and jobs_intersect([[(1.0, 2.0), (3.0, 9.0)], [(0.0, 0.5), (8.0, 8.5)]])
+    assert not jobs_intersect([]) and not jobs_intersect([[(0.0, 1.0)]])
+    # the rounds intersect as wholes, but the calls inside do not: one job's call is over long before the other's begins
+    assert run_together([Caller([0.0] * 2), Caller([1.0] * 2)], 2, limit=60, calls_only=True) == [False, False]
+    assert run_together([Caller([0.0] * 2), Caller([0.0] * 2)], 2, limit=60, calls_only=True) == [True, True]
+    # a job without any such span counts with its whole round, unless the caller asks for calls only
+    assert run_together([Caller([0.0]), Caller([0.3], calls=False)], 1, limit=60) == [True]
+    with pytest.raises(AssertionError, match=r"job 1, round 0: AssertionError: the job went through no library_call"):
+        run_together([Caller([0.0]), Caller([0.0], calls=False)], 1, limit=60, calls_only=True)
+    with library_call():  # outside run_together it does nothing
+        pass
+
+
+def test_the_barrier_starts_a_round_together():
+    naps = ([0.01, 0.6, 0.01], [0.6, 0.01, 0.01], [0.01, 0.01, 0.01])
+    jobs = [Sleeper(n) for n in naps]
+    main = threading.get_ident()
+    assert run_together(jobs, 3, limit=30) == [True, True, True]
+    for r in (1, 2):  # nobody begins a round before the slowest is back from the one before
+        slowest = max(j.ended[r - 1] for j in jobs)
+        assert all(j.began[r] >= slowest for j in jobs), r
+        # (and all begin it together: far closer than the 0.6 s by which they would differ without the barrier)
+        assert max(j.began[r] for j in jobs) - min(j.began[r] for j in jobs) < 0.3, r
+    # set-up, rounds and close of a job ran on one thread, its own
+    assert all(len(j.threads) == 1 and j.closed for j in jobs)
+    assert len({next(iter(j.threads)) for j in jobs} | {main}) == 4
+    # run_alone: the same jobs on the calling thread
+    alone = [Sleeper([0.0] * 2) for _ in range(2)]
+    run_alone(alone, 2)
+    assert all(j.threads == {main} and len(j.began) == 2 and j.closed for j in alone)
