@@ -2,7 +2,11 @@
 test_reference_build_agrees), as generators of (key, result) for one checker.  tests/golden/make_golden_agreement.py runs
 them over the real reference build and stores a digest of every result (tests/golden/reference_agreement.json); the tests
 run them over the oracle and compare with those digests, and, where oracle/_ref is present, with the reference build's own
-results as well.  A result is a tuple of ints, bools and bytes, so two checkers' results compare with ==."""
+results as well.  A result is a tuple of ints, bools and bytes, so two checkers' results compare with ==.
+
+The second half does the same for the crafted families of tests/crafted_cases.py (CRAFTED: one generator per family;
+tests/golden/reference_crafted.json; tests/test_oracle_crafted.py), whose stored digests tests/test_gpu_reference_digests.py
+also holds the kernels to."""
 from __future__ import annotations
 
 import hashlib
@@ -14,12 +18,19 @@ import numpy as np
 from cpprcoder_amd import workloads
 
 STORED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_agreement.json")
+STORED_CRAFTED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_crafted.json")
 
 
 def stored(part: str) -> dict:
     """The reference build's digests of one check ("adaptive", "rans", "bwt" or "damaged"), key -> digest."""
     with open(STORED) as f:
         return json.load(f)[part]
+
+
+def stored_crafted(family: str) -> dict:
+    """The reference build's digests of one family of tests/crafted_cases.py, key -> digest."""
+    with open(STORED_CRAFTED) as f:
+        return json.load(f)[family]
 
 
 def digest(result) -> str:
@@ -146,3 +157,102 @@ def damaged(chk):
             for _ in range(1 + i % 4):
                 s[int(rs.randint(1032 + 4, max(len(comp), 1032 + 5)))] ^= int(rs.randint(1, 256))
             yield f"{i}/simd={simd}/decode flips", chk.rans_decode(s, len(v), simd)
+
+
+# ---- the crafted families (tests/crafted_cases.py) ---------------------------------------------------------------------------
+# One generator per family.  A result under crafted_cases.case_key() can be rebuilt from a device call alone: an encode is
+# (stream,), a decode (every symbol came out, the bytes if so), a stream_decode (status, request size, bytes); the kernels
+# are held to those digests directly by tests/test_gpu_reference_digests.py.  What the reference says beyond that (a capped
+# sink, pieces) stands under keys of its own, which end in a word after the kind.
+def crafted_result(chk, c):
+    """One case of the range or rANS coders by one checker."""
+    if c.kind == "encode":
+        slots, sizes = chk.encode_blocks(c.data, c.n, coder=c.coder)
+        return (bytes(slots[0, : int(sizes[0])]),)
+    if c.kind == "decode":
+        slots = np.zeros((1, len(c.data) + 64), np.uint8)
+        slots[0, : len(c.data)] = c.data
+        out, ok = chk.decode_blocks(slots, np.array([len(c.data)], np.uint32), c.n, c.n, coder=c.coder)
+        return (bool(ok), out.tobytes() if ok else b"")
+    assert c.kind == "stream_decode" and c.coder == 0
+    (st, rq), out, _ = chk.adaptive_decode(c.data, c.n)
+    return (st, rq, out)
+
+
+def crafted_plain(family):
+    """The generator of a family that has nothing beyond its cases' own results."""
+    def run(chk):
+        import crafted_cases
+        for c in crafted_cases.cases(family):
+            yield crafted_cases.case_key(c), crafted_result(chk, c)
+    return run
+
+
+def crafted_carry(chk):
+    """Both range coders' streams; for the adaptive coder also into a capped sink and in pieces, as trace_cases.py does."""
+    import crafted_cases
+    for c in crafted_cases.cases("carry"):
+        key = crafted_cases.case_key(c)
+        got = crafted_result(chk, c)
+        yield key, got
+        if c.coder == 0:
+            for cap in (len(got[0]) // 2, 128):
+                yield f"{key} cap={cap}", chk.adaptive_encode(c.data, sink_capacity=cap)
+            yield f"{key} chunked piece=64", chk.adaptive_encode_chunked(c.data, 64)
+
+
+TRUNCATION_PIECES = (4096, 777)
+
+
+def crafted_truncations(chk):
+    """As one block, as one stream into a bounded sink, and that stream in pieces into a roomy one."""
+    import crafted_cases
+    for c in crafted_cases.cases("truncations"):
+        key = crafted_cases.case_key(c)
+        yield key, crafted_result(chk, c)
+        if c.kind == "stream_decode":
+            for piece in TRUNCATION_PIECES:
+                yield f"{key} chunked piece={piece}", chk.adaptive_decode_chunked(c.data, piece, 1 << 20)
+
+
+def crafted_halving(chk):
+    """One-shot; the input encoded in constant pieces of HALVING_PIECE bytes (for the long inputs the 16th piece ends with
+    the symbol that halves the table, cpprcoder.h:1138, and the 17th starts from the halved one); and the stream decoded
+    in pieces that fall nowhere in particular: what the resumable coders have returned when the last piece is in.  (The
+    uneven call sizes of resumable_cases.around_halving are not here: see tests/crafted_cases.py.)"""
+    import crafted_cases
+    import resumable_cases
+    for c in crafted_cases.cases("halving"):
+        key = crafted_cases.case_key(c)
+        yield key, crafted_result(chk, c)
+        if c.kind == "encode":
+            yield f"{key} chunked piece={resumable_cases.HALVING_PIECE}", chk.adaptive_encode_chunked(c.data, resumable_cases.HALVING_PIECE)
+        else:
+            yield f"{key} chunked piece={resumable_cases.CHUNKED_PIECE}", chk.adaptive_decode_chunked(c.data, resumable_cases.CHUNKED_PIECE, c.n)
+
+
+def crafted_bwt(chk, threads=8):
+    """The block sort: every block's encoding, and the inverse of every encoded block, each in one call over `threads`
+    threads (a block full of ties takes either checker a second or more)."""
+    import crafted_cases
+    cases = crafted_cases.cases("bwt")
+    enc = [c for c in cases if c.kind == "encode"]
+    dec = [c for c in cases if c.kind == "decode"]
+    if enc:  # (the oracle's own encodings are the ones crafted_cases made for its decode cases: not made twice)
+        made = crafted_cases.oracle_encoded() if chk.kind == "port" else crafted_cases.bwt_encoded(chk, [c.data for c in enc], threads)
+        for c, e in zip(enc, made):
+            yield crafted_cases.case_key(c), (e.tobytes(),)
+    if dec:
+        back = chk.bwt_decode(np.concatenate([c.data for c in dec]), threads=threads)
+        for i, c in enumerate(dec):
+            yield crafted_cases.case_key(c), (back[i * c.n: (i + 1) * c.n].tobytes(),)
+
+
+CRAFTED = {"carry": crafted_carry, "static": crafted_plain("static"), "rans": crafted_plain("rans"), "bwt": crafted_bwt,
+           "adaptive": crafted_plain("adaptive"), "damaged": crafted_plain("damaged"), "truncations": crafted_truncations,
+           "halving": crafted_halving}
+
+
+def device_key(key: str) -> bool:
+    """Is this stored key one that a device call alone can rebuild (it ends in the kind, with no word behind it)?"""
+    return key.endswith(("/encode", "/decode", "/stream_decode"))

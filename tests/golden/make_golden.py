@@ -8,6 +8,14 @@ bytes / sizes / hashes); no reference source goes into them.  The GPU box and CI
 only ever read the JSON.
 
     python tests/golden/make_golden.py
+
+The other fixtures have generators of their own beside this one (make_golden_rans.py, _bwt.py, _long.py, _traces.py,
+_containers.py).  make_golden_agreement.py writes two: reference_agreement.json (the reference build's digests on ordinary
+inputs) and reference_crafted.json (its digests on every crafted family of tests/crafted_cases.py: carry runs, the static
+coder's squeeze and large totals, the rANS steal loop, the block sort's switch points, bursts, targets past the table,
+truncations, the halving).  To regenerate both, byte for byte:
+
+    make -C oracle all ref && python tests/golden/make_golden_agreement.py
 """
 import json
 import os

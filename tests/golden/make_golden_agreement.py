@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Generate tests/golden/reference_agreement.json from the REAL reference build: a digest of every result of the checks in
 tests/agreement_cases.py (range coders, rANS, block sort, damaged streams), so that the tests that compare the oracle with the reference
-build run where oracle/_ref/ is not present too.  Runs only where oracle/_ref/ was built (`make -C oracle ref`, see
+build run where oracle/_ref/ is not present too; and tests/golden/reference_crafted.json, the same for the crafted families
+of tests/crafted_cases.py (agreement_cases.CRAFTED), which tests/test_oracle_crafted.py holds the oracle to and
+tests/test_gpu_reference_digests.py the kernels.  Runs only where oracle/_ref/ was built (`make -C oracle ref`, see
 make_golden.py).  Outputs are data: digests of the reference's outputs.
 
     python tests/golden/make_golden_agreement.py
@@ -35,6 +37,14 @@ def main() -> None:
         print(part, len(out[part]), "results", flush=True)
     with open(os.path.join(HERE, "reference_agreement.json"), "w") as f:
         json.dump(out, f, indent=1)
+        f.write("\n")
+    # the crafted families (tests/crafted_cases.py), in a fixture of their own so that the one above stays as it is
+    crafted = {"generator": out["generator"], "source": out["source"]}
+    for family, run in agreement_cases.CRAFTED.items():
+        crafted[family] = {k: agreement_cases.digest(r) for k, r in run(ref)}
+        print("crafted", family, len(crafted[family]), "results", flush=True)
+    with open(os.path.join(HERE, "reference_crafted.json"), "w") as f:
+        json.dump(crafted, f, indent=1)
         f.write("\n")
 
 

@@ -14,19 +14,11 @@ import numpy as np
 import pytest
 
 from cpprcoder_amd import rcx, workloads
-from gpu_support import CODERS, COUNT0, DATA, HEAD, LOW, Damaged, build, check_call, chunk_blocks, context
+from gpu_support import CODERS, COUNT0, DATA, HEAD, LOW, SHAPES, Damaged, build, check_call, chunk_blocks, context
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-SHAPES = {  # launch shapes (read when a context is created, rcx_api.hip rcx_ctx_create) and the output's offset
-    "default": ({}, 0),
-    "quads16": ({"RCX_DEC_QUADS": "16"}, 0),
-    "narrow": ({"RCX_WIDE_WG": "0"}, 0),
-    "one_lane": ({"RCX_LANES_PER_BLOCK": "1"}, 0),
-    "dst+3": ({}, 3),
-}
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,7 @@ stream alone (the rule in include/rcx.h, "Damaged streams").
 import numpy as np
 import pytest
 
+from adaptive_cases import ONE_VALUE_BYTES, ONE_VALUE_N, one_value_block
 from cpprcoder_amd import rcx, workloads
 from gpu_support import Damaged, assert_same_blocks, check_call, context, gpu_decode, gpu_encode
 
@@ -63,11 +64,11 @@ def test_round_trips_on_the_borrow_boundaries(contexts, oracle, nblocks, first_k
         assert np.array_equal(back, data), (name, int(np.nonzero(back != data)[0][0]) // BLOCK)
 
 
-@pytest.mark.parametrize("byte", [0, 255])
+@pytest.mark.parametrize("byte", ONE_VALUE_BYTES)
 def test_one_large_block_of_one_byte(contexts, oracle, byte):
     """2^18 symbols of one value: its count -- and every bound above it -- grows to 2^18 while t falls to range / 2^18."""
-    n = 1 << 18
-    data = np.full(n, byte, np.uint8)
+    n = ONE_VALUE_N
+    data = one_value_block(byte, n)
     slots, sizes = oracle.encode_blocks(data, n)
     for name, ctx in contexts.items():
         payload, offsets, _ = gpu_encode(ctx, data, n)

@@ -13,6 +13,9 @@ each damaged stream alone (include/rcx.h, "Damaged streams").  Every buffer is g
 import numpy as np
 import pytest
 
+from adaptive_cases import ALL_THREE, PASS_BURST_GROUPS, pass_burst_blocks
+from adaptive_cases import PASS_BLOCK as BLOCK
+from adaptive_cases import PASS_LENGTHS as LENGTHS  # no pass ... five passes, three groups, seven symbols one by one
 from adaptive_walk import past_the_table
 from cpprcoder_amd import rcx, workloads
 from gpu_support import Damaged, assert_same_blocks, check_call, check_items, context, gpu_decode, gpu_encode, oracle_streams
@@ -21,9 +24,6 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-BLOCK = 4096
-ALL_THREE = 64 * 5 + 16 * 3 + 7  # five passes, three groups, seven symbols one by one
-LENGTHS = (48, 64, 80, 112, 128, 129, 191, 192, ALL_THREE)
 SOURCES = ("uniform", "zipf")
 
 
@@ -138,23 +138,13 @@ def test_target_past_the_table_in_a_pass(contexts, oracle, which, group):
 
 
 # ---- 5. the cold refill in the second, third and fourth group of a pass -----------------------------------------------------
-@pytest.mark.parametrize("group", [1, 2, 3])
+@pytest.mark.parametrize("group", PASS_BURST_GROUPS)
 def test_cold_refill_inside_a_pass(contexts, oracle, group):
     """test_bursts_of_very_improbable_symbols at 4 KiB blocks: after some 3000 equal bytes every other value costs about 12
     bits, 6 dwords per 16 symbols where the top-up supplies 4, so the input ring runs low and the synchronous refill runs,
     again and again every few groups for the 32 groups the burst lasts.  The burst begins two groups in front of
     group `group` of a pass, in a pass of its own in every other block, and all 16 blocks of a wave share the top-up's
     branch: the refill is taken in front of every group of a pass."""
-    rs = np.random.RandomState(8600 + group)
-    blocks = []
-    for b in range(16):
-        fill = (65, 0, 255, 128)[b % 4]
-        x = np.full(BLOCK, fill, np.uint8)
-        others = np.array([v for v in range(256) if v != fill], np.uint8)
-        at = 3072 + 64 * (b % 8) + 16 * group - 32
-        burst = np.concatenate([rs.permutation(others), rs.permutation(others)])[: BLOCK - at]
-        x[at: at + len(burst)] = burst
-        blocks.append(x)
-    data = np.concatenate(blocks)
+    data = np.concatenate(pass_burst_blocks(group))  # (the builder: tests/adaptive_cases.py)
     for name in ("quads16", "default"):
         blocks_round_trip(contexts[name], oracle, data, BLOCK, (name, group))

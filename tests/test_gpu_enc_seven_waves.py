@@ -11,6 +11,7 @@ to 256 CUs, with a last workgroup that is part filled.
 import numpy as np
 import pytest
 
+from adaptive_cases import LEVEL3_CASES, level3_block
 from cpprcoder_amd import rcx
 from gpu_support import check_blocks, check_items, ctx, oracle_streams  # noqa: F401
 
@@ -50,16 +51,12 @@ def test_level3_boundaries(ctx, oracle, name):
         check_blocks(ctx, oracle, symbols(name, block * nblocks, i), block)
 
 
-@pytest.mark.parametrize("case", ["all 0", "all 255", "0 then 255"])
+@pytest.mark.parametrize("case", LEVEL3_CASES)
 def test_largest_level3_sums(ctx, oracle, case):
     """One bench-sized block.  Of symbol 0 alone: all three sums grow with every symbol, to 65536 + 192.  Of symbol 255
     alone: the sum below the last quarter is handed over with every symbol.  Of symbol 0 with a 255 now and then, and as
     the last symbol: the largest sums there can be, up to 192 + 65535, go through the plane."""
-    data = np.full(65536, 255 if case == "all 255" else 0, np.uint8)
-    if case == "0 then 255":
-        data[np.random.RandomState(3).randint(0, 65536, 300)] = 255
-        data[-1] = 255
-    check_blocks(ctx, oracle, data, 65536)
+    check_blocks(ctx, oracle, level3_block(case), 65536)  # (the builder: tests/adaptive_cases.py)
 
 
 @pytest.mark.parametrize("name", SETS)

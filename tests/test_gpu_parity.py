@@ -7,6 +7,7 @@ test/main.cpp:357-361).  Nothing here reads /root/reference.
 import numpy as np
 import pytest
 
+import adaptive_cases
 import golden_cases
 from cpprcoder_amd import workloads
 from gpu_support import assert_same_blocks, check_blocks, check_golden_blocks, context, ctx, gpu_decode, gpu_encode  # noqa: F401
@@ -243,17 +244,7 @@ def test_bursts_of_very_improbable_symbols(ctx, oracle):
     """After ~2^20 equal bytes every other byte value costs 20 bits: 2.5 output bytes per symbol for a while.
     That is more than the decoder's fast input top-up supplies (8 dwords per 16 symbols: its synchronous refill
     runs) and more than one 16-byte piece per chunk for the encoder's drain."""
-    block = 1 << 20
-    def one(fill, seed):
-        rs = np.random.RandomState(seed)
-        d = np.full(block, fill, np.uint8)
-        others = np.array([v for v in range(256) if v != fill], np.uint8)
-        tail = np.concatenate([rs.permutation(others) for _ in range(24)])
-        d[block - len(tail):] = tail
-        d[5000:5000 + 255] = rs.permutation(others)  # and once early, at 13 bits per symbol
-        return d
-    data = np.concatenate([one(65, 1), one(0, 2), one(255, 3), workloads.zipf(block, 4)])
-    check_blocks(ctx, oracle, data, block, threads=4)
+    check_blocks(ctx, oracle, adaptive_cases.long_bursts(), adaptive_cases.LONG_BURST_BLOCK, threads=4)
     assert ctx.last_redo(4) == 0
 
 

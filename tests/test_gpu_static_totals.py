@@ -14,6 +14,8 @@
 import numpy as np
 import pytest
 
+import agreement_cases
+import crafted_cases
 import static_cases as sc
 from cpprcoder_amd import rcx
 from gpu_support import assert_same_blocks, check_blocks, context, ctx, gpu_decode, gpu_encode, oracle_decode_one  # noqa: F401
@@ -149,11 +151,14 @@ def test_natural_block_of_total_16647552(encoders, one_lane, oracle):
 
 def test_natural_stream_of_two_to_the_24(ctx, oracle):
     """2^24 bytes, one early squeeze, total 2^24 - 32768: past RCX_MAX_BLOCK, so rcx_enc_static_k and rcx_dec_static_k code
-    it as a single stream."""
+    it as a single stream.  The kernel's stream is the oracle's, and it has the digest the real reference build's stream has
+    (tests/golden/reference_crafted.json: the one static encode that tests/test_gpu_reference_digests.py leaves to this test,
+    which codes the 2^24 symbols on one lane anyway)."""
     v = sc.natural_stream()
     ok, want, size = oracle.static_encode(v)
     st, _, comp = ctx.stream_encode(v, coder=STATIC)
     assert ok and st == rcx.OK and len(comp) == size and comp == want
+    assert agreement_cases.digest((comp,)) == agreement_cases.stored_crafted("static")[crafted_cases.NATURAL_STREAM + "/static/encode"]
     st, _, back = ctx.stream_decode(comp, len(v), coder=STATIC)
     assert st == rcx.OK and back == v.tobytes()
 
