@@ -63,6 +63,15 @@ are given against it, on the device, before anything is decoded -- BaseMismatchE
 unpack_delta_range decodes the blocks of the superblocks that cover the range, verifies only those blocks of the base and joins
 the span against the same span of the base: the transform is elementwise.  Not here: tensors by name against a base
 (pack_tensors), an op chosen by measurement, chains of deltas, bases of another length.
+
+Residuals against a base per item (pack_delta_items(items, bases, ...), pack_tensors_delta(named, base, ...);
+include/rcx_base_items.h, cpprcoder_amd/base_items.py): tensors by name against a base ARE here.  Every item has a width and
+either a predictor, or an op against a base of its own length, or neither; one split call transforms them all, and the
+sub-items are coded as pack_typed_items codes them.  The container is RCXK: a prefix with the items' ops and, with base_check
+(the default), the CRC-32 of every item's base, then a complete RCXJ (layout.py).  unpack_delta_items and unpack_tensors_delta
+need only the picked items' bases and verify them on the device before anything is decoded: BaseItemMismatchError names the
+item and, for tensors, the tensor.  pack_tensors_delta gives a tensor the op if the base holds its name with the same dtype
+and shape, and packs every other tensor as pack_tensors does.
 """
 import contextlib
 
@@ -787,6 +796,314 @@ def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool
     if int(doffs[-1]):
         with _scope(ctx) as ctx:
             flat, _ = _unpack_typed_items_device(ctx, c, pick, verify)
+            flat = flat if device == "cuda" else flat.cpu()
+    for n in wanted:
+        e = by_name[n]
+        dtype = getattr(torch, e["dtype"])
+        a, b = int(doffs[at]), int(doffs[at + e["count"]])
+        at += e["count"]
+        count = int(np.prod(e["shape"], dtype=np.int64)) if len(e["shape"]) else 1
+        if b - a != count * torch.empty(0, dtype=dtype).element_size():
+            raise ContainerError(f"{n!r}: the items do not hold the tensor the directory describes")
+        if b == a:
+            out[n] = torch.empty(e["shape"], dtype=dtype, device=device)
+        else:  # (a copy: a tensor begins where the one before ends, at any alignment)
+            out[n] = flat[a:b].clone().view(dtype).reshape(e["shape"])
+    return out
+
+
+# ---- RCXK: an op against a base of its own, or a predictor, or neither, per buffer ----------------------------------------------
+from .layout import (BASE_OP_NONE, DELTA_ITEMS_FLAG_BASE_CRC, DELTA_ITEMS_MAGIC, DELTA_ITEMS_VERSION, BaseItemMismatchError,  # noqa: E402,F401
+                     delta_items_header_bytes, parse_delta_items)
+
+
+def _item_ops(ops, has_base):
+    """ops: a name for every item that has a base, or one entry per item (a name, or None: no op) -> uint8[nitems]"""
+    nitems = len(has_base)
+    each = isinstance(ops, (list, tuple))
+    entries = list(ops) if each else [ops if has_base[i] else None for i in range(nitems)]
+    if len(entries) != nitems:
+        raise ContainerError("one op per item")
+    out = np.full(nitems, BASE_OP_NONE, np.uint8)
+    for i, e in enumerate(entries):
+        if e is None:
+            continue
+        if not isinstance(e, str) or e not in BASE_OPS:
+            raise ContainerError(f"an op is 'xor', 'sub', 'subzz' or None, not {e!r}")
+        if not has_base[i]:
+            raise ContainerError(f"item {i} has an op and no base")
+        out[i] = BASE_OPS[e]
+    return out
+
+
+def _base_offsets(lengths, ops):
+    """The bases of the items with an op back to back -> (their table of nitems + 1 offsets, where an item without one has length 0)"""
+    from . import rcx
+    return rcx.item_offsets(np.where(ops != BASE_OP_NONE, lengths, 0).astype(np.uint64))
+
+
+def _pack_delta_items_device(ctx, parts, refs, lengths, widths, preds, auto, ops, coder: int, checksum: bool, directory: bytes, gain, base_check: bool) -> bytes:
+    """parts, refs: the items that have bytes, and the bases of those of them that have an op -> the container: one gather each
+    (an upload unless all lie on the device), one split call, encode over the sub-items (and mix, and CRC-32 of the split text) as
+    _pack_typed_items_device does them, one CRC call over the bases for the guard, one download."""
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    _typed_items_tables(lengths, widths, preds)
+    nsub, nitems = int(widths.astype(np.int64).sum()), len(widths)
+    if int(lengths.sum()) == 0:  # nothing to code: no GPU
+        inner = typed_items_header_bytes(coder, lengths, widths, preds, np.zeros(nsub + 1, np.uint64), np.zeros(nsub, np.uint32) if checksum else None, directory)
+        return delta_items_header_bytes(ops, np.zeros(nitems, np.uint32) if base_check else None) + inner
+    import torch
+    from . import base_items, rcx, typed_items
+    d_src, d_ref = _gather_device(parts), _gather_device(refs)
+    with _scope(ctx) as ctx:
+        offs, boffs = rcx.item_offsets(lengths), _base_offsets(lengths, ops)
+        sub_offs = typed_items.sub_offsets(offs, widths)
+        d_split = torch.empty(d_src.numel(), dtype=torch.uint8, device="cuda")
+        if auto.any():  # (only items without an op are measured; the others go through as planes there and are not looked at)
+            preds = _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d_split)
+        base_items.split_device(ctx, d_src, d_ref if d_ref.numel() else None, offs, boffs[:-1], widths, preds, ops, d_split)
+        if base_check:
+            d_guard = torch.zeros(nitems, dtype=torch.int32, device="cuda")
+            if d_ref.numel():
+                ctx.crc32_items_device(d_ref, boffs, d_guard)
+        payload, offsets, crcs, raw = _encode_items(ctx, d_split, sub_offs, coder, checksum, gain)  # (one sync: the bases' CRCs are there too)
+        guard = None
+        if base_check:
+            guard = np.where((ops != BASE_OP_NONE) & (lengths > 0), _crcs_of(d_guard), 0).astype(np.uint32)
+        return delta_items_header_bytes(ops, guard) + typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory, raw) + payload.tobytes()
+
+
+def _delta_item_widths(sources, widths):
+    if widths is None:
+        each = [w for _, w in sources]
+        if any(w is None for w in each):
+            raise ContainerError("plain bytes have no element size: give the width")
+    else:
+        each = list(widths) if isinstance(widths, (list, tuple, np.ndarray)) else [widths] * len(sources)
+        if len(each) != len(sources):
+            raise ContainerError("one width per item")
+    if any(type(w) not in (int, np.uint8, np.int64, np.int32) or int(w) not in ITEM_WIDTHS for w in each):
+        raise ContainerError(f"an element is 1, 2, 4 or 8 bytes wide, not {each!r}")
+    return np.array(each, dtype=np.uint8)
+
+
+def _delta_item_predictors(predict, widths, ops):
+    """predict applies to the items without an op; an explicit predictor on an item with one is refused."""
+    based = ops != BASE_OP_NONE
+    if isinstance(predict, (list, tuple)):
+        if len(predict) != len(widths):
+            raise ContainerError("one predictor per item")
+        if any(e is not None for e, b in zip(predict, based) if b):
+            raise ContainerError("an item with a base takes no predictor")
+        return _item_predictors(list(predict), widths)
+    return _item_predictors([None if b or w == 1 else predict for b, w in zip(based, widths)], widths)
+
+
+def pack_delta_items(items, bases, widths=None, ops="subzz", predict=None, coder: int = 0, ctx=None, checksum: bool = False, directory: bytes = b"",
+                     stored=None, base_check: bool = True) -> bytes:
+    """items: a list of buffers as pack_typed_items takes them; bases: one entry per item, None or a buffer of the item's byte
+    length (any other length raises ContainerError) -> an RCXK container.  ops: "xor", "sub" or "subzz" for every item that has
+    a base, or a list with one of these or None per item (None: the item is packed without its base; an op on an item whose base
+    is None raises).  predict: as in pack_typed_items, for the items without an op; an explicit predictor on an item with one
+    raises.  One gather and upload for the items and one for the bases (none for what lies on the GPU), one split call, one encode
+    over the sub-items, one CRC call for the guard, one download.  base_check: the CRC-32 of every item's base goes into the
+    prefix, the only guard against unpacking with another base."""
+    gain = _gain(stored)
+    sources = [_source(x) for x in items]
+    if len(bases) != len(sources):
+        raise ContainerError("one base, or None, per item")
+    w = _delta_item_widths(sources, widths)
+    parts = [x for x, _ in sources]
+    lengths = np.array([_size(x) for x in parts], dtype=np.uint64)
+    theirs = [None if b is None else _source(b)[0] for b in bases]
+    for i, b in enumerate(theirs):
+        if b is not None and _size(b) != int(lengths[i]):
+            raise ContainerError(f"the base of item {i} has {_size(b)} bytes, the item {int(lengths[i])}: a base is as long as its item")
+    o = _item_ops(ops, [b is not None for b in theirs])
+    preds, auto = _delta_item_predictors(predict, w, o)
+    refs = [b for b, op in zip(theirs, o) if op != BASE_OP_NONE and _size(b)]
+    return _pack_delta_items_device(ctx, [x for x in parts if _size(x)], refs, lengths, w, preds, auto, o, coder, checksum, directory, gain, base_check)
+
+
+def _unpack_delta_items_device(ctx, c, refs, pick, verify: bool, name=lambda k: None):
+    """The picked items of a parsed RCXK container -> (the device buffer, the table of where each pick lies in it).  refs: the
+    bases of the picks that have an op and bytes, in the picks' order.  The bases are verified first, on the device, back to back
+    (a pick without a base has length 0 there); then the picks' sub-items are decoded and checked as _unpack_typed_items_device
+    does it, and joined against the bases."""
+    import torch
+    from . import base_items, rcx, typed_items
+    inner = c["inner"]
+    pick = np.asarray(pick, dtype=np.int64)
+    widths, preds, ops = inner["widths"][pick], inner["preds"][pick], c["ops"][pick]
+    doffs = rcx.item_offsets(inner["lengths"][pick])
+    n = int(doffs[-1])
+    d_out = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+    if n == 0:
+        return d_out, doffs
+    boffs = _base_offsets(inner["lengths"][pick], ops)
+    d_ref = _gather_device(refs)
+    if int(boffs[-1]) != d_ref.numel():
+        raise ContainerError("the bases are not as long as their items")
+    if verify and c["base_crcs"] is not None and d_ref.numel():
+        ctx.verify_items_device(d_ref, boffs, _cuda(c["base_crcs"][pick]))
+        st, bad = ctx.sync_status(raise_on_error=False)
+        if st == rcx.E_CORRUPT:
+            raise BaseItemMismatchError(int(pick[int(bad)]), name(int(pick[int(bad)])))
+        if st != rcx.OK:
+            raise rcx.RcxError(st, f"the base of item {bad}")
+    subs = np.concatenate([np.arange(inner["sub_first"][k], inner["sub_first"][k + 1], dtype=np.int64) for k in pick])
+    owner = np.repeat(pick, widths.astype(np.int64))
+    soffs = typed_items.sub_offsets(doffs, widths)
+    d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
+    if inner.get("stored") is None:
+        ctx.decode_items_device(_cuda(inner["payload"]), len(inner["payload"]), _cuda(inner["offsets"]), soffs, d_split, pick=subs.astype(np.uint64),
+                                coder=inner["coder"])
+    else:  # version 2 of the inner container: the stored sub-items are copied
+        from . import stored as calls
+        calls.decode_device(ctx, _cuda(inner["payload"]), len(inner["payload"]), _cuda(inner["offsets"]), inner["stored"], soffs, d_split,
+                            pick=subs.astype(np.uint64), coder=inner["coder"])
+    ctx.sync_status()
+    if verify and inner["crcs"] is not None:
+        ctx.verify_items_device(d_split, soffs, _cuda(inner["crcs"][subs]))
+        _sync_checked(ctx, "item", lambda k: int(owner[k]))
+    base_items.join_device(ctx, d_split, d_ref if d_ref.numel() else None, doffs, boffs[:-1], widths, preds, ops, d_out)
+    return d_out, doffs
+
+
+def _picked_bases(c, picked, base_of, what=lambda k: f"item {k}"):
+    """The bases of the picks that have an op and bytes, each as long as its item; a missing one raises."""
+    refs = []
+    for k in picked:
+        k = int(k)
+        if c["ops"][k] == BASE_OP_NONE or int(c["inner"]["lengths"][k]) == 0:
+            continue
+        b = base_of(k)
+        if b is None:
+            raise ContainerError(f"{what(k)} was packed against a base, and there is none")
+        b = _source(b)[0]
+        if _size(b) != int(c["inner"]["lengths"][k]):
+            raise ContainerError(f"the base of {what(k)} has {_size(b)} bytes, the item {int(c['inner']['lengths'][k])}")
+        refs.append(b)
+    return refs
+
+
+def unpack_delta_items(blob, bases, pick=None, ctx=None, verify: bool = True) -> list:
+    """-> the list of the picked items' bytes (all of them, in order, if pick is None).  bases: one entry per item of the
+    container; only those of the picked items that have an op are looked at, the others may be None.  A missing base raises
+    ContainerError.  The picked items' bases are verified against the prefix's table first (BaseItemMismatchError names the
+    item), then only their sub-items are decoded and verified; verify=False skips the guard and the inner checksums."""
+    c = parse_delta_items(blob)
+    if len(bases) != c["nitems"]:
+        raise ContainerError("one base, or None, per item of the container")
+    if pick is not None and any(not 0 <= int(k) < c["nitems"] for k in pick):
+        raise ContainerError("no such item")
+    picked = np.arange(c["nitems"], dtype=np.int64) if pick is None else np.array([int(k) for k in pick], dtype=np.int64)
+    if len(picked) == 0:
+        return []
+    if int(c["inner"]["lengths"][picked].sum()) == 0:
+        return [b""] * len(picked)
+    refs = _picked_bases(c, picked, lambda k: bases[k])
+    with _scope(ctx) as ctx:
+        d_out, doffs = _unpack_delta_items_device(ctx, c, refs, picked, verify)
+        out = d_out.cpu().numpy()
+        return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
+
+
+def _as_tensor(name, t):
+    import torch
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t if t.flags.c_contiguous else np.ascontiguousarray(t))
+    if type(t).__module__.split(".")[0] != "torch":
+        raise ContainerError(f"{name!r} is neither a numpy array nor a torch tensor")
+    return t
+
+
+def pack_tensors_delta(named, base, block: int = 65536, op="subzz", predict=None, coder: int = 0, ctx=None, checksum: bool = False, stored=None,
+                       base_check: bool = True) -> bytes:
+    """named, base: dicts of names -> numpy arrays or contiguous torch tensors (CPU or GPU) -> an RCXK container whose directory
+    names the tensors of `named`: a state dict against the one before it.  A tensor gets the op if `base` holds its name with
+    the same dtype and shape; every other tensor is packed as pack_tensors packs it, and `predict` (as in pack_tensors) applies
+    to those only.  op: a name for all, or a dict of names -> a name or None (None, or a name it lacks: packed without its base);
+    a name in the dict whose base is missing or of another dtype or shape raises ContainerError.  Every tensor is cut into
+    items of element_size * block bytes, and its base with it."""
+    gain = _gain(stored)
+    if not 16 <= block <= MAX_ITEM:
+        raise ContainerError("a block is 16 bytes to RCX_MAX_BLOCK")
+    if isinstance(op, dict):
+        for name, e in op.items():
+            if e is not None and name in named and (name not in base or _as_tensor(name, base[name]).dtype != _as_tensor(name, named[name]).dtype
+                                                    or tuple(_as_tensor(name, base[name]).shape) != tuple(_as_tensor(name, named[name]).shape)):
+                raise ContainerError(f"{name!r} has an op, and the base has no tensor of that name, dtype and shape")
+    parts, refs, lengths, widths, entry_preds, entry_ops, entries = [], [], [], [], [], [], []
+    for name, t in named.items():
+        t = _as_tensor(name, t)
+        src, width = _source(t)
+        if width not in ITEM_WIDTHS:
+            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
+        nbytes = _size(src)
+        count = -(-nbytes // (width * block))
+        entries.append({"name": name, "dtype": str(t.dtype).replace("torch.", ""), "shape": tuple(t.shape), "first": len(lengths), "count": count})
+        theirs = _as_tensor(name, base[name]) if name in base else None
+        each_op = op.get(name) if isinstance(op, dict) else op
+        if theirs is None or theirs.dtype != t.dtype or tuple(theirs.shape) != tuple(t.shape):
+            each_op = None
+        each = None if each_op is not None else predict.get(name) if isinstance(predict, dict) else predict
+        if nbytes:
+            parts.append(src)
+            if each_op is not None:
+                refs.append(_source(theirs)[0])
+            lengths += [width * block] * (count - 1) + [nbytes - (count - 1) * width * block]
+            widths += [width] * count
+            entry_preds += [None if width == 1 else each] * count
+            entry_ops += [each_op] * count
+    w = np.array(widths, dtype=np.uint8)
+    o = _item_ops(entry_ops, [e is not None for e in entry_ops])
+    preds, auto = _item_predictors(entry_preds, w)
+    return _pack_delta_items_device(ctx, parts, refs, np.array(lengths, dtype=np.uint64), w, preds, auto, o, coder, checksum, tensor_directory_bytes(entries),
+                                    gain, base_check)
+
+
+def unpack_tensors_delta(blob, base, names=None, device: str = "cpu", ctx=None, verify: bool = True) -> dict:
+    """-> a dict of torch tensors of the recorded dtype and shape, on `device` ("cuda": no download).  names: only those
+    tensors; only their items are decoded (and verified), and only their bases are needed and verified: a tensor that was
+    packed against a base and is missing from `base`, or has another size there, raises ContainerError, one whose bytes differ
+    BaseItemMismatchError with the item and the tensor's name."""
+    import torch
+    from . import rcx
+    c = parse_delta_items(blob)
+    inner = c["inner"]
+    entries = parse_tensor_directory(inner["directory"], c["nitems"])
+    by_name = {e["name"]: e for e in entries}
+    wanted = [e["name"] for e in entries] if names is None else list(names)
+    if any(n not in by_name for n in wanted):
+        raise ContainerError("no such tensor")
+    for n in wanted:
+        if not isinstance(getattr(torch, by_name[n]["dtype"], None), torch.dtype):
+            raise ContainerError(f"{by_name[n]['dtype']!r} is no torch dtype")
+    pick = np.concatenate([np.arange(by_name[n]["first"], by_name[n]["first"] + by_name[n]["count"], dtype=np.int64) for n in wanted] + [np.zeros(0, np.int64)])
+    owner = {int(k): e["name"] for e in entries for k in range(e["first"], e["first"] + e["count"])}
+    # the bases of the wanted tensors, cut as the tensors were: item k of a tensor is the same bytes of its base
+    cut = {}
+    for n in wanted:
+        e = by_name[n]
+        items = range(e["first"], e["first"] + e["count"])
+        if not any(c["ops"][k] != BASE_OP_NONE and int(inner["lengths"][k]) for k in items):
+            continue
+        if n not in base:
+            raise ContainerError(f"tensor {n!r} was packed against a base, and the base has none of that name")
+        ref = _source(_as_tensor(n, base[n]))[0]
+        if _size(ref) != int(inner["lengths"][e["first"]: e["first"] + e["count"]].sum()):
+            raise ContainerError(f"tensor {n!r}: the base has {_size(ref)} bytes, not the tensor's")
+        at = 0
+        for k in items:
+            cut[k] = ref[at: at + int(inner["lengths"][k])]
+            at += int(inner["lengths"][k])
+    out, at = {}, 0
+    flat, doffs = None, rcx.item_offsets(inner["lengths"][pick])
+    if int(doffs[-1]):
+        refs = _picked_bases(c, pick, cut.get, lambda k: f"item {k} of tensor {owner.get(k)!r}")
+        with _scope(ctx) as ctx:
+            flat, _ = _unpack_delta_items_device(ctx, c, refs, pick, verify, owner.get)
             flat = flat if device == "cuda" else flat.cpu()
     for n in wanted:
         e = by_name[n]

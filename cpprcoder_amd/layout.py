@@ -105,6 +105,22 @@ fifth magic:
     ..  the inner container, to the end of the blob: for width 2, 4 or 8 an RCXT of that width without a predictor, for width 1
         (no planes) an RCXB without block sort; n and block are the prefix's.  Whatever those carry -- checksums of the split
         text, stored blocks, any coder -- they carry here, and an RCXT reader that skips the prefix gets the residual.
+
+The delta item container holds many buffers of differing sizes, each with an element width and EITHER a predictor OR a base op
+against a base buffer of its own length that the reader holds as well, or neither (include/rcx_base_items.h;
+cpprcoder_amd/base_items.py): a state dict against the one before it, tensor by tensor.  As with RCXD, a prefix that names
+the ops and guards the bases, and behind it a complete typed item container of the split text.  A sixth magic:
+    0   4  magic  b"RCXK"
+    4   1  version (1)
+    5   1  flags: bit 0 = the base CRC table follows (DELTA_ITEMS_FLAG_BASE_CRC); every other bit 0
+    6   2  zero
+    8   8  nitems
+    16  nitems  the items' ops (include/rcx_base.h: 0 xor, 1 sub, 2 sub + zigzag; 0xFF = the item has no base)
+    ..  with bit 0: 4 * nitems  the CRC-32 of every item's base, all of its bytes (0 for an item without an op or without bytes)
+    ..  a complete RCXJ container, to the end of the blob: the same nitems, and predictor 0 wherever the op is not 0xFF.  The
+        checksums of the split text, stored sub-items, any coder and the directory are its own; an RCXJ reader that skips the
+        prefix gets the residuals of the items with an op and the data of the others.
+The tensor directory of pack_tensors_delta is that of pack_tensors.
 """
 import json
 import struct
@@ -140,6 +156,11 @@ DELTA_VERSION = 1
 DELTA_FLAG_BASE_CRC = 1  # the CRC table of the base follows the fixed part
 BASE_OPS = {"xor": 0, "sub": 1, "subzz": 2}  # include/rcx_base.h: RCX_BASE_*
 _DELTA_FIXED = struct.Struct("<4sBBBBI4sQ")
+DELTA_ITEMS_MAGIC = b"RCXK"
+DELTA_ITEMS_VERSION = 1
+DELTA_ITEMS_FLAG_BASE_CRC = 1  # the CRC table of the items' bases follows the ops
+BASE_OP_NONE = 0xFF  # include/rcx_base_items.h: RCX_BASE_NONE
+_DELTA_ITEMS_FIXED = struct.Struct("<4sBB2sQ")
 
 
 def coded_size(n: int, flags: int) -> int:
@@ -158,6 +179,16 @@ class BaseMismatchError(ContainerError):
     def __init__(self, index: int):
         self.index = int(index)
         super().__init__(f"the base is not the one the container was packed against: base block {self.index} differs")
+
+
+class BaseItemMismatchError(BaseMismatchError):
+    """The same for a delta item container: `index` is the first picked item whose base differs from the one it was packed
+    against, `name` its tensor in a container of tensors (else None)."""
+
+    def __init__(self, index: int, name=None):
+        self.index, self.name = int(index), name
+        ContainerError.__init__(self, f"the base of item {self.index}" + (f", tensor {name!r}," if name is not None else "")
+                                + " is not the one the container was packed against")
 
 
 class ChecksumError(ContainerError):
@@ -533,6 +564,63 @@ def parse_delta(blob):
         raise ContainerError("the inner container disagrees with the prefix")
     return {"op": op, "width": width, "flags": flags, "block": block, "n": n, "base_crcs": base_crcs, "kind": "blocks" if width == 1 else "typed",
             "inner": inner, "inner_at": at}
+
+
+# ---- RCXK ----------------------------------------------------------------------------------------------------------------------
+def _delta_items_ops(ops) -> np.ndarray:
+    ops = np.ascontiguousarray(ops, dtype=np.uint8)
+    if np.any(~np.isin(ops, tuple(BASE_OPS.values()) + (BASE_OP_NONE,))):
+        raise ContainerError("an op is 0 (xor), 1 (sub), 2 (subzz) or 0xFF (no base)")
+    return ops
+
+
+def delta_items_header_bytes(ops, base_crcs=None) -> bytes:
+    """The prefix of a delta item container; the inner container (typed_items_header_bytes with one item per op, predictor 0
+    wherever the op is not BASE_OP_NONE, and its payload) follows it.  base_crcs: the CRC-32 of every item's base (0 for an item
+    without an op or without bytes), or None for a container without that guard."""
+    ops = _delta_items_ops(ops)
+    flags, table = 0, b""
+    if base_crcs is not None:
+        base_crcs = np.ascontiguousarray(base_crcs, dtype="<u4")
+        if len(base_crcs) != len(ops):
+            raise ContainerError("one checksum per item's base")
+        if np.any(base_crcs[ops == BASE_OP_NONE] != 0):
+            raise ContainerError("an item without a base has checksum 0")
+        flags, table = DELTA_ITEMS_FLAG_BASE_CRC, base_crcs.tobytes()
+    return _DELTA_ITEMS_FIXED.pack(DELTA_ITEMS_MAGIC, DELTA_ITEMS_VERSION, flags, bytes(2), len(ops)) + ops.tobytes() + table
+
+
+def parse_delta_items(blob):
+    """-> dict(flags, nitems, ops uint8[nitems], base_crcs uint32[nitems] or None, inner: what parse_typed_items makes of the inner
+    container, inner_at: where it begins in the blob)"""
+    buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+    if len(buf) < _DELTA_ITEMS_FIXED.size:
+        raise ContainerError("shorter than a header")
+    magic, version, flags, reserved, nitems = _DELTA_ITEMS_FIXED.unpack(bytes(buf[: _DELTA_ITEMS_FIXED.size]))
+    if magic != DELTA_ITEMS_MAGIC:
+        raise ContainerError("not an RCXK container")
+    if version != DELTA_ITEMS_VERSION or flags & ~DELTA_ITEMS_FLAG_BASE_CRC:
+        raise ContainerError("unsupported container version or flags")
+    if reserved != bytes(2):
+        raise ContainerError("the reserved bytes are zero")
+    at, base_crcs = _DELTA_ITEMS_FIXED.size, None
+    size = nitems * (5 if flags & DELTA_ITEMS_FLAG_BASE_CRC else 1)
+    if len(buf) < at + size:  # (Python integers: a count of 2^63 is merely too large)
+        raise ContainerError("truncated tables of the ops and the bases")
+    ops = _delta_items_ops(np.array(buf[at: at + nitems]))
+    at += nitems
+    if flags & DELTA_ITEMS_FLAG_BASE_CRC:
+        base_crcs = np.frombuffer(bytes(buf[at: at + 4 * nitems]), dtype="<u4").astype(np.uint32)
+        at += 4 * nitems
+    rest = buf[at:]
+    if bytes(rest[:4]) != TYPED_ITEMS_MAGIC:
+        raise ContainerError("the split text lies in an RCXJ container")
+    inner = parse_typed_items(rest)
+    if inner["nitems"] != nitems:
+        raise ContainerError("the inner container disagrees with the prefix")
+    if np.any((ops != BASE_OP_NONE) & (inner["preds"] != 0)):
+        raise ContainerError("an item with a base takes no predictor")
+    return {"flags": flags, "nitems": nitems, "ops": ops, "base_crcs": base_crcs, "inner": inner, "inner_at": at}
 
 
 # ---- the tensor directory ------------------------------------------------------------------------------------------------------
