@@ -1,7 +1,7 @@
 """python -m cpprcoder_amd c|d|t ...  -- compress / decompress / test files with the MI355X block coder.
 
     python -m cpprcoder_amd c [-b BLOCK] [--blksort | --planes W [--predict delta|zigzag|auto]] [--crc] [--stored [FRACTION]]
-                              [--base FILE [--base-op xor|sub|subzz]] [--static | --coder adaptive|static|rans|rans8] IN OUT
+                              [--base FILE [--base-op xor|sub|subzz|auto]] [--static | --coder adaptive|static|rans|rans8] IN OUT
                                                                IN -> RCXB container (cpprcoder_amd/layout.py);
                                                                --blksort: the reference's block sort (blksort.h) first;
                                                                --planes W: IN is elements of W = 2, 4 or 8 bytes (bf16,
@@ -27,7 +27,8 @@
                                                                the base model, the last snapshot): every element becomes its
                                                                residual against FILE's element first (include/rcx_base.h;
                                                                --base-op: xor, sub, or subzz, the default, the zigzagged
-                                                               difference) -> RCXD container, which carries a CRC-32 per
+                                                               difference, or auto: the cheapest of the three by the
+                                                               measured order-0 cost) -> RCXD container, which carries a CRC-32 per
                                                                block of FILE.  With --planes W the elements are W bytes wide,
                                                                without it 1 byte (fp8, bytes); not with --blksort or
                                                                --predict.  Against an unrelated FILE the container grows
@@ -95,7 +96,7 @@ def parser() -> argparse.ArgumentParser:
     c.add_argument("--crc", action="store_true")
     c.add_argument("--stored", nargs="?", type=_fraction, const=True, default=None, metavar="FRACTION")
     c.add_argument("--base", default=None, metavar="FILE")
-    c.add_argument("--base-op", choices=BASE_OPS, default=None)
+    c.add_argument("--base-op", choices=list(BASE_OPS) + ["auto"], default=None)
     c.add_argument("src")
     c.add_argument("dst")
     d = sub.add_parser("d")
@@ -114,7 +115,7 @@ def parser() -> argparse.ArgumentParser:
     t.add_argument("--crc", action="store_true")
     t.add_argument("--stored", nargs="?", type=_fraction, const=True, default=None, metavar="FRACTION")
     t.add_argument("--base", default=None, metavar="FILE")
-    t.add_argument("--base-op", choices=BASE_OPS, default=None)
+    t.add_argument("--base-op", choices=list(BASE_OPS) + ["auto"], default=None)
     t.add_argument("files", nargs="+")
     return ap
 

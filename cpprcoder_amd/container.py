@@ -62,7 +62,7 @@ default) the prefix carries the CRC-32 of every block of the base, and unpack_de
 are given against it, on the device, before anything is decoded -- BaseMismatchError names the first bad block of the base.
 unpack_delta_range decodes the blocks of the superblocks that cover the range, verifies only those blocks of the base and joins
 the span against the same span of the base: the transform is elementwise.  Not here: tensors by name against a base
-(pack_tensors), an op chosen by measurement, chains of deltas, bases of another length.
+(pack_tensors), chains of deltas, bases of another length.
 
 Residuals against a base per item (pack_delta_items(items, bases, ...), pack_tensors_delta(named, base, ...);
 include/rcx_base_items.h, cpprcoder_amd/base_items.py): tensors by name against a base ARE here.  Every item has a width and
@@ -72,6 +72,19 @@ sub-items are coded as pack_typed_items codes them.  The container is RCXK: a pr
 need only the picked items' bases and verify them on the device before anything is decoded: BaseItemMismatchError names the
 item and, for tensors, the tensor.  pack_tensors_delta gives a tensor the op if the base holds its name with the same dtype
 and shape, and packs every other tensor as pack_tensors does.
+
+"auto" for ops (pack_delta_items(ops=[..., "auto", ...]), pack_tensors_delta(op="auto"), pack_delta(op="auto"); include/rcx_typed_stats.h,
+cpprcoder_amd/typed_stats.py): which of xor, sub and subzz an item wants, or whether it wants its base at all, is measured: one
+call reads items and bases once and gives the order-0 cost of every asked candidate -- none, delta, zigzag, xor, sub, subzz -- of
+every item, exactly what the split and statistics calls give one candidate at a time.  The rule (pick_candidate) is the one
+of predict="auto", extended: a candidate other than none qualifies if 64 * C < 63 * C_none; the cheapest qualifying one wins;
+ties go in the order delta, zigzag, subzz, sub, xor -- what needs no base first, subzz the default among the ops; if nothing
+qualifies the item is packed without its base and without a predictor.  An "auto" item is measured under none and the three ops,
+with predict="auto" under all six; pack_tensors_delta decides per tensor on the sums over its items, so a tensor needs its
+base entirely or not at all; pack_delta decides among the three ops only (pick_op: cheapest, ties subzz, sub, xor, no margin),
+because RCXD cannot say "no base".  The container is byte for byte what the decided names given explicitly write, and nothing in
+it records that they were measured; choose_delta_items and choose_tensors_delta return the decision alone, their
+_from_costs siblings make it from a table without a GPU.
 """
 import contextlib
 
@@ -379,6 +392,24 @@ def pick_predictor(c_none: int, c_delta: int, c_zigzag: int):
     return best[0] if best else None
 
 
+CANDIDATES = (None, "delta", "zigzag", "xor", "sub", "subzz")  # by number: include/rcx_typed_stats.h, RCX_CAND_*
+_CANDIDATE_ORDER = (1, 2, 5, 4, 3)  # ties: what needs no base first, subzz the default among the ops
+
+
+def pick_candidate(costs, asked: int = 0x3F):
+    """The rule of "auto" on the six costs of an item (any one unit; include/rcx_typed_stats.h) -> a name of CANDIDATES.
+    asked: bit c = candidate c was measured.  A candidate other than none qualifies if 64 * C < 63 * C_none; the cheapest
+    qualifying one wins, ties in the order delta, zigzag, subzz, sub, xor; None if nothing qualifies.  On the predictors alone
+    it is pick_predictor."""
+    if not asked & 1:
+        raise ContainerError("the rule compares against the cost without a transform: candidate 0 must be asked for")
+    best = None
+    for c in _CANDIDATE_ORDER:
+        if asked >> c & 1 and 64 * int(costs[c]) < 63 * int(costs[0]) and (best is None or int(costs[c]) < best[1]):
+            best = (CANDIDATES[c], int(costs[c]))
+    return best[0] if best else None
+
+
 def _measured_predictor(ctx, d_src, width: int, block: int, nblocks: int, d_split):
     """-> (the rule's pick, the predictor whose split text d_split holds now).  Three splits into d_split, a statistics pass
     over each (costs only), three sums in one download."""
@@ -489,6 +520,24 @@ def _verify_base_device(ctx, d_ref, block: int, crcs, first: int = 0) -> None:
         raise rcx.RcxError(st, f"base block {bad}")
 
 
+def pick_op(c_xor: int, c_sub: int, c_subzz: int) -> str:
+    """The rule of pack_delta(op="auto") on the three costs: the cheapest, ties in the order subzz, sub, xor."""
+    return min((int(c_subzz), 0, "subzz"), (int(c_sub), 1, "sub"), (int(c_xor), 2, "xor"))[2]
+
+
+def _measured_op(ctx, d_src, d_ref, n: int, width: int, block: int) -> str:
+    """pick_op on the sums over the superblocks: one measuring call with the superblocks as items against the base at the same
+    offsets, three sums on the device, one download."""
+    import torch
+    from . import typed_stats
+    count = -(-n // (width * block))
+    offs = np.minimum(np.arange(count + 1, dtype=np.uint64) * np.uint64(width * block), np.uint64(n))
+    d_cost = torch.zeros(typed_stats.CANDS * count, dtype=torch.int64, device="cuda")
+    typed_stats.items_device(ctx, d_src, d_ref, offs, offs[:-1], np.full(count, width, np.uint8), np.full(count, typed_stats.OP_BITS, np.uint8), d_cost)
+    sums = [int(v) for v in d_cost.view(count, typed_stats.CANDS).sum(dim=0).cpu()]  # (a superblock's cost is below 2^48)
+    return pick_op(sums[typed_stats.XOR], sums[typed_stats.SUB], sums[typed_stats.SUBZZ])
+
+
 def pack_delta(data, base, width=None, block: int = 65536, coder: int = 0, ctx=None, checksum: bool = False, stored=None, op: str = "subzz",
                base_check: bool = True) -> bytes:
     """data, base: each bytes, a numpy array or a contiguous torch tensor (CPU or GPU), of the same byte length -> an RCXD
@@ -496,10 +545,15 @@ def pack_delta(data, base, width=None, block: int = 65536, coder: int = 0, ctx=N
     8).  op: "xor", "sub" or "subzz" (include/rcx_base.h).  One upload each (none for GPU tensors), the residual and its planes in
     one kernel, then encode, mix and CRC-32 of the split text exactly as pack_typed does them; checksum= and stored= are the
     inner container's.  base_check: the CRC-32 of every block of the base goes into the prefix, the only guard against
-    unpacking with another base."""
+    unpacking with another base.  op="auto": the cheapest of the three by the measured order-0 cost of the whole buffer
+    (include/rcx_typed_stats.h on the superblock cut, the sums taken on the device, one download), ties in the order subzz, sub,
+    xor, no margin; the container is byte for byte what that op given by name writes.  RCXD cannot say "no base": against an
+    unrelated base every op loses to none, and only the item container (pack_delta_items, pack_tensors_delta) can decide that."""
     gain = _gain(stored)
-    if not isinstance(op, str) or op not in BASE_OPS:
-        raise ContainerError(f"an op is 'xor', 'sub' or 'subzz', not {op!r}")
+    measured = _is_auto(op)
+    if not measured and (not isinstance(op, str) or op not in BASE_OPS):
+        raise ContainerError(f"an op is 'xor', 'sub', 'subzz' or 'auto', not {op!r}")
+    op = "subzz" if measured else op  # (nothing to measure in an empty buffer)
     src, size = _source(data)
     ref = _source(base)[0]
     width = size if width is None else width
@@ -524,6 +578,8 @@ def pack_delta(data, base, width=None, block: int = 65536, coder: int = 0, ctx=N
     with _scope(ctx) as ctx:
         d_src, d_ref = _on_device(src), _on_device(ref)
         d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if measured:
+            op = _measured_op(ctx, d_src, d_ref, n, width, block)
         calls.split_device(ctx, d_src, d_ref, width, block, BASE_OPS[op], d_split)
         if base_check:
             d_guard = torch.zeros(rcx.block_count(n, block), dtype=torch.int32, device="cuda")
@@ -899,6 +955,139 @@ def _delta_item_predictors(predict, widths, ops):
     return _item_predictors([None if b or w == 1 else predict for b, w in zip(based, widths)], widths)
 
 
+def _is_auto(e) -> bool:
+    return isinstance(e, str) and e == AUTO
+
+
+def _says_auto(ops) -> bool:
+    return _is_auto(ops) or (isinstance(ops, (list, tuple)) and any(_is_auto(e) for e in ops)) or (isinstance(ops, dict) and any(_is_auto(e) for e in ops.values()))
+
+
+def _delta_item_masks(ops, predict, has_base, widths):
+    """ops, predict as pack_delta_items takes them, "auto" among them -> (masks uint8[nitems]: the candidates to measure per item,
+    bit c = candidate c of CANDIDATES, 0 for an item that is named; the op and the predictor entry per item, None where the
+    measurement decides).  An "auto" op needs a base; such an item's predictor entry is None (none and the three ops are
+    measured) or "auto" (all six, at width above 1); a named one raises in the list form and is not applied in the scalar form."""
+    nitems = len(widths)
+    each_op, each_pred = isinstance(ops, (list, tuple)), isinstance(predict, (list, tuple))
+    op_entries = list(ops) if each_op else [ops if has_base[i] else None for i in range(nitems)]
+    pred_entries = list(predict) if each_pred else [predict] * nitems
+    if len(op_entries) != nitems:
+        raise ContainerError("one op per item")
+    if len(pred_entries) != nitems:
+        raise ContainerError("one predictor per item")
+    masks = np.zeros(nitems, np.uint8)
+    for i, (o, p) in enumerate(zip(op_entries, pred_entries)):
+        if not (o is None or _is_auto(o) or (isinstance(o, str) and o in BASE_OPS)):
+            raise ContainerError(f"an op is 'xor', 'sub', 'subzz', 'auto' or None, not {o!r}")
+        if not (p is None or _is_auto(p) or (isinstance(p, str) and p in PREDICTORS)):
+            raise ContainerError(f"a predictor is None, 'delta', 'zigzag' or 'auto', not {p!r}")
+        if o is not None and not has_base[i]:
+            raise ContainerError(f"item {i} has an op and no base")
+        if _is_auto(o):
+            if p is not None and not _is_auto(p) and each_pred:
+                raise ContainerError("an item with a base takes no predictor")
+            masks[i] = 0x3F if _is_auto(p) and widths[i] > 1 else 0x39
+            op_entries[i] = pred_entries[i] = None
+        elif o is None:
+            if _is_auto(p):
+                masks[i] = 0x07 if widths[i] > 1 else 0
+                pred_entries[i] = None
+            elif not each_pred and widths[i] == 1:
+                pred_entries[i] = None
+        elif not each_pred:
+            pred_entries[i] = None  # (a named op: the scalar predictor is for the items without one)
+    return masks, op_entries, pred_entries
+
+
+def _decided(costs, masks, op_entries, pred_entries, groups=None):
+    """pick_candidate per measured item -- per group of items (first, count) on the sums over the group, if groups are given: a
+    tensor takes its base entirely or not at all -> (ops, predict): a name or None per item."""
+    costs = np.asarray(costs, dtype=np.uint64).reshape(len(masks), len(CANDIDATES))
+    ops, preds = list(op_entries), list(pred_entries)
+    for first, count in (groups if groups is not None else [(i, 1) for i in range(len(masks))]):
+        if count == 0 or not masks[first]:
+            continue
+        sums = [sum(int(v) for v in costs[first: first + count, c]) for c in range(len(CANDIDATES))]
+        choice = pick_candidate(sums, int(masks[first]))
+        for i in range(first, first + count):
+            ops[i] = choice if choice in BASE_OPS else None
+            preds[i] = choice if choice is not None and choice not in BASE_OPS else None
+    return ops, preds
+
+
+def _measured_candidates(ctx, parts, theirs, lengths, widths, masks):
+    """One measuring call for everything a pack has to measure (include/rcx_typed_stats.h) -> (costs uint64[nitems, 6]; the
+    items as views of the one device buffer; the bases likewise, those the measurement did not need as they were).  One gather
+    (an upload unless all lie on the device) each for the items and for the bases of the items that ask for an op."""
+    from . import typed_stats
+    nitems = len(widths)
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    need = ((masks & typed_stats.OP_BITS) != 0) & (lengths > 0)
+    costs, d_src, d_ref, offs, boffs = _measured_costs(ctx, [x for x in parts if _size(x)], [theirs[i] for i in np.flatnonzero(need)], lengths, widths, masks)
+    views = [d_src[int(offs[i]): int(offs[i + 1])] for i in range(nitems)]
+    bases = [d_ref[int(boffs[i]): int(boffs[i + 1])] if need[i] else theirs[i] for i in range(nitems)]
+    return costs, views, bases
+
+
+def _measured_costs(ctx, live, needed, lengths, widths, masks):
+    """live: the buffers that have bytes, back to back the items in order; needed: likewise the bases of the items whose mask has
+    an op bit and that have bytes -> (costs uint64[nitems, 6], the two device buffers, the items' offsets in them)."""
+    import torch
+    from . import rcx, typed_stats
+    nitems = len(widths)
+    need = ((masks & typed_stats.OP_BITS) != 0) & (lengths > 0)
+    d_src, d_ref = _gather_device(live), _gather_device(needed)
+    offs, boffs = rcx.item_offsets(lengths), rcx.item_offsets(np.where(need, lengths, 0).astype(np.uint64))
+    d_cost = torch.zeros(len(CANDIDATES) * nitems, dtype=torch.int64, device="cuda")
+    if masks.any():
+        typed_stats.items_device(ctx, d_src, d_ref if d_ref.numel() else None, offs, boffs[:-1], widths, masks, d_cost)
+    return d_cost.cpu().numpy().view(np.uint64).reshape(nitems, len(CANDIDATES)), d_src, d_ref, offs, boffs
+
+
+def _delta_items_inputs(items, bases, widths):
+    """-> (the items' bytes, their bases' bytes or None, lengths uint64[nitems], widths uint8[nitems]), checked."""
+    sources = [_source(x) for x in items]
+    if len(bases) != len(sources):
+        raise ContainerError("one base, or None, per item")
+    w = _delta_item_widths(sources, widths)
+    parts = [x for x, _ in sources]
+    lengths = np.array([_size(x) for x in parts], dtype=np.uint64)
+    theirs = [None if b is None else _source(b)[0] for b in bases]
+    for i, b in enumerate(theirs):
+        if b is not None and _size(b) != int(lengths[i]):
+            raise ContainerError(f"the base of item {i} has {_size(b)} bytes, the item {int(lengths[i])}: a base is as long as its item")
+    return parts, theirs, lengths, w
+
+
+def choose_delta_items_from_costs(costs, has_base, widths, ops="auto", predict=None):
+    """The decision of choose_delta_items from a table of costs [nitems, 6] (typed_stats.costs_numpy or the device call), without
+    a GPU: has_base and widths per item, ops and predict as pack_delta_items takes them -> (ops, predict), a name or None per
+    item.  Only the entries the masks ask for are looked at (an "auto" op: none and the three ops, with predict "auto" all six; a
+    predict "auto" without an op: none, delta, zigzag)."""
+    w = np.asarray(widths, dtype=np.uint8)
+    masks, op_entries, pred_entries = _delta_item_masks(ops, predict, list(has_base), w)
+    return _decided(costs, masks, op_entries, pred_entries)
+
+
+def delta_item_masks(has_base, widths, ops="auto", predict=None) -> np.ndarray:
+    """The masks of include/rcx_typed_stats.h that pack_delta_items and choose_delta_items measure with, uint8[nitems]."""
+    return _delta_item_masks(ops, predict, list(has_base), np.asarray(widths, dtype=np.uint8))[0]
+
+
+def choose_delta_items(items, bases, widths=None, ops="auto", predict=None, ctx=None):
+    """The decision pack_delta_items(..., ops=ops, predict=predict) makes, alone -> (ops, predict): lists with a name or None per
+    item, which given back to pack_delta_items write the same container -- and tell which tensors lean on their base.  One
+    measuring call on the GPU (include/rcx_typed_stats.h), the rule is pick_candidate."""
+    parts, theirs, lengths, w = _delta_items_inputs(items, bases, widths)
+    masks, op_entries, pred_entries = _delta_item_masks(ops, predict, [b is not None for b in theirs], w)
+    if not masks.any() or not int(lengths.sum()):  # nothing to measure: every cost is 0
+        return _decided(np.zeros((len(w), len(CANDIDATES)), np.uint64), masks, op_entries, pred_entries)
+    with _scope(ctx) as ctx:
+        costs, _, _ = _measured_candidates(ctx, parts, theirs, lengths, w, masks)
+    return _decided(costs, masks, op_entries, pred_entries)
+
+
 def pack_delta_items(items, bases, widths=None, ops="subzz", predict=None, coder: int = 0, ctx=None, checksum: bool = False, directory: bytes = b"",
                      stored=None, base_check: bool = True) -> bytes:
     """items: a list of buffers as pack_typed_items takes them; bases: one entry per item, None or a buffer of the item's byte
@@ -907,8 +1096,28 @@ def pack_delta_items(items, bases, widths=None, ops="subzz", predict=None, coder
     is None raises).  predict: as in pack_typed_items, for the items without an op; an explicit predictor on an item with one
     raises.  One gather and upload for the items and one for the bases (none for what lies on the GPU), one split call, one encode
     over the sub-items, one CRC call for the guard, one download.  base_check: the CRC-32 of every item's base goes into the
-    prefix, the only guard against unpacking with another base."""
+    prefix, the only guard against unpacking with another base.
+    "auto" as an entry of the list: the op of that item is measured (the module's docstring, pick_candidate; the one name
+    ops="auto" for all stays refused here, as it always was: choose_delta_items takes it and returns the lists) -- one
+    measuring call for everything the pack has to measure, the predict="auto" items without a base in it -- and may come out as
+    no base at all; such an item's predict entry is None, or "auto" to put the predictors into the comparison.  Then the path
+    is the one of the named choices, and the container byte for byte what choose_delta_items' lists given here write."""
     gain = _gain(stored)
+    if isinstance(ops, (list, tuple)) and _says_auto(ops):
+        parts, theirs, lengths, w = _delta_items_inputs(items, bases, widths)
+        masks, op_entries, pred_entries = _delta_item_masks(ops, predict, [b is not None for b in theirs], w)
+
+        def finish(ctx, costs, parts, theirs):
+            chosen_ops, chosen_preds = _decided(costs, masks, op_entries, pred_entries)
+            o = _item_ops(chosen_ops, [b is not None for b in theirs])
+            preds, auto = _delta_item_predictors(chosen_preds, w, o)
+            refs = [b for b, op in zip(theirs, o) if op != BASE_OP_NONE and _size(b)]
+            return _pack_delta_items_device(ctx, [x for x in parts if _size(x)], refs, lengths, w, preds, auto, o, coder, checksum, directory, gain, base_check)
+
+        if not int(lengths.sum()):  # nothing to measure: every cost is 0, and the rule says none
+            return finish(ctx, np.zeros((len(w), len(CANDIDATES)), np.uint64), parts, theirs)
+        with _scope(ctx) as ctx:
+            return finish(ctx, *_measured_candidates(ctx, parts, theirs, lengths, w, masks))
     sources = [_source(x) for x in items]
     if len(bases) != len(sources):
         raise ContainerError("one base, or None, per item")
@@ -1018,6 +1227,66 @@ def _as_tensor(name, t):
     return t
 
 
+def _tensor_candidates(named, base, block: int, op, predict):
+    """The items pack_tensors_delta cuts a state dict into, and what is to be measured of them -> dict(rows: per tensor (name,
+    its bytes, its base's bytes or None, first item, item count, the op entry, the predictor entry -- None where measured --,
+    the mask); lengths, widths, masks per item)."""
+    rows, lengths, widths, masks = [], [], [], []
+    for name, t in named.items():
+        t = _as_tensor(name, t)
+        src, width = _source(t)
+        if width not in ITEM_WIDTHS:
+            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
+        nbytes = _size(src)
+        count = -(-nbytes // (width * block)) if nbytes else 0
+        theirs = _as_tensor(name, base[name]) if name in base else None
+        if theirs is not None and (theirs.dtype != t.dtype or tuple(theirs.shape) != tuple(t.shape)):
+            theirs = None
+        each_op = (op.get(name) if isinstance(op, dict) else op) if theirs is not None else None
+        each = predict.get(name) if isinstance(predict, dict) else predict
+        m, o, p = _delta_item_masks([each_op], each, [theirs is not None], np.array([width], np.uint8))
+        rows.append((name, src, None if theirs is None else _source(theirs)[0], len(lengths), count, o[0], p[0], int(m[0])))
+        if nbytes:
+            lengths += [width * block] * (count - 1) + [nbytes - (count - 1) * width * block]
+            widths += [width] * count
+            masks += [int(m[0])] * count
+    return {"rows": rows, "lengths": np.array(lengths, np.uint64), "widths": np.array(widths, np.uint8), "masks": np.array(masks, np.uint8)}
+
+
+def tensor_delta_masks(named, base, block: int = 65536, op="auto", predict=None) -> dict:
+    """What choose_tensors_delta measures, without a GPU -> dict(lengths, widths, masks per item; first: name -> (its first item,
+    its item count)): the tables typed_stats.costs_numpy takes for choose_tensors_delta_from_costs."""
+    c = _tensor_candidates(named, base, block, op, predict)
+    return {"lengths": c["lengths"], "widths": c["widths"], "masks": c["masks"], "first": {r[0]: (r[3], r[4]) for r in c["rows"]}}
+
+
+def _tensors_decided(c, costs):
+    rows = c["rows"]
+    ops, preds = _decided(costs, c["masks"], [r[5] for r in rows for _ in range(r[4])], [r[6] for r in rows for _ in range(r[4])],
+                          groups=[(r[3], r[4]) for r in rows])
+    # (a tensor without bytes has no item to ask: the rule on costs of 0 says none)
+    return ({r[0]: (ops[r[3]] if r[4] else None if r[7] else r[5]) for r in rows}, {r[0]: (preds[r[3]] if r[4] else None if r[7] else r[6]) for r in rows})
+
+
+def choose_tensors_delta_from_costs(costs, named, base, block: int = 65536, op="auto", predict=None):
+    """The decision of choose_tensors_delta from a table of costs [nitems, 6] over the items of tensor_delta_masks, without a GPU."""
+    return _tensors_decided(_tensor_candidates(named, base, block, op, predict), costs)
+
+
+def choose_tensors_delta(named, base, block: int = 65536, op="auto", predict=None, ctx=None):
+    """The decision pack_tensors_delta(..., op=op, predict=predict) makes, alone -> (op, predict): dicts of names -> a name or
+    None, which given back to pack_tensors_delta write the same container.  Per TENSOR, pick_candidate on the sums over the
+    tensor's items: a tensor needs its base entirely or not at all."""
+    c = _tensor_candidates(named, base, block, op, predict)
+    if not c["masks"].any():
+        return _tensors_decided(c, np.zeros((len(c["masks"]), len(CANDIDATES)), np.uint64))
+    from . import typed_stats
+    with _scope(ctx) as ctx:
+        live = [r[1] for r in c["rows"] if r[4]]
+        needed = [r[2] for r in c["rows"] if r[4] and r[7] & typed_stats.OP_BITS]
+        return _tensors_decided(c, _measured_costs(ctx, live, needed, c["lengths"], c["widths"], c["masks"])[0])
+
+
 def pack_tensors_delta(named, base, block: int = 65536, op="subzz", predict=None, coder: int = 0, ctx=None, checksum: bool = False, stored=None,
                        base_check: bool = True) -> bytes:
     """named, base: dicts of names -> numpy arrays or contiguous torch tensors (CPU or GPU) -> an RCXK container whose directory
@@ -1034,6 +1303,16 @@ def pack_tensors_delta(named, base, block: int = 65536, op="subzz", predict=None
             if e is not None and name in named and (name not in base or _as_tensor(name, base[name]).dtype != _as_tensor(name, named[name]).dtype
                                                     or tuple(_as_tensor(name, base[name]).shape) != tuple(_as_tensor(name, named[name]).shape)):
                 raise ContainerError(f"{name!r} has an op, and the base has no tensor of that name, dtype and shape")
+    if _says_auto(op):
+        c = _tensor_candidates(named, base, block, op, predict)
+        if not c["masks"].any():
+            op, predict = _tensors_decided(c, np.zeros((len(c["masks"]), len(CANDIDATES)), np.uint64))
+            return pack_tensors_delta(named, base, block, op, predict, coder, ctx, checksum, stored, base_check)
+        with _scope(ctx) as ctx:  # what is measured and then packed goes up once
+            named = {name: _as_tensor(name, t).cuda() for name, t in named.items()}
+            base = {name: _as_tensor(name, base[name]).cuda() for name in named if name in base}
+            op, predict = choose_tensors_delta(named, base, block, op, predict, ctx)
+            return pack_tensors_delta(named, base, block, op, predict, coder, ctx, checksum, stored, base_check)
     parts, refs, lengths, widths, entry_preds, entry_ops, entries = [], [], [], [], [], [], []
     for name, t in named.items():
         t = _as_tensor(name, t)
