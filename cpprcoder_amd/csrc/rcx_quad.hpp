@@ -68,9 +68,10 @@ __device__ __forceinline__ u32 rcx_oct_excl_scan(u32 x, u32 m1, u32 m2, u32 m4)
 //   (D >= 0) every high word is 0 or -1: the symbol is the lane's last one plus three of them, and ~h_D & h_e is the
 //   owner word, -1 in the owning lane and 0 elsewhere (above it D < 0, h_e is -1 or -2 and h_D = -1 masks it).  That word
 //   is what ds_add puts on the count and what masks the output byte.  The scratch row's "counts" are arbitrary, and so are
-//   the symbol and the owner word then: the symbol reaches memory only as (sym & 3) * 4 + the lane's 16 bytes of the
-//   row round 1 chose (0 .. 16) and as an output byte of a block that is marked and decoded again, the owner word only as
-//   the ds_add's operand into that scratch row.
+//   the symbol and the owner word then: the symbol reaches memory only as bits 2 and 3 of its fourfold, inserted into
+//   the 16-byte aligned address of the lane's 16 bytes of the row round 1 chose (0 .. 16), and as an output byte of a
+//   block that is marked and decoded again, the owner word only as the ds_add's operand into that scratch row (DESIGN
+//   3.4, rounds 7 and 9).
 // A target at or past the total (corrupt input only) leaves no borrow in round 1 and "node 16",
 // whose counts are a scratch area behind the block's table.  Such a block is detected, not
 // decoded: it is marked in `redo` and decoded again by rcx_dec_adaptive_k, which has the
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     // different mask registers before any is used, and every DPP step has two independent
     // instructions in front of it.  Only register-to-register vector instructions are in there;
     // LDS and global accesses stay with the compiler (and its s_waitcnt placement).
-    const u32 T0p3 = T0 + 3;
+    const u32 T0p3x4 = 4u * (T0 + 3); // the lane's last symbol of a node, scaled like the symbol (below)
     const u32 leaves_lds = (u32)reinterpret_cast<uintptr_t>(seat.leaves); // low half of a flat LDS address = the LDS offset
     const u32 ring_lds = (u32)reinterpret_cast<uintptr_t>(seat.ring);
 #if defined(RCX_STAMP_DEC) /* diagnostic build only (tools/diag/stamp_quad.py): where does one symbol's time go? */
@@ -476,20 +477,52 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #define RCX_QUAD_STAMP(i)
 #define RCX_QUAD_NO_STAMP
 #endif
-// What a symbol leaves for the one behind it (below): its number (valid in the lane that owns it), that lane's word (-1
-// there, 0 in the quad's other lanes), and the LDS address of the lane's four counts of the node.
-    u32 p_sym_ = 0, p_la_ = leaves_lds, p_own_ = 0;
+// What a symbol leaves for the one behind it (below): its number scaled by 4 in two parts -- p_sb4_ = 64 x node + 4 x the
+// lane's last symbol, p_hs_ = the lane's three borrows (0 or -1 each), 4 x symbol = (p_hs_ << 2) + p_sb4_, valid in the
+// lane that owns it --, that lane's word (-1 there, 0 in the quad's other lanes), and the LDS address of the lane's four
+// counts of the node.
+    u32 p_hs_ = 0, p_sb4_ = 0, p_la_ = leaves_lds, p_own_ = 0;
+// {rem, 0}, the pair round 2 adds to, lives in one fixed register pair: its high half is zeroed here, once, and the
+// sequence behind the leaf read writes the low half by its name (RCX_QD_REM).
+#define RCX_QD_R_LO "v116"
+#define RCX_QD_R_PAIR "{v[116:117]}"
+    u64 R_ = 0;
+// Round 2's five pairs D, Y_a, Y_b, Y_c, Y_e: fixed registers as well, written and read inside one sequence and listed as
+// clobbered by it, so that the sequence can name their halves.
+#define RCX_QD_D "v[118:119]"
+#define RCX_QD_D_L "v118"
+#define RCX_QD_D_H "v119"
+#define RCX_QD_YA "v[120:121]"
+#define RCX_QD_YA_L "v120"
+#define RCX_QD_YA_H "v121"
+#define RCX_QD_YB "v[122:123]"
+#define RCX_QD_YB_L "v122"
+#define RCX_QD_YB_H "v123"
+#define RCX_QD_YC "v[124:125]"
+#define RCX_QD_YC_L "v124"
+#define RCX_QD_YC_H "v125"
+#define RCX_QD_YE "v[126:127]"
+#define RCX_QD_YE_L "v126"
+#define RCX_QD_YE_H "v127"
+#define RCX_QD_PAIRS_CLOBBERED "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127"
 // One symbol.  Its byte and the +1 on its count are NOT made here but by the next symbol (HP = 1: PWORD, PSHIFT are that
 // earlier symbol's word and bit position) or by RCX_QUAD_DEC_FINISH: nothing the coder state needs depends on them, so
 // they fill the slots the node index's steps across the quad need anyway (the ds_add still comes before the next leaf
 // read: LDS serves a wave's operations in order) and the wait for the leaf read.
 // The counts are kept negated (a symbol seen c times: -c), so the +1 is a ds_add of the owner word as it is, and the byte
 // is the symbol ANDed with it; the first byte of an output word (PSHIFT == 0) IS the word.
+// The symbol is carried scaled by 4 (psym4), because its count's address is then ONE bit insert: bits 2 and 3 of psym4
+// into the 16-byte aligned address of the lane's four counts.  The bit insert is also what bounds the address: whatever
+// psym4 holds -- in a block that took "node 16" the borrows are arbitrary words -- the result lies in [pla, pla + 12],
+// inside the lane's own 16 bytes of the row round 1 chose (an add of 4 x the borrows to pla would not: the ds_add of a
+// damaged block would land in another wave's tables).  psym4 & pown is 4 x the byte: it goes into the word at PSHIFT - 2,
+// and the first byte of a word is shifted down.
 #define RCX_QD_PREV_A_0 "s_nop 1\n\t"
-#define RCX_QD_PREV_A_1 "v_and_b32 %[pad], 3, %[psym]\n\t"                                                         \
-                        "v_lshl_add_u32 %[pad], %[pad], 2, %[pla]\n\t" /* LDS address of the earlier symbol's count */
-#define RCX_QD_PREV_S_FIRST "v_and_b32 %[pword], %[psym], %[pown]\n\t"
-#define RCX_QD_PREV_S_NEXT "v_and_b32 %[pye], %[psym], %[pown]\n\t"                                                 \
+#define RCX_QD_PREV_A_1 "v_lshl_add_u32 %[psym4], %[phs], 2, %[psb4]\n\t"                                           \
+                        "v_bfi_b32 %[pad], 12, %[psym4], %[pla]\n\t" /* LDS address of the earlier symbol's count */
+#define RCX_QD_PREV_S_FIRST "v_and_b32 %[pword], %[psym4], %[pown]\n\t"                                             \
+                            "v_lshrrev_b32 %[pword], 2, %[pword]\n\t"
+#define RCX_QD_PREV_S_NEXT "v_and_b32 %[pye], %[psym4], %[pown]\n\t"                                                \
                            "v_lshl_or_b32 %[pword], %[pye], %[psh], %[pword]\n\t"
 #define RCX_QP3 "quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 /* behind the leaf read: the remainder (round 1's other result) across the quad, and as the pair {rem, 0} round 2 adds to; \
@@ -504,14 +537,13 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
                      "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP1                                          \
                      "v_add_u32 %[u3], %[u3], %[h3]\n\t"                                                   \
                      "v_add_u32 %[u4], %[u4], %[h4]\n\t"                                                   \
-                     "v_min_u32_dpp %[rm], %[rm], %[rm] " RCX_QP2                                          \
+                     "v_min_u32_dpp " RCX_QD_R_LO ", %[rm], %[rm] " RCX_QP2 /* the low half of R; its high half stays 0 */ \
                      PREV                                                                                  \
-                     "v_mad_u64_u32 %[R], %[cr], %[rm], 1, 0"                                              \
                      : [u1] "+v"(nU1), [u2] "+v"(nU2), [u3] "+v"(nU3), [u4] "+v"(nU4), [rm] "=&v"(rem_),    \
-                       [R] "=&v"(R_), [cr] "=&s"(cr_) __VA_ARGS__                                           \
+                       [R] "+" RCX_QD_R_PAIR(R_) __VA_ARGS__                                                \
                      : [low] "v"(in.low), [x1] "v"(x1_), [x2] "v"(x2_),                                    \
                        [x3] "v"(x3_), [x4] "v"(x4_), [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_), \
-                       [pown] "v"(p_own_), [psym] "v"(p_sym_), [psh] "n"(PSHIFT))
+                       [pown] "v"(p_own_), [psym4] "v"(psym4_), [psh] "n"((PSHIFT) > 2 ? (PSHIFT)-2 : 0))
 #define RCX_QUAD_DEC_SYMBOL(MUL, INC, SH, HP, PWORD, PSHIFT)                                               \
     {                                                                                                      \
         /* cpprcoder.h:926-940 (in.n4 = the next four stream bytes, ready since the previous symbol) */    \
@@ -525,8 +557,8 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
            multiply-add per bound: {low, 0} - U_k * t has low - U_k * t in its low word and the borrow, 0 or -1, in   \
            its high word (its carry-out goes to a mask register nothing reads) */                          \
         const u64 lowp_ = in.low;                                                                          \
-        u32 node_, rem_, ro_, la_, pad_, pye_;                                                             \
-        u64 X1_, X2_, X3_, X4_, R_, cz_, cr_, cy_;                                                         \
+        u32 node_, rem_, ro_, la_, pad_, pye_, psym4_;                                                     \
+        u64 X1_, X2_, X3_, X4_, cz_, cy_;                                                                  \
         asm volatile("v_mad_i64_i32 %[X1], %[cz], %[n1], %[t], %[lp]\n\t"                                  \
                      "v_mad_i64_i32 %[X2], %[cz], %[n2], %[t], %[lp]\n\t"                                  \
                      "v_mad_i64_i32 %[X3], %[cz], %[n3], %[t], %[lp]\n\t"                                  \
@@ -543,9 +575,9 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
         asm volatile("v_add3_u32 %[nd], %[h1], %[h2], %[h3]\n\t"                                           \
                      "v_add3_u32 %[nd], %[nd], %[h4], 4\n\t" /* 4 - the lane's borrows (they stay: the update below) */ \
                      RCX_QD_PREV_A_##HP                                                                    \
-                     : [nd] "=&v"(node_), [pad] "=&v"(pad_)                                                 \
+                     : [nd] "=&v"(node_), [pad] "=&v"(pad_), [psym4] "=&v"(psym4_)                          \
                      : [h1] "v"(h1_), [h2] "v"(h2_), [h3] "v"(h3_), [h4] "v"(h4_),                         \
-                       [psym] "v"(p_sym_), [pla] "v"(p_la_));                                              \
+                       [phs] "v"(p_hs_), [psb4] "v"(p_sb4_), [pla] "v"(p_la_));                            \
         if (HP) (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), p_own_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916, the earlier symbol's: -1 on its negated count */ \
         asm volatile("v_add_u32_dpp %[nd], %[nd], %[nd] " RCX_QP1                                          \
                      "v_bfe_u32 %[ro], %[bp], 5, 5\n\t"  /* ring slot of the next pair ... */               \
@@ -574,8 +606,10 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
            lanes' unscaled sums across the quad), D = {rem, 0} + P x t, and Y_k = Y_(k-1) + l_k x t from Y_0 = D: the low \
            words are rem - t x (the counts up to and including the lane's k-th), the high words their borrows.  In the \
            lane that owns the symbol and below it D >= 0 and every high word is 0 or -1; above it D < 0, -1 or -2. */ \
+        /* The five pairs are fixed registers (RCX_QD_D ... RCX_QD_YE, scratch of this one sequence): their words have   \
+           names, so nothing of the compiler's has to stand between the multiply-adds and what reads their halves. */ \
         u32 qe_, pre_, o2_, o3_;                                                                           \
-        u64 D_, Ya_, Yb_, Yc_, Ye_;                                                                        \
+        u32 lo_, rg_, hi_;                                                                                 \
         asm volatile("v_add3_u32 %[qe], %[lx], %[ly], %[lz]\n\t"                                           \
                      "v_add_u32 %[qe], %[qe], %[lw]\n\t"                                                   \
                      "v_alignbit_b32 %[n4], %[w1], %[w0], %[bp]\n\t" /* (the next symbol's 4 stream bytes at bp8 ... */ \
@@ -584,43 +618,38 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
                      "v_and_b32_dpp %[o2], %[qe], %[m2] " RCX_QP2                                          \
                      "v_and_b32_dpp %[o3], %[qe], %[m2] " RCX_QP3                                          \
                      "v_add3_u32 %[qe], %[pre], %[o2], %[o3]\n\t" /* P */                                        \
-                     "v_mad_i64_i32 %[D], %[cy], %[qe], %[t], %[R]\n\t"                                    \
-                     "v_mad_i64_i32 %[Ya], %[cy], %[lx], %[t], %[D]\n\t"                                   \
-                     "v_mad_i64_i32 %[Yb], %[cy], %[ly], %[t], %[Ya]\n\t"                                  \
-                     "v_mad_i64_i32 %[Yc], %[cy], %[lz], %[t], %[Yb]\n\t"                                  \
-                     "v_mad_i64_i32 %[Ye], %[cy], %[lw], %[t], %[Yc]"                                      \
-                     : [n4] "=&v"(in.n4), [qe] "=&v"(qe_), [pre] "=&v"(pre_), [o2] "=&v"(o2_), [o3] "=&v"(o3_), \
-                       [D] "=&v"(D_), [Ya] "=&v"(Ya_), [Yb] "=&v"(Yb_), [Yc] "=&v"(Yc_),    \
-                       [Ye] "=&v"(Ye_), [cy] "=&s"(cy_)                                                     \
-                     : [lx] "v"(l_.x), [ly] "v"(l_.y), [lz] "v"(l_.z), [lw] "v"(l_.w), [t] "v"(t_),        \
-                       [R] "v"(R_), [m1] "v"(m1), [m2] "v"(m2),                                            \
-                       [w0] "v"(in.w0), [w1] "v"(in.w1), [bp] "v"(in.bp8), [swap] "s"(0x00010203u));       \
-        /* (as in round 1, something of the compiler's between the pairs and the statement that reads their words: the \
-           symbol, if none of the lane's counts borrows.  It costs an s_nop itself if it lands in a register the      \
-           sequence above wrote, so that one's scratch registers stay taken until the next: its last four operands) */ \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-        const u32 sb_ = (node_ << 4) + T0p3;                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                 \
-        const u32 d2_ = (u32)D_, ya_ = (u32)Ya_, yb_ = (u32)Yb_, yc_ = (u32)Yc_, ye_ = (u32)Ye_;           \
-        const u32 hd_ = (u32)(D_ >> 32), ha_ = (u32)(Ya_ >> 32), hb_ = (u32)(Yb_ >> 32), hc_ = (u32)(Yc_ >> 32), \
-                  he_ = (u32)(Ye_ >> 32);                                                                  \
-        u32 lo_, rg_, hi_;                                                                                 \
-        asm volatile("v_min3_u32 %[lo], %[d2], %[ya], %[yb]\n\t"                                           \
-                     "v_max3_u32 %[hi], %[ya], %[yb], %[yc]\n\t"                                           \
-                     "v_min_u32 %[lo], %[lo], %[yc]\n\t"                                                   \
-                     "v_max_u32 %[hi], %[hi], %[ye]\n\t"                                                   \
-                     "v_add3_u32 %[sym], %[sb], %[ha], %[hb]\n\t"                                          \
+                     "v_mad_i64_i32 " RCX_QD_D ", %[cy], %[qe], %[t], %[R]\n\t"                             \
+                     "v_mad_i64_i32 " RCX_QD_YA ", %[cy], %[lx], %[t], " RCX_QD_D "\n\t"                    \
+                     "v_mad_i64_i32 " RCX_QD_YB ", %[cy], %[ly], %[t], " RCX_QD_YA "\n\t"                   \
+                     "v_mad_i64_i32 " RCX_QD_YC ", %[cy], %[lz], %[t], " RCX_QD_YB "\n\t"                   \
+                     "v_mad_i64_i32 " RCX_QD_YE ", %[cy], %[lw], %[t], " RCX_QD_YC "\n\t"                   \
+                     "v_min3_u32 %[lo], " RCX_QD_D_L ", " RCX_QD_YA_L ", " RCX_QD_YB_L "\n\t"              \
+                     "v_max3_u32 %[hi], " RCX_QD_YA_L ", " RCX_QD_YB_L ", " RCX_QD_YC_L "\n\t"             \
+                     "v_min_u32 %[lo], %[lo], " RCX_QD_YC_L "\n\t"                                         \
+                     "v_max_u32 %[hi], %[hi], " RCX_QD_YE_L "\n\t"                                         \
+                     "v_add3_u32 %[hs], " RCX_QD_YA_H ", " RCX_QD_YB_H ", " RCX_QD_YC_H "\n\t" /* the symbol = the lane's last one + these three borrows */ \
                      "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP1                                          \
-                     "v_add_u32 %[sym], %[sym], %[hc]\n\t"                                                 \
                      "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP1                                          \
-                     "v_bfi_b32 %[own], %[hd], 0, %[he]\n\t" /* ~h_D & h_e: -1 in the lane that owns the symbol, 0 elsewhere */ \
+                     "v_bfi_b32 %[own], " RCX_QD_D_H ", 0, " RCX_QD_YE_H "\n\t" /* ~h_D & h_e: -1 in the lane that owns the symbol, 0 elsewhere */ \
                      "v_min_u32_dpp %[lo], %[lo], %[lo] " RCX_QP2                                          \
                      "v_max_u32_dpp %[hi], %[hi], %[hi] " RCX_QP2                                          \
                      "v_sub_u32 %[rg], %[lo], %[hi]"                                                       \
-                     : [lo] "=&v"(lo_), [rg] "=&v"(rg_), [sym] "=&v"(p_sym_), [own] "=&v"(p_own_), [hi] "=&v"(hi_) \
-                     : [d2] "v"(d2_), [ya] "v"(ya_), [yb] "v"(yb_), [yc] "v"(yc_), [ye] "v"(ye_), [sb] "v"(sb_), \
-                       [hd] "v"(hd_), [ha] "v"(ha_), [hb] "v"(hb_), [hc] "v"(hc_), [he] "v"(he_),          \
-                       "v"(qe_), "v"(pre_), "v"(o2_), "v"(o3_));                                            \
+                     : [n4] "=&v"(in.n4), [qe] "=&v"(qe_), [pre] "=&v"(pre_), [o2] "=&v"(o2_), [o3] "=&v"(o3_), \
+                       [lo] "=&v"(lo_), [rg] "=&v"(rg_), [hs] "=&v"(p_hs_), [own] "=&v"(p_own_), [hi] "=&v"(hi_), \
+                       [cy] "=&s"(cy_)                                                                      \
+                     : [lx] "v"(l_.x), [ly] "v"(l_.y), [lz] "v"(l_.z), [lw] "v"(l_.w), [t] "v"(t_),        \
+                       [R] "v"(R_), [m1] "v"(m1), [m2] "v"(m2),                                            \
+                       [w0] "v"(in.w0), [w1] "v"(in.w1), [bp] "v"(in.bp8), [swap] "s"(0x00010203u)         \
+                     : RCX_QD_PAIRS_CLOBBERED);                                                            \
+        /* The compiler's first vector instruction behind a sequence costs an s_nop 0 if it touches a register the      \
+           sequence wrote.  So the one that stands there reads none of them: 4 x (16 x node + the lane's last symbol),    \
+           the part of the scaled symbol that round 1 decided, which the next symbol adds the borrows to.  Nor may it    \
+           write one: the empty statement behind it keeps the sequence's scratch registers taken and the pairs' out of  \
+           its reach (round 7's remedy; it leans on nothing but the operands). */                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        p_sb4_ = (node_ << 6) + T0p3x4;                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                                 \
+        asm volatile("" : : "v"(p_sb4_), "v"(qe_), "v"(pre_), "v"(o2_), "v"(o3_), "v"(hi_) : RCX_QD_PAIRS_CLOBBERED); \
         RCX_QUAD_STAMP(1);                                                                                 \
         in.low = lo_;   /* :906 */                                                                         \
         in.range = rg_; /* :907 */                                                                         \
@@ -628,14 +657,14 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
     }
 // The byte and the count of the last symbol decoded (no symbol follows that would make them): into WORD at bit SHIFT.
 #define RCX_QD_FINISH(BYTE, SHIFT, ...)                                                                    \
-        asm volatile("v_and_b32 %[pad], 3, %[psym]\n\t"                                                    \
+        asm volatile(RCX_QD_PREV_A_1                                                                       \
                      BYTE                                                                                  \
-                     "v_lshl_add_u32 %[pad], %[pad], 2, %[pla]"                                            \
-                     : [pad] "=&v"(pad_) __VA_ARGS__                                                        \
-                     : [pown] "v"(p_own_), [psym] "v"(p_sym_), [pla] "v"(p_la_), [psh] "n"(SHIFT))
+                     : [pad] "=&v"(pad_), [psym4] "=&v"(psym4_) __VA_ARGS__                                 \
+                     : [pown] "v"(p_own_), [phs] "v"(p_hs_), [psb4] "v"(p_sb4_), [pla] "v"(p_la_),         \
+                       [psh] "n"((SHIFT) > 2 ? (SHIFT)-2 : 0))
 #define RCX_QUAD_DEC_FINISH(WORD, SHIFT)                                                                    \
     {                                                                                                      \
-        u32 pad_, pye_;                                                                                    \
+        u32 pad_, pye_, psym4_;                                                                            \
         if ((SHIFT) == 0) RCX_QD_FINISH(RCX_QD_PREV_S_FIRST, 0, , [pword] "=&v"(WORD));                    \
         else RCX_QD_FINISH(RCX_QD_PREV_S_NEXT, SHIFT, , [pye] "=&v"(pye_), [pword] "+v"(WORD));            \
         (void)__hip_atomic_fetch_add(reinterpret_cast<RcxLdsU32*>(pad_), p_own_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* :916 */ \
@@ -790,6 +819,24 @@ __global__ __launch_bounds__(64 * WAVES) void rcx_dec_quad_k(const u8* __restric
 #undef RCX_QD_PREV_S_NEXT
 #undef RCX_QD_REM
 #undef RCX_QD_FINISH
+#undef RCX_QD_R_LO
+#undef RCX_QD_R_PAIR
+#undef RCX_QD_D
+#undef RCX_QD_D_L
+#undef RCX_QD_D_H
+#undef RCX_QD_YA
+#undef RCX_QD_YA_L
+#undef RCX_QD_YA_H
+#undef RCX_QD_YB
+#undef RCX_QD_YB_L
+#undef RCX_QD_YB_H
+#undef RCX_QD_YC
+#undef RCX_QD_YC_L
+#undef RCX_QD_YC_H
+#undef RCX_QD_YE
+#undef RCX_QD_YE_L
+#undef RCX_QD_YE_H
+#undef RCX_QD_PAIRS_CLOBBERED
 #undef RCX_QP3
 #undef RCX_QUAD_DIVQ_LOAD
 #undef RCX_QUAD_DIVQ_ENTRY
