@@ -85,6 +85,11 @@ base entirely or not at all; pack_delta decides among the three ops only (pick_o
 because RCXD cannot say "no base".  The container is byte for byte what the decided names given explicitly write, and nothing in
 it records that they were measured; choose_delta_items and choose_tensors_delta return the decision alone, their
 _from_costs siblings make it from a table without a GPU.
+
+open_items(blob) (include/rcx_picks.h, cpprcoder_amd/picks.py) is for a reader that picks on the GPU: an RCXI container, or the
+stored item container, is parsed once and its payload, stream table, stored flags and lengths are put on the device; decode_into
+takes picks, destinations and their count from device tensors, only enqueues, and can be captured in a graph and replayed
+against tables that device code rewrites.  A bad entry is skipped and latched (sync_status), every other entry decodes.
 """
 import contextlib
 
@@ -379,6 +384,83 @@ def unpack_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
             picked = np.arange(c["nitems"], dtype=np.uint64) if pick is None else pick
             return [x.tobytes() for x in _decode_picked_checked(ctx, c, c["lengths"], picked, "item")]
         return [x.tobytes() for x in ctx.decode_items(c["payload"], c["offsets"], c["lengths"], pick=pick, coder=c["coder"])]
+
+
+class OpenItems:
+    """An item container on the device (open_items): payload, stream table, stored flags and the items' lengths are uploaded
+    once; decode_into enqueues one call whose picks, destinations and count are read on the device (include/rcx_picks.h)."""
+
+    def __init__(self, c, lengths, offsets, stored, crcs, ctx):
+        import torch
+        from . import picks, rcx
+        self.coder, self.nitems = c["coder"], len(lengths)
+        self.lengths = np.array(lengths, dtype=np.uint64)
+        self.crcs = crcs
+        self.max_len = int(self.lengths.max()) if self.nitems else 0
+        self._own = ctx is None
+        self.ctx = rcx.Context(0) if ctx is None else ctx
+        self.payload_size = len(c["payload"])
+        self.d_payload = torch.zeros(max(self.payload_size, 16), dtype=torch.uint8, device="cuda")
+        if self.payload_size:
+            self.d_payload[: self.payload_size] = _cuda(c["payload"])
+        self.d_offsets = _cuda(offsets)
+        self.d_stored = None if stored is None else _cuda(np.asarray(stored) != 0, dtype=np.uint8)
+        self.d_lengths = _cuda(self.lengths if self.nitems else np.zeros(1, np.uint64))
+        self._picks = picks
+
+    def reserve(self, max_pick: int) -> None:
+        """The scratch of decode_into calls with at most max_pick entries: after it they allocate nothing in the context."""
+        self._picks.reserve(self.ctx, max_pick, self.max_len, self.coder)
+
+    def decode_into(self, d_pick, d_dst_at, d_count, d_dst, max_pick: int | None = None, stream=None) -> None:
+        """Entry k < d_count[0]: item d_pick[k] -> d_dst[d_dst_at[k] : + its length].  d_pick, d_dst_at: int64 cuda tensors
+        [>= max_pick]; d_count: an int64 cuda tensor of one entry; d_dst: a uint8 cuda tensor.  Enqueues only: the lengths are
+        looked up on the device (an entry that names no item gets length 1, so that the call skips and latches it; entries at or
+        past the count may hold anything).  Failures are the context's: sync_status()."""
+        import torch
+        max_pick = d_pick.numel() if max_pick is None else int(max_pick)
+        p = d_pick[:max_pick]
+        inside = (p >= 0) & (p < self.nitems)
+        d_len = torch.where(inside, self.d_lengths[torch.clamp(p, 0, max(self.nitems - 1, 0))], torch.ones_like(p))
+        self._picks.decode_device(self.ctx, self.d_payload, self.payload_size, self.d_offsets, p, d_dst_at, d_len, d_count, d_dst, self.max_len,
+                                  max_pick=max_pick, stored=self.d_stored, coder=self.coder, stream=stream)
+
+    def verify(self, d_out, pick, dst_offsets=None) -> None:
+        """For a result that lies back to back (item pick[k] at dst_offsets[k], the prefix sums of the lengths if None): the
+        CRC-32 check of a container with checksums, on the device -> ChecksumError naming the item.  pick is a HOST table."""
+        if self.crcs is None:
+            return
+        from . import rcx
+        pick = np.asarray(pick, dtype=np.int64)
+        doffs = rcx.item_offsets(self.lengths[pick]) if dst_offsets is None else np.asarray(dst_offsets, dtype=np.uint64)
+        self.ctx.verify_items_device(d_out, doffs, _cuda(self.crcs[pick]))
+        _sync_checked(self.ctx, "item", lambda k: int(pick[k]))
+
+    def close(self) -> None:
+        if self._own and self.ctx is not None:
+            self.ctx.close()
+        self.ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def open_items(blob, ctx=None) -> OpenItems:
+    """An item container -- RCXI (pack_items, with or without checksums) or the stored item container, RCXJ whose items all have
+    width 1 (pack_typed_items(items, widths=1, stored=...)) -- parsed once and put on the device -> OpenItems, whose decode_into
+    takes picks, destinations and their count from device memory and can be captured in a graph.  ctx=None: a context of its
+    own, closed by close()."""
+    head = bytes(memoryview(blob)[:4])
+    if head == TYPED_ITEMS_MAGIC:
+        c = parse_typed_items(blob)
+        if np.any(c["widths"] != 1):
+            raise ContainerError("open_items takes typed items of width 1 only: wider items are joined after they are decoded")
+        return OpenItems(c, c["lengths"], c["offsets"], c.get("stored"), c["crcs"], ctx)
+    c = parse_items(blob)
+    return OpenItems(c, c["lengths"], c["offsets"], None, c["crcs"], ctx)
 
 
 # ---- RCXT: the byte-plane filter in front of the coder -----------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "rcx_base_api.hpp" // residuals against a base buffer in front of the plane filter (include/rcx_base.h)
 #include "rcx_base_items_api.hpp" // the same per item: an op and a base span of its own for every buffer (include/rcx_base_items.h)
 #include "rcx_typed_stats_api.hpp" // the cost of every candidate predictor and op of every item, in one pass (include/rcx_typed_stats.h)
+#include "rcx_picks_api.hpp" // item decode planned on the device: every table in HBM, capturable (include/rcx_picks.h)
 
 extern "C" {
 

@@ -1,12 +1,14 @@
 // rcx_geom.hpp -- where a coding kernel finds the bytes of its work entry `blk`: the geometry policy.
 //
-// Every coding kernel is a template over one of these two.  RcxBlocks is the many-block geometry (one buffer cut into
+// Every coding kernel is a template over one of these.  RcxBlocks is the many-block geometry (one buffer cut into
 // blocks of one size: position and length follow from the index); it is empty, and a kernel instantiated with it is
 // the kernel the block calls always ran.  RcxItems is the item geometry (rcx_encode_items* / rcx_decode_items*,
 // include/rcx.h): position and length come from tables in WORK ORDER that the host planned (rcx_api.hip, ItemPlan) and
 // uploaded with the call.  A launch covers the entries of one length class, whose scratch slots share a stride: the
 // table pointers, like sizes / redo / starts / models, are already advanced to the class's first entry, so a kernel
-// indexes all of them by `blk` as before.
+// indexes all of them by `blk` as before.  RcxPicks (rcx_decode_picks_device, include/rcx_picks.h) is the item geometry
+// whose tables a kernel planned (rcx_picks.hpp): the launch is shaped by the most entries there can be, and how many of the
+// tables' entries are meant is a word in device memory that every wave reads when it opens (`counted`).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,15 +16,24 @@
 
 struct RcxBlocks {
     static constexpr bool items = false;
+    static constexpr bool counted = false;
 };
 
 struct RcxItems {
     static constexpr bool items = true;
+    static constexpr bool counted = false;
     const u64* at;     // byte offset of the entry's bytes in d_src (encode) / d_dst (decode)
     const u32* len;    // its length, 1 .. RCX_MAX_BLOCK (an item of length 0 has no entry)
     const u32* id;     // what a failure reports: the item (encode, also its place in the offsets table), the pick position (decode)
     const u32* stream; // decode: which stream of the compacted set the entry reads
     const u32* inv;    // the size scan, which runs in the caller's order: item -> its work entry, 0xFFFFFFFF for an item of length 0
+};
+
+// The decoders only.  Entries 0 .. *nlive - 1 of the tables are meant; what lies behind them is never read (entry 0 apart,
+// as above, so the tables have one entry at least).
+struct RcxPicks : RcxItems {
+    static constexpr bool counted = true;
+    const u32* nlive;
 };
 
 // Where entry `blk` lies.  A lane without an entry has length 0 and the position of the launch's first entry -- with
@@ -38,18 +49,28 @@ __device__ __forceinline__ void rcx_where(const RcxItems& g, bool live, u64 blk,
 // one); with items they are the tables' (and the block lines are left without a use).  RCX_ENTRY_ONLY is the same for a
 // kernel that can run as the second pass behind a many-lane kernel: ONLY != nullptr leaves just the entries that one
 // marked (ONLY[blk] != 0), and a wave none of whose lanes has an entry returns.
+// With a counted geometry (RcxPicks) `live` also asks the device's count, and a wave none of whose lanes has an entry
+// returns: the launch is shaped for the most entries there can be, and no decoder has a barrier.  (`if constexpr` on a
+// dependent condition: the other geometries' kernels are instantiated without these lines.)
 // Macros, not functions: a function is optimised on its own before it is inlined into the kernel, and what arrives
 // there differs enough from these lines written in place that 18 of the 50 kernels came out with different
 // instructions, down into their symbol loops (tools/diag/kernel_diff.py).
+#define RCX_ENTRY_COUNTED(GEOM, BLK)                                                                  \
+    if constexpr (decltype(GEOM)::counted) {                                                          \
+        live = live && (BLK) < (u64)(GEOM).nlive[0];                                                  \
+        if (!__any(live)) return;                                                                     \
+    }
 #define RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)                                                          \
     u64 at = live ? (BLK) * (u64)(BLOCK) : 0;                                                         \
     u32 len = live ? (u32)(((N) - at) < (u64)(BLOCK) ? ((N) - at) : (u64)(BLOCK)) : 0u;               \
     if constexpr (decltype(GEOM)::items) rcx_where(GEOM, live, BLK, at, len)
 #define RCX_ENTRY(GEOM, BLK, NBLOCKS, N, BLOCK)                                                       \
     bool live = (BLK) < (NBLOCKS);                                                                    \
+    RCX_ENTRY_COUNTED(GEOM, BLK)                                                                      \
     RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)
 #define RCX_ENTRY_ONLY(GEOM, BLK, NBLOCKS, N, BLOCK, ONLY)                                            \
     bool live = (BLK) < (NBLOCKS);                                                                    \
+    RCX_ENTRY_COUNTED(GEOM, BLK)                                                                      \
     if (ONLY) {                                                                                       \
         live = live && (ONLY)[BLK] != 0;                                                              \
         if (!__any(live)) return;                                                                     \
