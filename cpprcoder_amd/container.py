@@ -880,6 +880,135 @@ def unpack_typed_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
         return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
 
 
+class OpenTypedItems:
+    """A typed item container on the device (open_typed_items): payload, stream table, stored flags, the items' lengths, widths
+    and predictors and sub_first are uploaded once; decode_into enqueues the sub-items' decode into a staging buffer
+    (include/rcx_picks.h) and their join to where the caller wants the items (include/rcx_typed_picks.h), picks, destinations
+    and count read on the device.  Both calls' tables have SLOTS entries a pick, so that a latched position of either stage
+    names the pick: pick_of."""
+
+    SLOTS = 8  # table entries a pick: its sub-items in the decode call (a width is 8 at the most), itself in the first one of the join call
+
+    def __init__(self, c, ctx):
+        import torch
+        from . import picks, rcx, typed_picks
+        self.coder, self.nitems, self.nsub = c["coder"], c["nitems"], c["nsub"]
+        self.lengths = np.array(c["lengths"], dtype=np.uint64)
+        self.widths, self.preds = np.array(c["widths"], dtype=np.uint8), np.array(c["preds"], dtype=np.uint8)
+        self.sub_first = np.array(c["sub_first"], dtype=np.int64)
+        self.crcs = c["crcs"]
+        self.max_len = int(self.lengths.max()) if self.nitems else 0
+        self.max_sub_len = int(c["sub_lengths"].max()) if self.nsub else 0
+        self._own = ctx is None
+        self.ctx = rcx.Context(0) if ctx is None else ctx
+        self.payload_size = len(c["payload"])
+        self.d_payload = torch.zeros(max(self.payload_size, 16), dtype=torch.uint8, device="cuda")
+        if self.payload_size:
+            self.d_payload[: self.payload_size] = _cuda(c["payload"])
+        self.d_offsets = _cuda(c["offsets"])
+        stored = c.get("stored")
+        self.d_stored = None if stored is None else _cuda(np.asarray(stored) != 0, dtype=np.uint8)
+        some = self.nitems > 0
+        self.d_lengths = _cuda(self.lengths if some else np.zeros(1, np.uint64))
+        self.d_widths = _cuda(self.widths if some else np.ones(1, np.uint8)).to(torch.int64)
+        self.d_preds = _cuda(self.preds if some else np.zeros(1, np.uint8)).to(torch.int64)
+        self.d_sub_first = _cuda(self.sub_first)
+        self.max_bytes, self.d_stage = 0, None
+        self._picks, self._join = picks, typed_picks
+
+    def reserve(self, max_pick: int, max_bytes: int) -> None:
+        """The scratch of decode_into calls with at most max_pick picks of at most max_bytes together, and the staging buffer of
+        max_bytes: after it they allocate nothing in the context."""
+        import torch
+        self._picks.reserve(self.ctx, self.SLOTS * max_pick, self.max_sub_len, self.coder)
+        self._join.reserve(self.ctx, self.SLOTS * max_pick, max_bytes)
+        self.max_bytes = int(max_bytes)
+        self.d_stage = torch.zeros(max(self.max_bytes, 16), dtype=torch.uint8, device="cuda")
+
+    def pick_of(self, position: int) -> int:
+        """The pick position k that a latched position of decode_into names (sync_status()[1]), whichever stage latched it."""
+        return int(position) // self.SLOTS
+
+    def decode_into(self, d_pick, d_dst_at, d_count, d_dst, max_pick: int | None = None, stream=None) -> None:
+        """Entry k < d_count[0]: item d_pick[k], joined -> d_dst[d_dst_at[k] : + its length].  d_pick, d_dst_at: int64 cuda tensors
+        [>= max_pick]; d_count: an int64 cuda tensor of one entry; d_dst: a uint8 cuda tensor; reserve() comes first, and the picked
+        items have at most its max_bytes between them (else nothing is joined and RCX_E_CAPACITY is latched).  Enqueues only, all of
+        it on `stream` (a torch stream; None: the current one).  An entry that names no item is skipped and latched; entries at or past
+        the count may hold anything.  Failures are the context's: sync_status(), its position through pick_of."""
+        import torch
+        if self.d_stage is None:
+            raise ContainerError("reserve(max_pick, max_bytes) comes first: it makes the staging buffer")
+        max_pick = d_pick.numel() if max_pick is None else int(max_pick)
+        S = self.SLOTS
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            p = d_pick[:max_pick]
+            meant = torch.arange(max_pick, device=p.device) < d_count[:1]
+            inside = meant & (p >= 0) & (p < self.nitems)
+            item = torch.where(inside, p, torch.zeros_like(p))
+            zero = torch.zeros_like(p)
+            length = torch.where(inside, self.d_lengths[item], zero)
+            w = torch.where(inside, self.d_widths[item], torch.ones_like(p))
+            stage_at = torch.cumsum(length, 0) - length
+            # the decode call's tables: slot q < w of pick k is its plane q, m bytes at q * m of the pick's staging span, the last with the tail
+            q = torch.arange(S, device=p.device).unsqueeze(0)
+            m = (length // w).unsqueeze(1)
+            tail = (length - (length // w) * w).unsqueeze(1)
+            live = q < w.unsqueeze(1)
+            sub_len = torch.where(live, m + torch.where(q == w.unsqueeze(1) - 1, tail, torch.zeros_like(tail)), torch.zeros_like(q))
+            sub_stream = self.d_sub_first[item].unsqueeze(1) + q
+            sub_at = stage_at.unsqueeze(1) + q * m
+            # a pick that names no item: a stream that does not exist, so that the call skips it and latches the pick
+            lost = (meant & ~inside).unsqueeze(1) & (q == 0)
+            sub_len = torch.where(lost, torch.ones_like(sub_len), sub_len)
+            sub_stream = torch.where(lost, torch.full_like(sub_stream, self.nsub), sub_stream)
+            count = d_count[:1] * S
+            # the join call's tables: the pick itself in its first slot, the others empty
+            first = (q == 0).to(torch.int64)
+            from_at = (stage_at.unsqueeze(1) * first).contiguous()
+            to_at = (torch.where(inside, d_dst_at[:max_pick], zero).unsqueeze(1) * first).contiguous()
+            item_len = (length.unsqueeze(1) * first).contiguous()
+            widths = (w.unsqueeze(1) * first + (1 - first)).to(torch.uint8).contiguous()
+            preds = (torch.where(inside, self.d_preds[item], zero).unsqueeze(1) * first).to(torch.uint8).contiguous()
+            self._picks.decode_device(self.ctx, self.d_payload, self.payload_size, self.d_offsets, sub_stream.contiguous().view(-1), sub_at.contiguous().view(-1),
+                                      sub_len.contiguous().view(-1), count, self.d_stage, self.max_sub_len, max_pick=S * max_pick, stored=self.d_stored,
+                                      coder=self.coder, stream=stream, dst_cap=self.max_bytes)
+            self._join.join_device(self.ctx, self.d_stage, from_at.view(-1), to_at.view(-1), item_len.view(-1), widths.view(-1), preds.view(-1), count, d_dst,
+                                   self.max_bytes, max_pick=S * max_pick, stream=stream, src_cap=self.max_bytes)
+
+    def verify(self, pick) -> None:
+        """After decode_into whose picks were `pick` (a HOST table, all of them valid) and a synchronisation: the CRC-32 check of a
+        container with checksums over the sub-items in the staging buffer, on the device -> ChecksumError naming the item."""
+        if self.crcs is None:
+            return
+        from . import rcx, typed_items
+        pick = np.asarray(pick, dtype=np.int64)
+        if len(pick) == 0 or int(self.lengths[pick].sum()) == 0:
+            return
+        subs = np.concatenate([np.arange(self.sub_first[k], self.sub_first[k + 1], dtype=np.int64) for k in pick])
+        owner = np.repeat(pick, self.widths[pick].astype(np.int64))
+        soffs = typed_items.sub_offsets(rcx.item_offsets(self.lengths[pick]), self.widths[pick])
+        self.ctx.verify_items_device(self.d_stage, soffs, _cuda(self.crcs[subs]))
+        _sync_checked(self.ctx, "item", lambda k: int(owner[k]))
+
+    def close(self) -> None:
+        if self._own and self.ctx is not None:
+            self.ctx.close()
+        self.ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def open_typed_items(blob, ctx=None) -> OpenTypedItems:
+    """Any RCXJ container -- version 1 or 2, any widths and predictors, stored sub-items, with or without checksums -- parsed
+    once and put on the device -> OpenTypedItems, whose decode_into takes picks, destinations and their count from device memory,
+    decodes and joins, and can be captured in a graph.  ctx=None: a context of its own, closed by close()."""
+    return OpenTypedItems(parse_typed_items(blob), ctx)
+
+
 # ---- tensors with names, on top of the typed item container ---------------------------------------------------------------
 def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=None, checksum: bool = False, stored=None) -> bytes:
     """named: a dict of names -> numpy arrays or contiguous torch tensors (CPU or GPU) -> an RCXJ container whose directory

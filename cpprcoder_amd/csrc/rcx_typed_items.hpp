@@ -59,6 +59,24 @@ struct RcxTypedTables {
     const u32* scan_len;
     const u8* scan_kind; // width | predictor << 4
     u64 nscan;
+    static constexpr bool PICKS = false; // (no member: the tables a kernel is handed stay as they are)
+};
+
+// The same tables as the planner of rcx_typed_picks.hpp leaves them in device memory: an entry is read at from[k] and
+// written at to[k], and the scan list's length is a word in memory.  The walking kernels take either kind (TB).
+struct RcxTypedPickTables {
+    const RcxTypedClasses* classes;
+    const u64* ufirst;
+    const u64* from; // [nent] byte offset of the entry in src
+    const u64* to;   // [nent] ... and in dst
+    const u32* len;
+    const u32* rowtab;
+    const u64* scan_from;
+    const u64* scan_to;
+    const u32* scan_len;
+    const u8* scan_kind;
+    const u32* nscan; // one word
+    static constexpr bool PICKS = true;
 };
 
 RCX_HD u32 rcx_typed_class(u32 width, u32 pred) { return 3u * (width == 1 ? 0u : width == 2 ? 1u : width == 4 ? 2u : 3u) + pred; }
@@ -292,14 +310,15 @@ __device__ __forceinline__ void rcx_typed_dispatch(u32 c, F f)
 
 // One step of a workgroup in a class of width W: rows row0 .. row0 + K - 1 of rowtab, units base + j * 256 + tid of the class's
 // `total`, all loads first.  GUARD = false: every one of them exists; GUARD = true: the class's last step.
-template <u32 W, bool JOIN, u32 PRED, bool GUARD>
-__device__ __forceinline__ void rcx_typed_step(const u8* __restrict__ src, u8* __restrict__ dst, const RcxTypedTables& t, u64 ubase, u64 base, u64 total,
+template <u32 W, bool JOIN, u32 PRED, bool GUARD, class TB>
+__device__ __forceinline__ void rcx_typed_step(const u8* __restrict__ src, u8* __restrict__ dst, const TB& t, u64 ubase, u64 base, u64 total,
                                                u32 row0, u32 tid)
 {
     constexpr u32 K = RCX_PLANES_U4 / W;
     u32 w[K][4 * W];
     [[maybe_unused]] typename RcxElem<W>::T prev[K];
     u64 at[K], g[K];
+    [[maybe_unused]] u64 out_at[K]; // device-planned tables: where the entry goes, `at` being where it comes from
     u32 m[K], u[K], lo[K], hi[K];
     // Where every row's unit lies, for all K rows before the first load of data, and the K rows' table reads side by side: the
     // memory counter runs down in order, so a table read behind a row's loads would wait for those loads, and a search of
@@ -327,14 +346,20 @@ __device__ __forceinline__ void rcx_typed_step(const u8* __restrict__ src, u8* _
 #pragma unroll
     for (u32 j = 0; j < K; ++j) {
         u[j] = (u32)(g[j] - t.ufirst[lo[j]]);
-        at[j] = t.at[lo[j]];
+        if constexpr (TB::PICKS) {
+            at[j] = t.from[lo[j]];
+            out_at[j] = t.to[lo[j]];
+        } else {
+            at[j] = t.at[lo[j]];
+        }
         m[j] = t.len[lo[j]] / W;
     }
     u64 to[K];
 #pragma unroll
     for (u32 j = 0; j < K; ++j) {
         const u64 elements = at[j] + (u64)u[j] * (16u * W), planes = at[j] + 16ull * u[j]; // plane p: + p * m
-        to[j] = JOIN ? elements : planes;
+        if constexpr (TB::PICKS) to[j] = JOIN ? out_at[j] + (u64)u[j] * (16u * W) : out_at[j] + 16ull * u[j];
+        else to[j] = JOIN ? elements : planes;
         if constexpr (PRED != 0) prev[j] = 0; // the predictor restarts with the item
         if (!GUARD || base + (u64)j * RCX_TYPED_ROW + tid < total) {
 #pragma unroll
@@ -366,14 +391,26 @@ __device__ __forceinline__ void rcx_typed_step(const u8* __restrict__ src, u8* _
 }
 
 // Rest lane r of a class of width W: byte r % 17W of the class's entry r / 17W, if it has one.
-template <u32 W, bool JOIN, u32 PRED>
-__device__ __forceinline__ void rcx_typed_rest(const u8* __restrict__ src, u8* __restrict__ dst, const RcxTypedTables& t, u32 first, u32 count, u64 r)
+template <u32 W, bool JOIN, u32 PRED, class TB>
+__device__ __forceinline__ void rcx_typed_rest(const u8* __restrict__ src, u8* __restrict__ dst, const TB& t, u32 first, u32 count, u64 r)
 {
     constexpr u32 PER = 17u * W;
     const u64 k = r / PER;
     if (k >= count) return;
     const u32 j = (u32)(r - k * PER), len = t.len[first + k], m = len / W;
-    const u64 at = t.at[first + k];
+    u64 at;
+    if constexpr (TB::PICKS) { // (join without a predictor only: the entry lies elsewhere in dst)
+        static_assert(!TB::PICKS || (JOIN && PRED == 0), "device-planned tables are the join's");
+        at = t.from[first + k];
+        const u64 to = t.to[first + k];
+        u32 e, p;
+        const u32 kind = rcx_typed_rest_of<W>(len, j, e, p);
+        if (kind == 1) dst[to + (u64)e * W + p] = src[at + (u64)p * m + e];
+        else if (kind == 2) dst[to + e] = src[at + e];
+        return;
+    } else {
+        at = t.at[first + k];
+    }
     u32 e, p;
     const u32 kind = rcx_typed_rest_of<W>(len, j, e, p);
     if (kind == 1) {
@@ -396,6 +433,7 @@ __device__ __forceinline__ void rcx_typed_rest(const u8* __restrict__ src, u8* _
 // Split (every class), and join of the classes without a predictor.  A fixed grid loops over the steps, then over the
 // blocks of rest lanes; the class of a step or block is found on scalars and branched on once.
 // ===========================================================================
+// (rcx_typed_picks_items_k below repeats these two loops for the device-planned tables: a change here goes there too)
 template <bool JOIN>
 __global__ __launch_bounds__(RCX_PLANES_THREADS) void rcx_typed_items_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedTables t)
 {
@@ -426,10 +464,50 @@ __global__ __launch_bounds__(RCX_PLANES_THREADS) void rcx_typed_items_k(const u8
     }
 }
 
-// One item of the scan list, by one wave: rcx_predict_join_k's walk of one superblock of m = len / W elements at `at`.
-template <u32 W, bool ZIGZAG>
-__device__ __forceinline__ void rcx_typed_scan_item(const u8* __restrict__ src, u8* __restrict__ dst, u64 at, u32 len, u32 lane)
+// The same walk with the tables the device planned (rcx_typed_picks.hpp): join only, the classes without a predictor.  A
+// kernel of its own with the loops written out again, not a shared body: with the loops in a function that both kernels
+// inline, the compiler turned the loop tests of the kernel above round, and that kernel is to stay what it was.
+// (four waves a SIMD, as rcx_typed_items_k<true> has by itself: the second position table costs registers, and at three
+// waves the kernel lost 6 % on large items)
+__global__ __launch_bounds__(RCX_PLANES_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void rcx_typed_picks_items_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedPickTables t)
 {
+    constexpr bool JOIN = true;
+    const RcxTypedClasses* const cl = t.classes;
+    const u32 tid = threadIdx.x;
+    const u64 steps = cl->step_end[RCX_TYPED_CLASSES - 1];
+    for (u64 s = blockIdx.x; s < steps; s += gridDim.x) {
+        const u32 c = rcx_typed_class_of(cl->step_end, s);
+        const u64 local = s - (c ? cl->step_end[c - 1] : 0);
+        const u64 ubase = cl->ubase[c], total = cl->ubase[c + 1] - ubase;
+        const u32 rows = cl->row_first[c];
+        rcx_typed_dispatch<JOIN>(c, [&](auto w_, auto p_) {
+            constexpr u32 W = decltype(w_)::value, PRED = decltype(p_)::value, K = RCX_PLANES_U4 / W, STEP = K * RCX_TYPED_ROW;
+            const u64 base = local * STEP;
+            const u32 row0 = rows + (u32)(local * K);
+            if (base + STEP <= total) rcx_typed_step<W, JOIN, PRED, false>(src, dst, t, ubase, base, total, row0, tid);
+            else rcx_typed_step<W, JOIN, PRED, true>(src, dst, t, ubase, base, total, row0, tid);
+        });
+    }
+    const u64 blocks = cl->rest_end[RCX_TYPED_CLASSES - 1];
+    for (u64 b = blockIdx.x; b < blocks; b += gridDim.x) {
+        const u32 c = rcx_typed_class_of(cl->rest_end, b);
+        const u64 r = (b - (c ? cl->rest_end[c - 1] : 0)) * RCX_TYPED_ROW + tid;
+        const u32 first = cl->ent_first[c], count = cl->ent_first[c + 1] - first;
+        rcx_typed_dispatch<JOIN>(c, [&](auto w_, auto p_) {
+            rcx_typed_rest<decltype(w_)::value, JOIN, decltype(p_)::value>(src, dst, t, first, count, r);
+        });
+    }
+}
+
+
+// One item of the scan list, by one wave: rcx_predict_join_k's walk of one superblock of m = len / W elements at `at`.
+// APART (the tables the device planned): it is written at `out` of dst, not at `at`.
+template <u32 W, bool ZIGZAG, bool APART = false>
+__device__ __forceinline__ void rcx_typed_scan_item(const u8* __restrict__ src, u8* __restrict__ dst, u64 at, u32 len, u32 lane, [[maybe_unused]] u64 out = 0)
+{
+    u64 to;
+    if constexpr (APART) to = out;
+    else to = at;
     typedef typename RcxElem<W>::T T;
     constexpr u32 ROW = RCX_PREDICT_TILE_UNITS * 16u;
     const u32 m = len / W;
@@ -442,7 +520,7 @@ __device__ __forceinline__ void rcx_typed_scan_item(const u8* __restrict__ src, 
     if (rows) rcx_predict_load_row<W>(src, at, m, 0, lane, cur);
     u32 row = 0;
     const u8* planes = src + at + 16ull * lane; // of the lane's unit in row 0
-    u8* elements = dst + at + (u64)lane * (16u * W);
+    u8* elements = dst + to + (u64)lane * (16u * W);
     for (; row + 2 < full; row += 2) { // two tiles a turn while the two rows behind them are whole
         rcx_predict_load_unit<W>(planes + (u64)(row + 1) * ROW, m, nxt);
         rcx_predict_join_tile<W, ZIGZAG>(cur, elements + (u64)row * (ROW * W), true, carry, lane);
@@ -452,7 +530,7 @@ __device__ __forceinline__ void rcx_typed_scan_item(const u8* __restrict__ src, 
     for (; row < rows; ++row) { // the last rows, with the tests: the next row is loaded first
         if (row + 1 < rows) rcx_predict_load_row<W>(src, at, m, row + 1, lane, nxt);
         const u32 u = row * RCX_PREDICT_TILE_UNITS + lane;
-        rcx_predict_join_tile<W, ZIGZAG>(cur, dst + at + (u64)u * (16u * W), u < units, carry, lane);
+        rcx_predict_join_tile<W, ZIGZAG>(cur, dst + to + (u64)u * (16u * W), u < units, carry, lane);
 #pragma unroll
         for (u32 i = 0; i < 4 * W; ++i) cur[i] = nxt[i];
     }
@@ -464,15 +542,16 @@ __device__ __forceinline__ void rcx_typed_scan_item(const u8* __restrict__ src, 
             for (u32 p = 0; p < W; ++p) z |= (T)src[at + (u64)p * m + e0 + lane] << (8u * p);
         }
         const T upto = rcx_wave_scan<T>(ZIGZAG ? rcx_unzigzag<W>(z) : z, lane);
-        if (lane < left) rcx_store_elem<W>(dst + at + (u64)(e0 + lane) * W, (T)(upto + carry) & rcx_elem_mask<W>());
+        if (lane < left) rcx_store_elem<W>(dst + to + (u64)(e0 + lane) * W, (T)(upto + carry) & rcx_elem_mask<W>());
     }
-    if (lane < len - m * W) dst[at + (u64)m * W + lane] = src[at + (u64)m * W + lane]; // the tail
+    if (lane < len - m * W) dst[to + (u64)m * W + lane] = src[at + (u64)m * W + lane]; // the tail
 }
 
 // ===========================================================================
 // Join with a predictor: a workgroup is one wave, a wave owns whole items of the scan list (longest first) and walks
 // each tile by tile.  Width and predictor are the item's, the same in all 64 lanes: read, made scalar, branched on.
 // ===========================================================================
+// (rcx_typed_picks_scan_k below repeats the loop and the switch for the device-planned scan list)
 __global__ __launch_bounds__(RCX_PREDICT_TILE_UNITS) void rcx_typed_items_scan_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedTables t)
 {
     const u32 lane = threadIdx.x;
@@ -487,6 +566,27 @@ __global__ __launch_bounds__(RCX_PREDICT_TILE_UNITS) void rcx_typed_items_scan_k
         case 4u | 32u: rcx_typed_scan_item<4, true>(src, dst, at, len, lane); break;
         case 8u | 16u: rcx_typed_scan_item<8, false>(src, dst, at, len, lane); break;
         default: rcx_typed_scan_item<8, true>(src, dst, at, len, lane); break;
+        }
+    }
+}
+
+// ... over the scan list the device planned: as many waves as the launch has, the list's length read from memory, an item
+// read at scan_from and written at scan_to
+__global__ __launch_bounds__(RCX_PREDICT_TILE_UNITS) void rcx_typed_picks_scan_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedPickTables t)
+{
+    const u32 lane = threadIdx.x;
+    const u64 nscan = t.nscan[0];
+    for (u64 i = blockIdx.x; i < nscan; i += gridDim.x) {
+        const u64 at = t.scan_from[i], to = t.scan_to[i];
+        const u32 len = t.scan_len[i];
+        const u32 kind = (u32)__builtin_amdgcn_readfirstlane((int)t.scan_kind[i]);
+        switch (kind) {
+        case 2u | 16u: rcx_typed_scan_item<2, false, true>(src, dst, at, len, lane, to); break;
+        case 2u | 32u: rcx_typed_scan_item<2, true, true>(src, dst, at, len, lane, to); break;
+        case 4u | 16u: rcx_typed_scan_item<4, false, true>(src, dst, at, len, lane, to); break;
+        case 4u | 32u: rcx_typed_scan_item<4, true, true>(src, dst, at, len, lane, to); break;
+        case 8u | 16u: rcx_typed_scan_item<8, false, true>(src, dst, at, len, lane, to); break;
+        default: rcx_typed_scan_item<8, true, true>(src, dst, at, len, lane, to); break;
         }
     }
 }

@@ -34,7 +34,8 @@
  * src_offsets (nitems + 1 entries), widths and preds (nitems bytes each; preds == NULL: no item has a predictor) are HOST
  * tables.  The call plans on the host -- items by (width, predictor), their units of 16 elements numbered through, for
  * join the items with a predictor longest first -- and sends its tables inside the call, into the context's scratch
- * (rcx_ctx_scratch_bytes counts them).  SO THE CALLS CANNOT BE CAPTURED INTO A GRAPH, as the item calls cannot; they
+ * (rcx_ctx_scratch_bytes counts them).  SO THE CALLS CANNOT BE CAPTURED INTO A GRAPH, as the item calls cannot (the join
+ * that can is rcx_typed_join_picks_device of rcx_typed_picks.h, which reads its tables on the device); they
  * enqueue on the given stream and return.  A context serves one call at a time, on one stream at a time.  The number of
  * launches does not depend on nitems: one for split, at most two for join.
  * They read exactly [d_src + src_offsets[0], d_src + src_offsets[nitems]) and write exactly the same range of d_dst, at

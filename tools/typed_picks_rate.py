@@ -1,0 +1,283 @@
+#!/usr/bin/env python3
+"""Rates of rcx_typed_join_picks_device (include/rcx_typed_picks.h) next to the host-planned rcx_typed_items_join_device, by the
+method of tools/picks_rate.py: warm-up, 7 passes, everything that is compared alternated, median and min-max.  DESIGN.md
+section 21 quotes profiles/r20_typed_picks_rate.jsonl.
+
+    python tools/typed_picks_rate.py --baseline-library PATH [--out profiles/r20_typed_picks_rate.jsonl] [--repeats 7] [--parts A,B,C,D]
+
+  A  the ragged batch of tools/typed_items_rate.py part B, joined: 200 000 items of 0 .. 4096 bytes, widths 2, 4, 8, all
+     predictors.  Wall time of a call (host clock from the call to the return of a device synchronise) and GPU time (device
+     events around it), both calls.  Bar: the device-planned call's wall median is no more than the host-planned call's median
+     plus that call's own min-max spread in this run.
+  B  part A of the same tool: the GiB as superblocks of w x 64 KiB, widths 2, 4, 8, without a predictor and with delta.  The
+     walking launches alone (the context's RCX_T_DECODE events around them) against the host-planned join's kernels (the call
+     timed behind queued device copies that cover its host plan), and the planner (RCX_T_SCAN) on its own line.  Bar per width
+     and predictor: the walking median is no more than the host-planned kernels' median plus their min-max spread.
+  C  max_pick = 200 000 with *d_count = 100, 1000, 10 000, 200 000 of A's entries: GPU time of the call.  Report only.
+  D  container.open_typed_items(...).decode_into on A's items packed as RCXJ (adaptive coder), eager and as a graph replay,
+     beside unpack_typed_items' device path for the same picks without the download (container._unpack_typed_items_device: host
+     plan, uploads, decode, join).  That path runs this build's library -- the container module binds one librcx a process --
+     whose host-planned kernels tools/diag/kernel_diff.py shows unchanged from the parent.  Report only.
+
+--baseline-library: a librcx.so of the parent commit: the host-planned side of parts A and B is that library, never this build.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from cpprcoder_amd import container, predict, rcx, typed_items, typed_picks, workloads  # noqa: E402
+
+WIDTHS = (2, 4, 8)
+BLOCK = 65536
+
+
+def dev64(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint64)).view(np.int64)).cuda()
+
+
+def dev8(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint8))).cuda()
+
+
+def spread(ms):
+    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4), "passes": len(ms)}
+
+
+def alternated(fns, repeats, warmup=2, after=None, before=None):
+    """Several calls measured in turn -> {name: {"gpu_ms": [...], "wall_ms": [...], "after": [...]}}: device events around the
+    call, and the host clock from the call to the return of a device synchronise; before(name) runs in front of the first
+    event (what it enqueues is outside the events and keeps the device busy while the call's host side runs), after(name) is
+    called behind each."""
+    for _ in range(warmup):
+        for k, fn in fns.items():
+            fn()
+            torch.cuda.synchronize()
+            if after:
+                after(k)
+    out = {k: {"gpu_ms": [], "wall_ms": [], "after": []} for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            if before:
+                before(k)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            out[k]["wall_ms"].append((time.perf_counter() - t0) * 1e3)
+            out[k]["gpu_ms"].append(a.elapsed_time(b))
+            if after:
+                out[k]["after"].append(after(k))
+    return out
+
+
+class Baseline:
+    """rcx_typed_items_join_device of another build of the library (plain ctypes), on a context of its own."""
+
+    def __init__(self, path):
+        self.L = C.CDLL(path)
+        vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int
+        self.L.rcx_ctx_create.argtypes = [i32, C.POINTER(vp)]
+        self.L.rcx_typed_items_join_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
+        self.L.rcx_ctx_destroy.argtypes = [vp]
+        self.h = vp()
+        assert self.L.rcx_ctx_create(0, C.byref(self.h)) == 0
+
+    def join(self, src, offs, widths, preds, dst):
+        st = self.L.rcx_typed_items_join_device(self.h, src.data_ptr(), offs.ctypes.data, widths.ctypes.data, preds.ctypes.data, len(widths), dst.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream)
+        assert st == 0
+
+
+class Ragged:
+    """Part A's batch: 200 000 items, split once by the host-planned call."""
+
+    def __init__(self, ctx, count=200_000):
+        rs = np.random.RandomState(13)
+        self.count = count
+        self.lengths = rs.randint(0, 4097, count).astype(np.uint64)
+        self.widths = np.array(WIDTHS, np.uint8)[rs.randint(0, 3, count)]
+        self.preds = rs.randint(0, 3, count).astype(np.uint8)
+        self.offs = rcx.item_offsets(self.lengths)
+        self.total = int(self.offs[-1])
+        self.ctx = ctx
+        self.items = torch.from_numpy(workloads.uniform(self.total, 12345)).cuda()
+        self.split = torch.zeros_like(self.items)
+        self.out = torch.zeros_like(self.items)
+        typed_items.split_device(ctx, self.items, self.offs, self.widths, self.preds, self.split)
+        ctx.sync_status()
+        self.d_at, self.d_len = dev64(self.offs[:-1]), dev64(self.lengths)
+        self.d_w, self.d_p, self.d_count = dev8(self.widths), dev8(self.preds), dev64([count])
+        typed_picks.reserve(ctx, count, self.total)
+
+    def device_planned(self):
+        typed_picks.join_device(self.ctx, self.split, self.d_at, self.d_at, self.d_len, self.d_w, self.d_p, self.d_count, self.out, self.total)
+
+    def check(self, upto=None):
+        self.ctx.sync_status()
+        n = self.total if upto is None else int(self.offs[upto])
+        assert torch.equal(self.out[:n], self.items[:n]), "the joined entries are not the items"
+
+
+def part_a(w, args, emit, base):
+    t = alternated({"device_planned": w.device_planned, "host_planned": lambda: base.join(w.split, w.offs, w.widths, w.preds, w.out)}, args.repeats)
+    w.check()
+    row = {"part": "A", "items": w.count, "bytes": w.total, "host_planned_by": "the parent commit's library"}
+    for k, v in t.items():
+        row[k] = {"wall_ms": spread(v["wall_ms"]), "gpu_ms": spread(v["gpu_ms"])}
+    host = row["host_planned"]["wall_ms"]
+    row["bar_ms"] = round(host["median"] + host["max"] - host["min"], 4)
+    row["pass"] = row["device_planned"]["wall_ms"]["median"] <= row["bar_ms"]
+    row["pass_mark"] = "device-planned call wall median <= host-planned call median + the host-planned min-max spread of this run"
+    emit(row)
+
+
+def part_b(ctx, args, emit, base):
+    n = 1 << 30
+    src, mid, out, busy_a, busy_b = (torch.zeros(n, dtype=torch.uint8, device="cuda") for _ in range(5))
+    src.copy_(torch.from_numpy(workloads.uniform(n, 12345)).cuda())
+    ctx.set_timing(True)
+    for w in WIDTHS:
+        sb = w * BLOCK
+        lengths = np.array([sb] * (n // sb) + ([n % sb] if n % sb else []), np.uint64)
+        offs, widths = rcx.item_offsets(lengths), np.full(len(lengths), w, np.uint8)
+        d_at, d_len, d_w, d_count = dev64(offs[:-1]), dev64(lengths), dev8(widths), dev64([len(lengths)])
+        typed_picks.reserve(ctx, len(lengths), n)
+        for name, pred in (("none", predict.NONE), ("delta", predict.DELTA)):
+            preds = np.full(len(lengths), pred, np.uint8)
+            d_p = dev8(preds)
+            typed_items.split_device(ctx, src, offs, widths, preds, mid)
+            ctx.sync_status()
+            ctx.get_timing(reset=True)
+
+            def cover(k):  # queued copies in front of the host-planned call: its kernels wait behind them while the host plans
+                if k == "host_planned":
+                    for _ in range(4):
+                        busy_b.copy_(busy_a)
+
+            def host_kernels():  # the events go behind the copies: record, call, record
+                base.join(mid, offs, widths, preds, out)
+
+            fns = {"device_planned": lambda: typed_picks.join_device(ctx, mid, d_at, d_at, d_len, d_w, d_p if pred else None, d_count, out, n),
+                   "host_planned": host_kernels}
+            t = alternated(fns, args.repeats, before=cover, after=lambda k: {s: v["ms"] for s, v in ctx.get_timing(reset=True).items() if s in ("scan", "decode")})
+            ctx.sync_status()
+            assert torch.equal(out, src), (w, name)
+            walk = spread([a["decode"] for a in t["device_planned"]["after"]])
+            planner = spread([a["scan"] for a in t["device_planned"]["after"]])
+            host = spread(t["host_planned"]["gpu_ms"])
+            bar = host["median"] + host["max"] - host["min"]
+            emit({"part": "B", "width": w, "predictor": name, "items": len(lengths), "bytes": n,
+                  "join_kernels_ms": {"device_planned_walk": walk, "host_planned_kernels_behind_copies": host}, "planner_ms": planner,
+                  "device_planned_call_gpu_ms": spread(t["device_planned"]["gpu_ms"]), "walk_gbps": round(n / walk["median"] / 1e6, 1),
+                  "bar_ms": round(bar, 4), "pass": walk["median"] <= bar,
+                  "pass_mark": "walking launches' median <= host-planned join kernels' median + their min-max spread of this run",
+                  "note": "the host-planned figure is device events around the call behind 4 queued GiB copies, so it holds the copies' tail and the upload"})
+    ctx.set_timing(False)
+
+
+def part_c(w, args, emit):
+    row = {"part": "C", "max_pick": w.count, "spread_live_entries": "not built", "what": "GPU time of one call (device events), the first `count` of part A's entries meant"}
+    for count in (100, 1000, 10_000, w.count):
+        w.d_count.fill_(count)
+        w.out.zero_()
+        t = alternated({"call": w.device_planned}, args.repeats)
+        w.check(upto=count)
+        row[f"count_{count}"] = {"gpu_ms": spread(t["call"]["gpu_ms"]), "wall_ms": spread(t["call"]["wall_ms"])}
+    w.d_count.fill_(w.count)
+    emit(row)
+
+
+def part_d(w, args, emit):
+    ctx = w.ctx
+    host = w.items.cpu().numpy()
+    items = [host[int(w.offs[i]): int(w.offs[i + 1])] for i in range(w.count)]
+    blob = container.pack_typed_items(items, widths=[int(x) for x in w.widths], predict=[(None, "delta", "zigzag")[int(p)] for p in w.preds], ctx=ctx)
+    rs = np.random.RandomState(14)
+    pick = rs.permutation(w.count)
+    plen = w.lengths[pick]
+    doffs = rcx.item_offsets(plen)
+    box = container.open_typed_items(blob, ctx=ctx)
+    box.reserve(w.count, w.total)
+    d_pick, d_at, d_count = dev64(pick), dev64(doffs[:-1]), dev64([w.count])
+    out = torch.zeros(w.total, dtype=torch.uint8, device="cuda")
+    eager = lambda: box.decode_into(d_pick, d_at, d_count, out)  # noqa: E731
+    eager()
+    ctx.sync_status()
+    want = torch.cat([w.items[int(w.offs[i]): int(w.offs[i + 1])] for i in pick[:2000]])
+    assert torch.equal(out[: want.numel()], want)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        eager()
+    c = container.parse_typed_items(blob)
+    fns = {"graph_replay": g.replay, "eager": eager}
+    fns["unpack_typed_items_device_path_this_build"] = lambda: container._unpack_typed_items_device(ctx, c, pick, False)
+    t = alternated(fns, args.repeats)
+    ctx.sync_status()
+    assert torch.equal(out[: want.numel()], want)
+    row = {"part": "D", "items": w.count, "bytes": w.total, "container_bytes": len(blob), "coder": "adaptive",
+           "note": "unpack_typed_items' device path (host plan, uploads, decode, join; no download) runs this build's library: its kernels are the parent's "
+                   "(tools/diag/kernel_diff.py), one process holds one librcx"}
+    for k, v in t.items():
+        row[k] = {"wall_ms": spread(v["wall_ms"]), "gpu_ms": spread(v["gpu_ms"])}
+    emit(row)
+    box.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20_typed_picks_rate.jsonl"))
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--parts", default="A,B,C,D")
+    ap.add_argument("--baseline-library", required=True, help="a librcx.so of the parent commit: the host-planned side")
+    ap.add_argument("--build-note", default=None, help="goes into every row as `build`: which build of the library a run measured")
+    args = ap.parse_args()
+    args.parts = args.parts.split(",")
+    if args.repeats < 5:
+        ap.error("at least 5 passes")
+    rows = []
+
+    def emit(row):
+        if args.build_note:
+            row["build"] = args.build_note
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        with open(args.out, "w") as f:  # (kept up to date: a run that is cut short leaves what it had)
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+    base = Baseline(args.baseline_library)
+    ctx = rcx.Context(0)
+    if {"A", "C", "D"} & set(args.parts):
+        w = Ragged(ctx)
+        if "A" in args.parts:
+            part_a(w, args, emit, base)
+        if "C" in args.parts:
+            part_c(w, args, emit)
+        if "D" in args.parts:
+            part_d(w, args, emit)
+        del w
+    if "B" in args.parts:
+        part_b(ctx, args, emit, base)
+    ctx.close()
+    failed = [r for r in rows if r.get("pass") is False]
+    if failed:
+        print(f"{len(failed)} pass mark(s) missed", file=sys.stderr)
+        raise SystemExit(1)
+
+
+if __name__ == "__main__":
+    main()
