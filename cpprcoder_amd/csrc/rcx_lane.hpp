@@ -73,6 +73,7 @@ struct alignas(16) DivEntry {
 #if defined(RCX_HOST_SIM)
 RCX_DEV u32 rcx_clz(u32 x) { return (u32)__builtin_clz(x); }
 RCX_DEV u32 rcx_mul24(u32 a, u32 b) { return (a & 0xFFFFFFu) * (b & 0xFFFFFFu); }
+RCX_DEV u32 rcx_mulhi(u32 a, u32 b) { return (u32)(((u64)a * b) >> 32); }
 RCX_DEV u32 rcx_perm(u32 hi, u32 lo, u32 sel)
 {
     u64 v = ((u64)hi << 32) | lo;
@@ -98,6 +99,7 @@ extern uint64_t rcx_sim_counters[4];
 #define RCX_SIM_COUNT(i, n) ((void)0)
 RCX_DEV u32 rcx_clz(u32 x) { return (u32)__builtin_clz(x); }
 RCX_DEV u32 rcx_mul24(u32 a, u32 b) { return __umul24(a, b); }
+RCX_DEV u32 rcx_mulhi(u32 a, u32 b) { return __umulhi(a, b); }
 RCX_DEV u32 rcx_perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 RCX_DEV u32 rcx_bswap(u32 x) { return __builtin_bswap32(x); }
 RCX_DEV void rcx_lds_inc(u32* p) { (void)__hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
@@ -367,16 +369,20 @@ struct EncLane {
         range <<= k8;
         return (moved & 0xFFFFFF00u) | k8 | carry; // k8 is 0, 8, 16 or 24: bits 3 and 4
     }
-    // the same with the divisor's fields passed separately (the addend as the 64-bit pair the multiply-add takes)
-    RCX_DEV u32 arith_q(u32 cum, u32 f, u32 mul, u32 shift, u64 add)
+    // The same with the divisor as the quad decoder's table has it (rcx_ctx.hpp rcx_divtab_k): multiplier, increment (0 or 1)
+    // and the shift, which 16 symbols share.  Here `range` is the range as :707 leaves it, NOT renormalised, and `k8` the
+    // shift that renormalises it (0 in front of the first symbol): the shift rides in the add of the increment (one
+    // v_lshl_add_u32, as in RCX_QUAD_DEC_SYMBOL).  The add does not wrap: a range is f * t with f <= total - 255 (every
+    // other count is at least 1) and t = floor(R / total) >= 1, so it is at most R - 255 where it is not shifted, and its
+    // low eight bits are 0 where it is; the initial range is 0xFFFFFF00, and symbol 0's total, 256, has the increment 1.
+    RCX_DEV u32 arith_i(u32 cum, u32 f, u32 mul, u32 inc, u32 sh, u32& k8)
     {
-        const u32 t = (u32)(((u64)range * mul + add) >> 32) >> (shift & 31u); // cpprcoder.h:703
-        const u32 moved = low + rcx_mul24(cum, t);                            // :706
+        const u32 t = rcx_mulhi((range << k8) + inc, mul) >> sh; // cpprcoder.h:703
+        const u32 moved = low + rcx_mul24(cum, t);               // :706
         const u32 carry = moved < low ? 1u : 0u;
-        range = rcx_mul24(f, t);                                              // :707
-        const u32 k8 = rcx_clz(range) & 0x18u;
+        range = rcx_mul24(f, t);                                 // :707
+        k8 = rcx_clz(range) & 0x18u;
         low = moved << k8;
-        range <<= k8;
         return (moved & 0xFFFFFF00u) | k8 | carry; // k8 is 0, 8, 16 or 24: bits 3 and 4
     }
     RCX_DEV void emit(u32 rec)

@@ -123,7 +123,7 @@ int encode_launches(rcx_ctx* c, int coder, const void* d_src, u64 n, u32 block, 
     } else if (variant == 3) {
         const u32 lanes = packed ? RCX_LANES : encode_lanes(c, nblocks);
         hipLaunchKernelGGL(rcx_enc_mc5_k<G>, dim3(grid_for(nblocks, lanes)), dim3(RCX_MC5_THREADS), 0, s, src, n, block, nblocks, v.slots, slot,
-                           v.sizes, c->divtab(), c->status, v.redo, lanes, g);
+                           v.sizes, c->divq(), c->status, v.redo, lanes, g);
         // Blocks in which a carry ran through more output bytes than the five-wave kernel keeps in LDS were
         // marked, not finished: the one-wave kernel encodes them again.  Nothing is marked on ordinary data
         // and every wave of this launch returns at once.

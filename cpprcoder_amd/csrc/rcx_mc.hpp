@@ -24,11 +24,6 @@ __device__ __forceinline__ void rcx_lds_barrier()
 static __device__ unsigned long long rcx_stamp_out[16];
 #define rcx_stamp_wait stamp_wait_
 #endif
-// divisor entry as the encoder stages it: the 64-bit addend is read as a register pair
-struct alignas(16) DivQ {
-    u32 mul, st; // st = total << 5 | shift
-    u64 add;
-};
 
 // ===========================================================================
 // Encode, pass 1, five-wave split ("MC5"): as rcx_enc_mc_k, with the coder itself cut in two
@@ -55,7 +50,14 @@ struct alignas(16) DivQ {
 #define RCX_DRAIN_WAVE 5
 #define RCX_L3_WAVE 6
 #define RCX_MC5_THREADS 448
-#define RCX_MC5_ROLE(HW) ((0x6541230u >> (4u * (HW))) & 15u) /* one hex digit per hardware wave, wave 0 lowest */
+// (Both are switches for measuring other pairings, DESIGN.md 3.2: with seven waves a SIMD has two at the most.)
+#if !defined(RCX_MC5_ROLES)
+#define RCX_MC5_ROLES 0x6541230u /* one hex digit per hardware wave, wave 0 lowest */
+#endif
+#if !defined(RCX_MC5_PRIO)
+#define RCX_MC5_PRIO 0x10u /* the roles that run at s_setprio 1 (rcx_mc5_pipeline), one bit each: level 1 */
+#endif
+#define RCX_MC5_ROLE(HW) (((u32)RCX_MC5_ROLES >> (4u * (HW))) & 15u)
 // The ring between the model waves and the arithmetic wave: four dwords per symbol and lane.  Kept as 16 contiguous
 // bytes per lane (one ds_read_b128 for the arithmetic wave; the model waves' 4-byte stores hit each bank four times)
 // or, RCX_RING_PLANAR=1, as four dword planes (conflict-free stores, two ds_read2st64_b32).
@@ -82,7 +84,8 @@ struct alignas(16) DivQ {
 // The level-3 wave's sums: a fifth value per symbol and lane, in a dword plane of its own beside the ring (the ring's record
 // stays the 16 bytes per lane that the arithmetic wave reads at once), double-buffered like it, behind the output rings.
 #define RCX_MC5_RING3_DW (2 * RCX_MC_CHUNK * RCX_LANES)
-#define RCX_MC5_LDS_U4 (RCX_MC_LDS_U4 + RCX_MC5_RING2_DW / 4 + RCX_LANES / 4 + RCX_MC5_OUT_DW / 4 + RCX_MC5_RING3_DW / 4)
+#define RCX_MC5_TREE_U4 (RCX_GROUPS * RCX_LANES) /* the model's groups; no staged divisors behind them (RCX_LDS_U4 has 64) */
+#define RCX_MC5_LDS_U4 (RCX_MC5_TREE_U4 + RCX_MC_RING_U4 + RCX_MC5_RING2_DW / 4 + RCX_LANES / 4 + RCX_MC5_OUT_DW / 4 + RCX_MC5_RING3_DW / 4)
 
 struct __attribute__((packed, aligned(4))) RcxU4Unaligned {
     u32 x, y, z, w;
@@ -337,57 +340,78 @@ struct McOutput {
 
 template <bool FULL>
 __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u32 nchunks, const u8* in,
-                                                 const DivEntry* __restrict__ divtab, const Tree& tree, DivEntry* stage,
-                                                 u32* ring, u32* ring2, u32* ring3, EncLane& enc, DivEntry& ahead, StagedWriter& wr,
+                                                 const u32* __restrict__ divq, const Tree& tree,
+                                                 u32* ring, u32* ring2, u32* ring3, EncLane& enc, StagedWriter& wr,
                                                  u32* out_pos, u32& drained, u8* payload, u32 cap, bool live)
 {
     // wave roles: 0 arithmetic, 1 writer, 2 model level 2, 3 model leaf level, 4 model level 1, 5 drain, 6 model level 3
+    // (a pipeline step ends at the workgroup's barrier, in whichever of the two loops below a wave runs)
 #if defined(RCX_STAMP)
     unsigned long long stamp_wait_ = 0;
     const unsigned long long stamp_begin_ = __builtin_amdgcn_s_memtime();
+#define RCX_MC5_STEP_ENDS()                                                \
+    {                                                                      \
+        const unsigned long long t0_ = __builtin_amdgcn_s_memtime();       \
+        rcx_lds_barrier();                                                 \
+        stamp_wait_ += __builtin_amdgcn_s_memtime() - t0_;                 \
+    }
+#define RCX_MC5_STAMPS_OUT()                                               \
+    if (blockIdx.x == 7 && lane == 0) {                                    \
+        rcx_stamp_out[wave * 2] = __builtin_amdgcn_s_memtime() - stamp_begin_; \
+        rcx_stamp_out[wave * 2 + 1] = stamp_wait_;                         \
+    }
+#else
+#define RCX_MC5_STEP_ENDS() rcx_lds_barrier()
+#define RCX_MC5_STAMPS_OUT()
 #endif
     // Two waves of a SIMD share its issue slots by priority, then age.  The level-1 wave is the younger one beside the
     // arithmetic wave and was the kernel's pole (busy 174 of 177 cycles a symbol); the arithmetic wave has 45 to give.
     // (Measured on full 64 KiB blocks, 64 to a workgroup; set for the guarded pipeline and single streams as well, where
     // its effect is not measured.  It changes the order in which instructions issue, never a result.)
-    if (wave == 4) __builtin_amdgcn_s_setprio(1);
-    U4 piece_ahead;
-    piece_ahead.x = piece_ahead.y = piece_ahead.z = piece_ahead.w = 0;
-    if (FULL && wave >= 2 && wave != RCX_DRAIN_WAVE && nchunks > 0) piece_ahead = *reinterpret_cast<const U4*>(in);
-    u32 l3a = 64, l3b = 128, l3c = 192; // level-3 wave: its sums (cpprcoder.h:1094-1132: every count 1)
-    for (u32 k = 0; k <= nchunks + 1; ++k) {
-        if (wave == 0) {
+    if ((RCX_MC5_PRIO >> wave) & 1u) __builtin_amdgcn_s_setprio(1);
+    // The arithmetic wave's divisors, in registers as the quad decoder has them (rcx_quad.hpp, RCX_QUAD_DIVQ_DW): the 16
+    // multipliers and 16 increments of a chunk are eight 16-byte registers that every lane loads alike, each loaded again
+    // -- with the next chunk's quarter -- right behind its quarter's last symbol, and waited for once, at the top of the
+    // next chunk (the wave has no other global traffic, and a barrier lies in between).  Vector loads through a zero the
+    // compiler cannot see through: scalar ones would share lgkmcnt with the wave's LDS reads.  A short block's last chunk
+    // loads the group behind it: the table has 2 * RCX_STAGE spare entries (rcx_ctx.hpp ensure_divtab).
+    // The wave has a loop of its own, so that these 32 registers are not carried through the other waves' steps (carried
+    // through, they are split around the model waves' 64 registers of groups, and the chain waits for the copies).
+    if (wave == 0) {
+        U4 dm[4], di[4];
+        u32 prev_k8 = 0; // the renormalising shift of the symbol before (EncLane::arith_i)
+        u32 vz;
+        asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
+        const u32* dq = divq + vz;
+#pragma unroll
+        for (u32 q = 0; q < 4; ++q) {
+            dm[q] = reinterpret_cast<const U4*>(dq)[q];
+            di[q] = reinterpret_cast<const U4*>(dq + 16)[q];
+        }
+        RCX_MC5_STEP_ENDS(); // (step 0: the model waves' first chunk)
+        for (u32 k = 1; k <= nchunks; ++k) {
             // ---- arithmetic: chunk k-1, records into ring2[(k-1)&1] ----
-            if (k >= 1 && k <= nchunks) {
+            {
                 const u32 i0 = (k - 1) * RCX_MC_CHUNK;
-                if ((i0 % RCX_STAGE) == 0) {
-                    // staged with the 64-bit addend of the multiply-add as a register pair (see DivQ)
-                    DivQ q;
-                    q.mul = ahead.mul;
-                    q.st = ahead.shift;
-                    q.add = ahead.add;
-                    reinterpret_cast<DivQ*>(stage)[lane] = q;
-                    ahead = divtab[i0 + RCX_STAGE + lane];
-                }
+                // the chunk's divisors: asked for a chunk ago, waited for here, once, by a statement that reads them
+                asm volatile("" ::"v"(dm[0].x), "v"(di[0].x), "v"(dm[1].x), "v"(di[1].x), "v"(dm[2].x), "v"(di[2].x), "v"(dm[3].x), "v"(di[3].x));
+                // their shift: floor(log2(total)) is one value for the chunk's 16 totals (the powers of two from 256 up are
+                // multiples of 16); wave-uniform, a scalar
+                const u32 sh = 31u - rcx_clz(256u + i0);
+                const u32* dq_next = dq + (size_t)k * RCX_QUAD_DIVQ_DW; // chunk k - 1 is group k - 1 of the table
                 // the model waves' answers: field f of symbol s of lane l at dword RCX_RING_AT(s, f) + RCX_RING_LANE * l
                 const u32* rs = ring + ((k - 1) & 1u) * (4 * RCX_MC_CHUNK * RCX_LANES) + RCX_RING_LANE * lane;
                 const u32* rs3 = ring3 + ((k - 1) & 1u) * (RCX_MC_CHUNK * RCX_LANES) + lane; // (level 3: two symbols per ds_read2st64_b32)
                 u32* ws2 = ring2 + ((k - 1) & 1u) * (RCX_MC_CHUNK * RCX_LANES) + lane;
-                // the chunk's divisors through one vector base register and immediate offsets (a wave-uniform
-                // address would be rebuilt in a scalar register and moved over for every read)
-                u32 st_lds = (u32)reinterpret_cast<uintptr_t>(stage + (i0 % RCX_STAGE));
-                asm volatile("" : "+v"(st_lds));
-                const RcxLdsDivQ* st = reinterpret_cast<const RcxLdsDivQ*>(st_lds);
                 U4 eq[RCX_MC_CHUNK];
                 u32 c3q[RCX_MC_CHUNK];
-                RcxDivQv kq[RCX_MC_CHUNK];
                 u32 rec_even = 0;
+#define RCX_A_U4_AT(V, C) ((C) == 0 ? (V).x : (C) == 1 ? (V).y : (C) == 2 ? (V).z : (V).w)
 #define RCX_A_ISSUE(T)                                                                                              \
     {                                                                                                               \
         eq[T].x = rs[RCX_RING_AT((T), 0)], eq[T].y = rs[RCX_RING_AT((T), 1)], eq[T].z = rs[RCX_RING_AT((T), 2)];    \
         eq[T].w = rs[RCX_RING_AT((T), 3)];                                                                          \
         if (((T)&1u) == 0) c3q[T] = rs3[(T)*RCX_LANES], c3q[(T) + 1] = rs3[((T) + 1) * RCX_LANES];                   \
-        kq[T] = st[T];                                                                                              \
     }
 #pragma unroll
                 for (u32 t = 0; t < RCX_ARITH_AHEAD; ++t) RCX_A_ISSUE(t);
@@ -395,9 +419,17 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                 for (u32 s = 0; s < RCX_MC_CHUNK; ++s) {
                     if (s + RCX_ARITH_AHEAD < RCX_MC_CHUNK) RCX_A_ISSUE(s + RCX_ARITH_AHEAD);
                     const U4 e = eq[s];
-                    const RcxDivQv kk = kq[s];
                     u32 rec = 0; // past the end of a short block: a record that does nothing
-                    if (FULL || i0 + s < len) rec = enc.arith_q(e.x + e.y + e.z + c3q[s], e.w, kk.x, kk.y, ((u64)kk.w << 32) | kk.z);
+                    if (FULL || i0 + s < len)
+                        rec = enc.arith_i(e.x + e.y + e.z + c3q[s], e.w, RCX_A_U4_AT(dm[s >> 2], s & 3u), RCX_A_U4_AT(di[s >> 2], s & 3u), sh, prev_k8);
+                    if ((s & 3u) == 3u) { // the quarter's registers are free: the next chunk's quarter
+                        // (held in place by statements that no memory access is moved across: left to the compiler, all eight
+                        // loads gather behind the first quarter, in other registers)
+                        asm volatile("" ::: "memory");
+                        dm[s >> 2] = reinterpret_cast<const U4*>(dq_next)[s >> 2];
+                        di[s >> 2] = reinterpret_cast<const U4*>(dq_next + 16)[s >> 2];
+                        asm volatile("" ::: "memory");
+                    }
                     // two symbols' records leave as one ds_write2st64_b32 (consecutive symbols are 64 dwords apart): an LDS
                     // instruction costs a lone wave 12-16 cycles of issue whatever it carries (tools/diag/ubench.hip k_t_*)
                     if ((s & 1u) == 0) rec_even = rec;
@@ -407,8 +439,20 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                     }
                 }
 #undef RCX_A_ISSUE
+#undef RCX_A_U4_AT
             }
-        } else if (wave == 1) {
+            RCX_MC5_STEP_ENDS();
+        }
+        RCX_MC5_STEP_ENDS(); // (step nchunks + 1: the writer's last chunk)
+        RCX_MC5_STAMPS_OUT();
+        return;
+    }
+    U4 piece_ahead;
+    piece_ahead.x = piece_ahead.y = piece_ahead.z = piece_ahead.w = 0;
+    if (FULL && wave >= 2 && wave != RCX_DRAIN_WAVE && nchunks > 0) piece_ahead = *reinterpret_cast<const U4*>(in);
+    u32 l3a = 64, l3b = 128, l3c = 192; // level-3 wave: its sums (cpprcoder.h:1094-1132: every count 1)
+    for (u32 k = 0; k <= nchunks + 1; ++k) {
+        if (wave == 1) {
             RCX_MC_WRITER_STAGE(k, ring2, wr, out_pos) // chunk k-2
         } else if (wave == RCX_DRAIN_WAVE) {
             // ---- drain: what the writer had a barrier ago ----
@@ -521,7 +565,7 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                     if (s + RCX_MODEL_AHEAD < RCX_MC_CHUNK) RCX_M0_ISSUE(s + RCX_MODEL_AHEAD);
                     const u32 cc = rcx_byte_of(piece, s);
                     const u32 sum0 = rcx_pre4(ga[s], cc & 3), f0 = rcx_sel4(ga[s], cc & 3);
-                    if (FULL) { // (pairs: two ds_write2st64_b32 for two symbols)
+                    if (FULL) { // (pairs: fields 2 and 3 are one aligned qword, and the compiler makes the four stores ONE ds_write2st64_b64)
                         if ((s & 1u) == 0) held = sum0, held_f = f0;
                         else {
                             ws[RCX_RING_AT(s - 1, 2)] = held, ws[RCX_RING_AT(s, 2)] = sum0;
@@ -535,26 +579,17 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
 #undef RCX_M0_ISSUE
             }
         }
-#if defined(RCX_STAMP)
-        const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-        rcx_lds_barrier();
-        stamp_wait_ += __builtin_amdgcn_s_memtime() - t0_;
-#else
-        rcx_lds_barrier();
-#endif
+        RCX_MC5_STEP_ENDS();
     }
-#if defined(RCX_STAMP)
-    if (blockIdx.x == 7 && lane == 0) {
-        rcx_stamp_out[wave * 2] = __builtin_amdgcn_s_memtime() - stamp_begin_;
-        rcx_stamp_out[wave * 2 + 1] = stamp_wait_;
-    }
-#endif
+    RCX_MC5_STAMPS_OUT();
+#undef RCX_MC5_STEP_ENDS
+#undef RCX_MC5_STAMPS_OUT
 }
 
 template <class G = RcxBlocks>
 __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __restrict__ src, u64 n, u32 block, u64 nblocks,
                                                                 u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes,
-                                                                const DivEntry* __restrict__ divtab, u32* status,
+                                                                const u32* __restrict__ divq, u32* status,
                                                                 u32* __restrict__ redo, u32 lanes_used, const G g = G())
 {
     __shared__ U4 lds[RCX_MC5_LDS_U4];
@@ -567,9 +602,8 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     RCX_ENTRY(g, blk, nblocks, n, block);
 
     Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
-    DivEntry* stage = reinterpret_cast<DivEntry*>(lds + RCX_GROUPS * RCX_LANES);
-    u32* ring = reinterpret_cast<u32*>(lds + RCX_LDS_U4);
-    u32* ring2 = reinterpret_cast<u32*>(lds + RCX_MC_LDS_U4);
+    u32* ring = reinterpret_cast<u32*>(lds + RCX_MC5_TREE_U4); // (no divisor staging behind the tree: rcx_mc5_pipeline)
+    u32* ring2 = reinterpret_cast<u32*>(lds + RCX_MC5_TREE_U4 + RCX_MC_RING_U4);
     RCX_MC_OUTPUT(oq, ring2 + RCX_MC5_RING2_DW);
     u32* ring3 = oq.drained + RCX_LANES;
 
@@ -594,12 +628,8 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     StagedWriter wr;
     wr.begin(oq.ring, oq.dummy, lane);
     u32 drained = 0;
-    DivEntry ahead;
-    ahead.mul = ahead.add = ahead.shift = ahead.total = 0;
     U4 v;
-    if (wave == 0) {
-        ahead = divtab[lane];
-    } else if (wave == 1) {
+    if (wave == 1) {
         if (live) enc.begin(wave_slots, lane * (u32)slot, (u32)slot, len);
         oq.pos[lane] = 0;
     } else if (wave == 2) { // cpprcoder.h:1094-1132: every count 1 (level 3: registers of rcx_mc5_pipeline)
@@ -616,8 +646,8 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
 
     u8* payload = wave_slots + (u64)lane * slot + 4;
     const u32 cap = ((u32)slot - 4) & ~3u; // as EncLane::begin
-    if (full) rcx_mc5_pipeline<true>(wave, lane, len, nchunks, in, divtab, tree, stage, ring, ring2, ring3, enc, ahead, wr, oq.pos, drained, payload, cap, live);
-    else rcx_mc5_pipeline<false>(wave, lane, len, nchunks, in, divtab, tree, stage, ring, ring2, ring3, enc, ahead, wr, oq.pos, drained, payload, cap, live);
+    if (full) rcx_mc5_pipeline<true>(wave, lane, len, nchunks, in, divq, tree, ring, ring2, ring3, enc, wr, oq.pos, drained, payload, cap, live);
+    else rcx_mc5_pipeline<false>(wave, lane, len, nchunks, in, divq, tree, ring, ring2, ring3, enc, wr, oq.pos, drained, payload, cap, live);
 
     RCX_MC_CLOSE_HANDOVER(wave, RCX_DRAIN_WAVE, oq, enc, drained);
     if (wave == 1 && live) {

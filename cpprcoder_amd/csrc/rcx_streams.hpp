@@ -173,7 +173,7 @@ int rcx_stream_encode(rcx_ctx* c, int coder, const uint8_t* src, uint32_t n,
         // (its model, arithmetic and writer are five instruction streams on four SIMDs): one block, one lane in use.
         if ((r = ensure_redo(c, 1)) != RCX_OK) return r;
         hipLaunchKernelGGL(rcx_enc_mc5_k, dim3(1), dim3(RCX_MC5_THREADS), 0, nullptr, c->h_in, (u64)n, block, (u64)1, c->slots, slot, c->sizes,
-                           c->divtab(), c->status, c->redo, 1u);
+                           c->divq(), c->status, c->redo, 1u);
         adaptive_pass(c->redo);
     } else {
         adaptive_pass(nullptr);

@@ -62,7 +62,7 @@ def main():
                     quads = min(16, pow2(-(-nblocks // (4 * cus))))
                     enc_wgs, dec_waves = -(-nblocks // lanes), -(-nblocks // quads)
                     shape = {"enc_blocks_per_workgroup": lanes, "enc_workgroups": enc_wgs, "enc_waves_per_cu": round(7 * min(enc_wgs, cus) / cus, 2),
-                             "enc_lds_bytes_per_wave": 154624 // 7, "dec_blocks_per_wave": quads, "dec_waves": dec_waves,
+                             "enc_lds_bytes_per_wave": 153600 // 7, "dec_blocks_per_wave": quads, "dec_waves": dec_waves,
                              "dec_waves_per_cu": round(min(dec_waves, 8 * cus) / cus, 2), "dec_lds_bytes_per_wave": 78848 // 4}
                 total = int(offs[-1])
                 e, d = sorted(enc_ms)[1], sorted(dec_ms)[1]
