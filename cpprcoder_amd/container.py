@@ -91,16 +91,19 @@ stored item container, is parsed once and its payload, stream table, stored flag
 takes picks, destinations and their count from device tensors, only enqueues, and can be captured in a graph and replayed
 against tables that device code rewrites.  A bad entry is skipped and latched (sync_status), every other entry decodes.
 """
+import collections
 import contextlib
 
 import numpy as np
 
-from .layout import (BASE_OPS, DELTA_FLAG_BASE_CRC, DELTA_MAGIC, DELTA_VERSION, FLAG_BLKSORT, FLAG_CRC32, FLAG_STORED, ITEM_MAGIC, ITEM_VERSION,  # noqa: F401
+from .layout import (BASE_OP_NONE, BASE_OPS, DELTA_FLAG_BASE_CRC, DELTA_ITEMS_FLAG_BASE_CRC, DELTA_ITEMS_MAGIC, DELTA_ITEMS_VERSION, DELTA_MAGIC,  # noqa: F401
+                     DELTA_VERSION, FLAG_BLKSORT, FLAG_CRC32, FLAG_STORED, ITEM_MAGIC, ITEM_VERSION,
                      ITEM_WIDTHS, MAGIC, MAX_ITEM, PREDICTORS,
                      TYPED_ITEMS_MAGIC, TYPED_ITEMS_VERSION, TYPED_ITEMS_VERSION_STORED, TYPED_MAGIC, TYPED_VERSION, TYPED_VERSION_PRED, TYPED_VERSION_STORED, VERSION,
-                     VERSION_CRC, VERSION_STORED, WIDTHS, BaseMismatchError, ChecksumError, ContainerError, _typed_items_tables, block_lengths, coded_size,
-                     delta_header_bytes, header_bytes, item_header_bytes, parse, parse_delta, parse_items, parse_tensor_directory, parse_typed,
-                     parse_typed_items, tensor_directory_bytes, typed_header_bytes, typed_items_header_bytes)
+                     VERSION_CRC, VERSION_STORED, WIDTHS, BaseItemMismatchError, BaseMismatchError, ChecksumError, ContainerError, _typed_items_tables,
+                     block_lengths, coded_size, delta_header_bytes, delta_items_header_bytes, header_bytes, item_header_bytes, parse, parse_delta,
+                     parse_delta_items, parse_items, parse_tensor_directory, parse_typed, parse_typed_items, tensor_directory_bytes, typed_header_bytes,
+                     typed_items_header_bytes)
 
 AUTO = "auto"  # pack_typed(predict=AUTO): measured, see pick_predictor; never in a container
 
@@ -136,6 +139,16 @@ def _size(src) -> int:
     return int(src.numel()) if hasattr(src, "numel") else len(src)
 
 
+def _element_width(size, width, allowed, text: str) -> int:
+    """width=None: the element size of the array or tensor; plain bytes need a width."""
+    width = size if width is None else width
+    if width is None:
+        raise ContainerError("plain bytes have no element size: give the width")
+    if width not in allowed:
+        raise ContainerError(f"an element is {text} bytes wide, not {width}")
+    return width
+
+
 # ---- the device paths: one upload, the device calls, one download --------------------------------------------------------
 def _cuda(a, dtype=None):
     import torch
@@ -148,7 +161,7 @@ def _crcs_of(t) -> np.ndarray:
 
 
 def _gain(stored):
-    """The option stored=None | True | fraction of pack and pack_typed -> None, or the gain of include/rcx_stored.h."""
+    """The option stored=None | True | fraction of the pack calls -> None, or the gain of include/rcx_stored.h."""
     if stored is None or stored is False:
         return None
     from . import stored as calls
@@ -158,96 +171,76 @@ def _gain(stored):
         raise ContainerError(f"stored is None, True or a fraction 0 <= g < 1 of the block, not {stored!r}") from e
 
 
-def _mix_device(ctx, d_src, block: int, d_dst, d_offs, gain: int):
-    """Behind the encode call on d_src: the mix of include/rcx_stored.h -> (mixed streams, their table, the flags), on the device."""
+def _encode_device(ctx, d_src, cut, coder: int, checksum: bool, gain=None):
+    """The coder's input on the device, cut into blocks (cut: the block size) or into items (cut: their table of offsets)
+    -> (payload, offsets, crcs or None, stored flags or None): encode, the mix of the stored blocks or items behind it (with a
+    gain: include/rcx_stored.h, rcx_stored_items.h), the CRC-32 of every block or item of d_src (if asked for), one sync, the
+    downloads."""
     import torch
-    from . import rcx, stored as calls
-    nblocks = rcx.block_count(d_src.numel(), block)
-    d_mixed = torch.empty(d_src.numel(), dtype=torch.uint8, device="cuda")  # a mixed payload is never longer than the text
-    d_moffs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
-    d_flags = torch.zeros(nblocks, dtype=torch.uint8, device="cuda")
-    calls.mix_device(ctx, d_src, block, d_dst, d_dst.numel(), d_offs, gain, d_mixed, d_moffs, d_flags)
-    return d_mixed, d_moffs, d_flags
-
-
-def _encode_blocks(ctx, d_src, block: int, coder: int, checksum: bool, gain):
-    """The coder's input on the device -> (payload, offsets, crcs or None, stored flags or None): encode, the mix of the stored
-    blocks (if asked for), the CRC-32 of every block of d_src (if asked for), one sync, the downloads."""
-    import torch
-    from . import rcx
-    nblocks = rcx.block_count(d_src.numel(), block)
-    d_dst = torch.empty(rcx.encode_bound(d_src.numel(), block, coder), dtype=torch.uint8, device="cuda")
-    d_offs = torch.zeros(nblocks + 1, dtype=torch.int64, device="cuda")
-    ctx.encode_blocks_device(d_src, block, d_dst, d_offs, coder=coder)
+    from . import rcx, stored, stored_items
+    items = np.ndim(cut) > 0
+    count = len(cut) - 1 if items else rcx.block_count(d_src.numel(), cut)
+    bound = max(rcx.encode_items_bound(cut, coder), 1) if items else rcx.encode_bound(d_src.numel(), cut, coder)
+    d_dst = torch.empty(bound, dtype=torch.uint8, device="cuda")
+    d_offs = torch.zeros(count + 1, dtype=torch.int64, device="cuda")
+    (ctx.encode_items_device if items else ctx.encode_blocks_device)(d_src, cut, d_dst, d_offs, coder=coder)
     d_flags = None
-    if gain is not None:
-        d_dst, d_offs, d_flags = _mix_device(ctx, d_src, block, d_dst, d_offs, gain)
+    if gain is not None:  # (a mixed payload is never longer than the text)
+        d_mixed = torch.empty(max(int(cut[-1] - cut[0]) if items else d_src.numel(), 1), dtype=torch.uint8, device="cuda")
+        d_moffs = torch.zeros(count + 1, dtype=torch.int64, device="cuda")
+        d_flags = torch.zeros(max(count, 1), dtype=torch.uint8, device="cuda")
+        (stored_items.mix_items_device if items else stored.mix_device)(ctx, d_src, cut, d_dst, d_dst.numel(), d_offs, gain, d_mixed, d_moffs, d_flags)
+        d_dst, d_offs, d_flags = d_mixed, d_moffs, d_flags[:count]
     if checksum:
-        d_crc = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
-        ctx.crc32_blocks_device(d_src, block, d_crc)
+        d_crc = torch.zeros(count, dtype=torch.int32, device="cuda")
+        (ctx.crc32_items_device if items else ctx.crc32_blocks_device)(d_src, cut, d_crc)
     ctx.sync_status()
     offsets = d_offs.cpu().numpy().astype(np.uint64)
     return (d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc) if checksum else None,
             None if d_flags is None else d_flags.cpu().numpy())
 
 
-def _mix_items_device(ctx, d_src, soffs, d_dst, d_offs, gain: int):
-    """Behind the item encode call on d_src: the mix of include/rcx_stored_items.h -> (mixed streams, their table, the flags), on the device."""
-    import torch
-    from . import stored_items as calls
-    nitems = len(soffs) - 1
-    d_mixed = torch.empty(max(int(soffs[-1] - soffs[0]), 1), dtype=torch.uint8, device="cuda")  # a mixed payload is never longer than the items
-    d_moffs = torch.zeros(nitems + 1, dtype=torch.int64, device="cuda")
-    d_flags = torch.zeros(max(nitems, 1), dtype=torch.uint8, device="cuda")
-    calls.mix_items_device(ctx, d_src, soffs, d_dst, d_dst.numel(), d_offs, gain, d_mixed, d_moffs, d_flags)
-    return d_mixed, d_moffs, d_flags[:nitems]
-
-
-def _encode_items(ctx, d_src, soffs, coder: int, checksum: bool, gain=None):
-    """The item twin: the items of d_src at soffs -> (payload, offsets, crcs or None, stored flags or None): encode, the mix of
-    the stored items (if asked for), the CRC-32 of every item of d_src (if asked for), one sync, the downloads."""
-    import torch
-    from . import rcx
-    d_dst = torch.empty(max(rcx.encode_items_bound(soffs, coder), 1), dtype=torch.uint8, device="cuda")
-    d_offs = torch.zeros(len(soffs), dtype=torch.int64, device="cuda")
-    ctx.encode_items_device(d_src, soffs, d_dst, d_offs, coder=coder)
-    d_flags = None
-    if gain is not None:
-        d_dst, d_offs, d_flags = _mix_items_device(ctx, d_src, soffs, d_dst, d_offs, gain)
-    if checksum:
-        d_crc = torch.zeros(len(soffs) - 1, dtype=torch.int32, device="cuda")
-        ctx.crc32_items_device(d_src, soffs, d_crc)
-    ctx.sync_status()
-    offsets = d_offs.cpu().numpy().astype(np.uint64)
-    return (d_dst[: int(offsets[-1])].cpu().numpy(), offsets, _crcs_of(d_crc) if checksum else None,
-            None if d_flags is None else d_flags.cpu().numpy())
-
-
-def _sync_checked(ctx, kind: str, name=lambda k: k):
-    """The latch behind a verify call: a mismatch becomes ChecksumError with the container's index."""
+def _raise_latched(ctx, mismatch, what: str) -> None:
+    """The latch behind a verify call: a mismatch becomes the exception mismatch(position) makes, any other failure RcxError
+    naming `what` and the position."""
     from . import rcx
     st, bad = ctx.sync_status(raise_on_error=False)
     if st == rcx.E_CORRUPT:
-        raise ChecksumError(kind, name(int(bad)))
+        raise mismatch(int(bad))
     if st != rcx.OK:
-        raise rcx.RcxError(st, f"{kind} {bad}")
+        raise rcx.RcxError(st, f"{what} {bad}")
+
+
+def _verify_items_device(ctx, d_out, doffs, crcs, kind: str, owner) -> None:
+    """Stream k of d_out at doffs against crcs[k] -> ChecksumError naming owner[k], the container's index of it."""
+    ctx.verify_items_device(d_out, doffs, _cuda(crcs))
+    _raise_latched(ctx, lambda k: ChecksumError(kind, int(owner[k])), kind)
+
+
+def _decode_streams_device(ctx, c, doffs, d_out, pick=None) -> None:
+    """The streams pick[k] of a parsed container -> d_out at doffs; pick=None: every block, d_out whole.  With stored streams
+    through the call that copies them.  Then the sync: the decoder's own failures come first -- a stream that runs dry is an
+    RcxError, as without checksums."""
+    from . import stored
+    d_payload, d_offsets = _cuda(c["payload"]), _cuda(c["offsets"])
+    if c.get("stored") is not None:
+        stored.decode_device(ctx, d_payload, len(c["payload"]), d_offsets, c["stored"], doffs, d_out, pick=pick, coder=c["coder"])
+    elif pick is None:
+        ctx.decode_blocks_device(d_payload, len(c["payload"]), d_offsets, d_out.numel(), c["block"], d_out, coder=c["coder"])
+    else:
+        ctx.decode_items_device(d_payload, len(c["payload"]), d_offsets, doffs, d_out, pick=pick, coder=c["coder"])
+    ctx.sync_status()
 
 
 def _decode_all_device(ctx, c, m: int, verify: bool):
-    """Every block of a container, m bytes -> the device buffer: through the block call, or with stored blocks through the call
-    that copies them; then, if `verify` and the container has checksums, the blocks are verified."""
+    """Every block of a container, m bytes -> the device buffer; then, if `verify` and the container has checksums, the blocks
+    are verified."""
     import torch
     d_out = torch.empty(m, dtype=torch.uint8, device="cuda")
-    if c.get("stored") is None:
-        ctx.decode_blocks_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), m, c["block"], d_out, coder=c["coder"])
-    else:
-        from . import stored as calls
-        doffs = np.minimum(np.arange(c["nblocks"] + 1, dtype=np.uint64) * np.uint64(c["block"]), np.uint64(m))
-        calls.decode_device(ctx, _cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), c["stored"], doffs, d_out, coder=c["coder"])
-    ctx.sync_status()  # (the decoder's own failures first: a stream that runs dry is an RcxError, as without checksums)
+    _decode_streams_device(ctx, c, np.minimum(np.arange(c["nblocks"] + 1, dtype=np.uint64) * np.uint64(c["block"]), np.uint64(m)), d_out)
     if verify and c["crcs"] is not None:
         ctx.verify_blocks_device(d_out, c["block"], _cuda(c["crcs"]))
-        _sync_checked(ctx, "block")
+        _raise_latched(ctx, lambda k: ChecksumError("block", k), "block")
     return d_out
 
 
@@ -257,25 +250,13 @@ def _decode_picked_device(ctx, c, lengths, pick, kind: str, checked: bool):
     import torch
     from . import rcx
     pick = np.asarray(pick, dtype=np.uint64)
-    doffs = rcx.item_offsets(np.asarray(lengths, dtype=np.uint64)[pick.astype(np.int64)])
+    at = pick.astype(np.int64)
+    doffs = rcx.item_offsets(np.asarray(lengths, dtype=np.uint64)[at])
     d_out = torch.empty(max(int(doffs[-1]), 1), dtype=torch.uint8, device="cuda")
-    if c.get("stored") is None:
-        ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), doffs, d_out, pick=pick, coder=c["coder"])
-    else:
-        from . import stored as calls
-        calls.decode_device(ctx, _cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), c["stored"], doffs, d_out, pick=pick, coder=c["coder"])
-    ctx.sync_status()
+    _decode_streams_device(ctx, c, doffs, d_out, pick)
     if checked:
-        ctx.verify_items_device(d_out, doffs, _cuda(c["crcs"][pick.astype(np.int64)]))
-        _sync_checked(ctx, kind, lambda k: int(pick[k]))
+        _verify_items_device(ctx, d_out, doffs, c["crcs"][at], kind, at)
     return d_out, doffs
-
-
-def _decode_picked_checked(ctx, c, lengths, pick, kind: str) -> list:
-    """Streams pick[k] of a checked container, decoded back to back and verified -> their bytes."""
-    d_out, doffs = _decode_picked_device(ctx, c, lengths, pick, kind, True)
-    out = d_out.cpu().numpy()
-    return [out[int(doffs[k]): int(doffs[k + 1])] for k in range(len(pick))]
 
 
 # ---- RCXB and RCXI ---------------------------------------------------------------------------------------------------------------
@@ -296,7 +277,7 @@ def pack(data, block: int = 65536, coder: int = 0, ctx=None, blksort: bool = Fal
                 d_sorted = torch.empty(rcx.bwt_encode_bound(len(src)), dtype=torch.uint8, device="cuda")
                 ctx.bwt_encode_device(d_src, d_sorted)
                 d_src = d_sorted[: coded_size(len(src), FLAG_BLKSORT)]
-            payload, offsets, crcs, raw = _encode_blocks(ctx, d_src, block, coder, checksum, gain)
+            payload, offsets, crcs, raw = _encode_device(ctx, d_src, block, coder, checksum, gain)
             return header_bytes(coder, block, len(src), offsets, flags, crcs, raw) + payload.tobytes()
         payload, offsets = ctx.encode_blocks(ctx.bwt_encode(src) if blksort else src, block, coder=coder)
         return header_bytes(coder, block, len(src), offsets, flags) + payload.tobytes()
@@ -345,14 +326,12 @@ def unpack_range(blob, start: int, stop: int, ctx=None, verify: bool = True) -> 
     pick = np.arange(first, last + 1, dtype=np.uint64)
     lengths = block_lengths(c["n"], block)
     with _scope(ctx) as ctx:
-        if verify and c["crcs"] is not None:
-            parts = _decode_picked_checked(ctx, c, lengths, pick, "block")
-        elif c["stored"] is not None:
-            d_out, doffs = _decode_picked_device(ctx, c, lengths, pick, "block", False)
-            parts = [d_out[: int(doffs[-1])].cpu().numpy()]
+        checked = verify and c["crcs"] is not None
+        if checked or c["stored"] is not None:
+            d_out, doffs = _decode_picked_device(ctx, c, lengths, pick, "block", checked)
+            out = d_out[: int(doffs[-1])].cpu().numpy()
         else:
-            parts = ctx.decode_items(c["payload"], c["offsets"], lengths, pick=pick, coder=c["coder"])
-    out = np.concatenate(parts)
+            out = np.concatenate(ctx.decode_items(c["payload"], c["offsets"], lengths, pick=pick, coder=c["coder"]))
     return out[start - first * block: stop - first * block].tobytes()
 
 
@@ -365,7 +344,7 @@ def pack_items(items, coder: int = 0, ctx=None, checksum: bool = False) -> bytes
         if checksum:
             from . import rcx
             d_src = _cuda(np.concatenate(parts) if parts else np.zeros(0, np.uint8))
-            payload, offsets, crcs, _ = _encode_items(ctx, d_src, rcx.item_offsets(lengths), coder, True)
+            payload, offsets, crcs, _ = _encode_device(ctx, d_src, rcx.item_offsets(lengths), coder, True)
             return item_header_bytes(coder, lengths, offsets, crcs) + payload.tobytes()
         payload, offsets = ctx.encode_items(parts, coder=coder)
         return item_header_bytes(coder, lengths, offsets) + payload.tobytes()
@@ -382,13 +361,15 @@ def unpack_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
     with _scope(ctx) as ctx:
         if verify and c["crcs"] is not None:
             picked = np.arange(c["nitems"], dtype=np.uint64) if pick is None else pick
-            return [x.tobytes() for x in _decode_picked_checked(ctx, c, c["lengths"], picked, "item")]
+            d_out, doffs = _decode_picked_device(ctx, c, c["lengths"], picked, "item", True)
+            out = d_out.cpu().numpy()
+            return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
         return [x.tobytes() for x in ctx.decode_items(c["payload"], c["offsets"], c["lengths"], pick=pick, coder=c["coder"])]
 
 
-class OpenItems:
-    """An item container on the device (open_items): payload, stream table, stored flags and the items' lengths are uploaded
-    once; decode_into enqueues one call whose picks, destinations and count are read on the device (include/rcx_picks.h)."""
+class _Opened:
+    """What both have: the context (the caller's, or one of its own that close() closes) and, on the device, the payload, the
+    stream table, the stored flags and the items' lengths."""
 
     def __init__(self, c, lengths, offsets, stored, crcs, ctx):
         import torch
@@ -407,6 +388,22 @@ class OpenItems:
         self.d_stored = None if stored is None else _cuda(np.asarray(stored) != 0, dtype=np.uint8)
         self.d_lengths = _cuda(self.lengths if self.nitems else np.zeros(1, np.uint64))
         self._picks = picks
+
+    def close(self) -> None:
+        if self._own and self.ctx is not None:
+            self.ctx.close()
+        self.ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class OpenItems(_Opened):
+    """An item container on the device (open_items): payload, stream table, stored flags and the items' lengths are uploaded
+    once; decode_into enqueues one call whose picks, destinations and count are read on the device (include/rcx_picks.h)."""
 
     def reserve(self, max_pick: int) -> None:
         """The scratch of decode_into calls with at most max_pick entries: after it they allocate nothing in the context."""
@@ -433,19 +430,7 @@ class OpenItems:
         from . import rcx
         pick = np.asarray(pick, dtype=np.int64)
         doffs = rcx.item_offsets(self.lengths[pick]) if dst_offsets is None else np.asarray(dst_offsets, dtype=np.uint64)
-        self.ctx.verify_items_device(d_out, doffs, _cuda(self.crcs[pick]))
-        _sync_checked(self.ctx, "item", lambda k: int(pick[k]))
-
-    def close(self) -> None:
-        if self._own and self.ctx is not None:
-            self.ctx.close()
-        self.ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        _verify_items_device(self.ctx, d_out, doffs, self.crcs[pick], "item", pick)
 
 
 def open_items(blob, ctx=None) -> OpenItems:
@@ -472,7 +457,6 @@ def pick_predictor(c_none: int, c_delta: int, c_zigzag: int):
         if 64 * c < 63 * int(c_none) and (best is None or c < best[1]):
             best = (name, c)
     return best[0] if best else None
-
 
 CANDIDATES = (None, "delta", "zigzag", "xor", "sub", "subzz")  # by number: include/rcx_typed_stats.h, RCX_CAND_*
 _CANDIDATE_ORDER = (1, 2, 5, 4, 3)  # ties: what needs no base first, subzz the default among the ops
@@ -517,23 +501,19 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
     calls.  stored=True | fraction: blocks of the split text that do not shrink (by that fraction) are kept raw -- the low
     mantissa planes of floating-point data -- and the container is version 3 if there is one (the module's docstring)."""
     gain = _gain(stored)
-    auto = isinstance(predict, str) and predict == AUTO
+    auto = _is_auto(predict)
     if not auto and (not (predict is None or isinstance(predict, str)) or predict not in PREDICTORS):
         raise ContainerError(f"a predictor is None, 'delta', 'zigzag' or 'auto', not {predict!r}")
     pred = 0 if auto else PREDICTORS[predict]  # (nothing to measure in an empty buffer: none, version 1)
     src, size = _source(data)
-    width = size if width is None else width
-    if width is None:
-        raise ContainerError("plain bytes have no element size: give the width")
-    if width not in WIDTHS:
-        raise ContainerError(f"an element is 2, 4 or 8 bytes wide, not {width}")
+    width = _element_width(size, width, WIDTHS, "2, 4 or 8")
     import torch
     from . import predict as predictor, rcx
     n = _size(src)
     if n == 0:
         return typed_header_bytes(coder, block, 0, width, np.zeros(1, np.uint64), np.zeros(0, np.uint32) if checksum else None, pred)
     with _scope(ctx) as ctx:
-        d_src = src if hasattr(src, "numel") else _cuda(src)
+        d_src = _on_device(src)
         d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
         held = None  # the predictor whose split text d_split holds
         if auto:
@@ -541,7 +521,7 @@ def pack_typed(data, width=None, block: int = 65536, coder: int = 0, ctx=None, c
             pred = PREDICTORS[choice]
         if held != pred:
             predictor.split_device(ctx, d_src, width, block, pred, d_split)  # (no predictor: the plane filter's own kernel)
-        payload, offsets, crcs, raw = _encode_blocks(ctx, d_split, block, coder, checksum, gain)
+        payload, offsets, crcs, raw = _encode_device(ctx, d_split, block, coder, checksum, gain)
         return typed_header_bytes(coder, block, n, width, offsets, crcs, pred, raw) + payload.tobytes()
 
 
@@ -560,30 +540,39 @@ def unpack_typed(blob, ctx=None, verify: bool = True) -> bytes:
         return d_out.cpu().numpy().tobytes()
 
 
+def _cover(n: int, block: int, width: int, nblocks: int, start: int, stop: int):
+    """The superblocks of width * block bytes that cover [start, stop) of n bytes -> (their blocks, where their span begins and
+    ends in the data)."""
+    superblock = width * block
+    first, last = start // superblock, (stop - 1) // superblock
+    return np.arange(first * width, min(nblocks, (last + 1) * width), dtype=np.uint64), first * superblock, min(n, (last + 1) * superblock)
+
+
+def _decode_cover_device(ctx, c, pick, span: int, verify: bool):
+    """The picked blocks follow one another and all but the container's last are whole: back to back they are the span's split text."""
+    d_split, doffs = _decode_picked_device(ctx, c, block_lengths(c["n"], c["block"]), pick, "block", verify and c["crcs"] is not None)
+    if int(doffs[-1]) != span:
+        raise ContainerError("decoded size differs from the header")
+    return d_split[:span]
+
+
 def unpack_typed_range(blob, start: int, stop: int, ctx=None, verify: bool = True) -> bytes:
     """The bytes [start, stop) of the original: only the blocks of the superblocks that cover them are decoded and, in a
     container with checksums, verified; their span is joined as a buffer of its own."""
     import torch
     from . import predict as predictor
     c = parse_typed(blob)
-    n, block, width, nblocks = c["n"], c["block"], c["width"], c["nblocks"]
-    if not 0 <= start <= stop <= n:
+    if not 0 <= start <= stop <= c["n"]:
         raise ContainerError("range outside the data")
     if start == stop:
         return b""
-    superblock = width * block
-    first, last = start // superblock, (stop - 1) // superblock
-    pick = np.arange(first * width, min(nblocks, (last + 1) * width), dtype=np.uint64)
-    span = min(n, (last + 1) * superblock) - first * superblock
+    pick, lo, hi = _cover(c["n"], c["block"], c["width"], c["nblocks"], start, stop)
     with _scope(ctx) as ctx:
-        # the picked blocks follow one another and all but the container's last are whole: back to back they are the span's split text
-        d_split, doffs = _decode_picked_device(ctx, c, block_lengths(n, block), pick, "block", verify and c["crcs"] is not None)
-        if int(doffs[-1]) != span:
-            raise ContainerError("decoded size differs from the header")
-        d_out = torch.empty(span, dtype=torch.uint8, device="cuda")
-        predictor.join_device(ctx, d_split[:span], width, block, c["pred"], d_out)
+        d_split = _decode_cover_device(ctx, c, pick, hi - lo, verify)
+        d_out = torch.empty(hi - lo, dtype=torch.uint8, device="cuda")
+        predictor.join_device(ctx, d_split, c["width"], c["block"], c["pred"], d_out)
         out = d_out.cpu().numpy()
-    return out[start - first * superblock: stop - first * superblock].tobytes()
+    return out[start - lo: stop - lo].tobytes()
 
 
 # ---- RCXD: residuals against a base in front of the plane filter -------------------------------------------------------------------
@@ -593,13 +582,8 @@ def _on_device(src):
 
 def _verify_base_device(ctx, d_ref, block: int, crcs, first: int = 0) -> None:
     """d_ref: the base's bytes from its block `first` on, on the device; crcs: the table's entries for them."""
-    from . import rcx
     ctx.verify_blocks_device(d_ref, block, _cuda(crcs))
-    st, bad = ctx.sync_status(raise_on_error=False)
-    if st == rcx.E_CORRUPT:
-        raise BaseMismatchError(first + int(bad))
-    if st != rcx.OK:
-        raise rcx.RcxError(st, f"base block {bad}")
+    _raise_latched(ctx, lambda k: BaseMismatchError(first + k), "base block")
 
 
 def pick_op(c_xor: int, c_sub: int, c_subzz: int) -> str:
@@ -638,11 +622,7 @@ def pack_delta(data, base, width=None, block: int = 65536, coder: int = 0, ctx=N
     op = "subzz" if measured else op  # (nothing to measure in an empty buffer)
     src, size = _source(data)
     ref = _source(base)[0]
-    width = size if width is None else width
-    if width is None:
-        raise ContainerError("plain bytes have no element size: give the width")
-    if width not in ITEM_WIDTHS:
-        raise ContainerError(f"an element is 1, 2, 4 or 8 bytes wide, not {width}")
+    width = _element_width(size, width, ITEM_WIDTHS, "1, 2, 4 or 8")
     n = _size(src)
     if _size(ref) != n:
         raise ContainerError(f"the base has {_size(ref)} bytes, the data {n}: a base is as long as the data")
@@ -666,7 +646,7 @@ def pack_delta(data, base, width=None, block: int = 65536, coder: int = 0, ctx=N
         if base_check:
             d_guard = torch.zeros(rcx.block_count(n, block), dtype=torch.int32, device="cuda")
             ctx.crc32_blocks_device(d_ref, block, d_guard)
-        payload, offsets, crcs, raw = _encode_blocks(ctx, d_split, block, coder, checksum, gain)  # (one sync: the base's CRCs are there too)
+        payload, offsets, crcs, raw = _encode_device(ctx, d_split, block, coder, checksum, gain)  # (one sync: the base's CRCs are there too)
         return delta_header_bytes(BASE_OPS[op], width, block, n, _crcs_of(d_guard) if base_check else None) + inner(offsets, crcs, raw) + payload.tobytes()
 
 
@@ -705,24 +685,19 @@ def unpack_delta_range(blob, base, start: int, stop: int, ctx=None, verify: bool
     from . import base as calls
     c = parse_delta(blob)
     ref = _delta_base(c, base)
-    n, block, width, inner = c["n"], c["block"], c["width"], c["inner"]
-    if not 0 <= start <= stop <= n:
+    block, width = c["block"], c["width"]
+    if not 0 <= start <= stop <= c["n"]:
         raise ContainerError("range outside the data")
     if start == stop:
         return b""
-    superblock = width * block
-    first, last = start // superblock, (stop - 1) // superblock
-    pick = np.arange(first * width, min(inner["nblocks"], (last + 1) * width), dtype=np.uint64)
-    lo, hi = first * superblock, min(n, (last + 1) * superblock)
+    pick, lo, hi = _cover(c["n"], block, width, c["inner"]["nblocks"], start, stop)
     with _scope(ctx) as ctx:
         d_ref = _on_device(ref[lo:hi])
-        if verify and c["base_crcs"] is not None:  # a superblock is whole blocks of the base: its blocks first * width ..
-            _verify_base_device(ctx, d_ref, block, c["base_crcs"][first * width: first * width + (hi - lo + block - 1) // block], first * width)
-        d_split, doffs = _decode_picked_device(ctx, inner, block_lengths(n, block), pick, "block", verify and inner["crcs"] is not None)
-        if int(doffs[-1]) != hi - lo:
-            raise ContainerError("decoded size differs from the header")
+        if verify and c["base_crcs"] is not None:  # a superblock is whole blocks of the base: its blocks lo / block ..
+            _verify_base_device(ctx, d_ref, block, c["base_crcs"][lo // block: lo // block + (hi - lo + block - 1) // block], lo // block)
+        d_split = _decode_cover_device(ctx, c["inner"], pick, hi - lo, verify)
         d_out = torch.empty(hi - lo, dtype=torch.uint8, device="cuda")
-        calls.join_device(ctx, d_split[: hi - lo], d_ref, width, block, c["op"], d_out)
+        calls.join_device(ctx, d_split, d_ref, width, block, c["op"], d_out)
         out = d_out.cpu().numpy()
     return out[start - lo: stop - lo].tobytes()
 
@@ -746,7 +721,7 @@ def _item_predictors(predict, widths):
         raise ContainerError("one predictor per item")
     preds, auto = np.zeros(nitems, np.uint8), np.zeros(nitems, bool)
     for i, e in enumerate(entries):
-        if isinstance(e, str) and e == AUTO:
+        if _is_auto(e):
             auto[i] = widths[i] > 1  # (a width-1 item is never predicted)
         elif (e is None or isinstance(e, str)) and e in PREDICTORS:
             if e is not None and widths[i] == 1:
@@ -780,27 +755,46 @@ def _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d
     return out
 
 
-def _pack_typed_items_device(ctx, parts, lengths, widths, preds, auto, coder: int, checksum: bool, directory: bytes, gain=None) -> bytes:
+def _pack_items_device(ctx, parts, lengths, widths, preds, auto, coder: int, checksum: bool, directory: bytes, gain, delta=None) -> bytes:
     """parts: the items that have bytes -> the container: one gather (an upload unless all lie on the device), split, encode over
     the sub-items, with a gain the mix of the stored sub-items behind it (the rule is applied to what was coded, after predict="auto"
-    has decided), with checksum the CRC-32 of the sub-items of the split text, one download."""
+    has decided), with checksum the CRC-32 of the sub-items of the split text, one download.  delta=None: RCXJ.  delta=(refs, ops,
+    base_check): RCXK -- refs are the bases of those parts that have an op, gathered likewise; the one split call takes them, and
+    one CRC call over the bases makes the guard."""
     lengths = np.asarray(lengths, dtype=np.uint64)
     _typed_items_tables(lengths, widths, preds)
-    nsub = int(widths.astype(np.int64).sum())
+    nsub, nitems = int(widths.astype(np.int64).sum()), len(widths)
+    refs, ops, base_check = delta if delta is not None else (None, None, False)
+
+    def blob(preds, offsets, crcs, raw, guard):
+        prefix = b"" if delta is None else delta_items_header_bytes(ops, guard)
+        return prefix + typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory, raw)
+
     if int(lengths.sum()) == 0:  # nothing to code: no GPU
-        return typed_items_header_bytes(coder, lengths, widths, preds, np.zeros(nsub + 1, np.uint64), np.zeros(nsub, np.uint32) if checksum else None, directory)
+        crcs = np.zeros(nsub, np.uint32) if checksum else None
+        return blob(preds, np.zeros(nsub + 1, np.uint64), crcs, None, np.zeros(nitems, np.uint32) if base_check else None)
     import torch
-    from . import rcx, typed_items
+    from . import base_items, rcx, typed_items
     d_src = _gather_device(parts)
+    d_ref = None if delta is None else _gather_device(refs)
     with _scope(ctx) as ctx:
         offs = rcx.item_offsets(lengths)
         sub_offs = typed_items.sub_offsets(offs, widths)
         d_split = torch.empty(d_src.numel(), dtype=torch.uint8, device="cuda")
-        if auto.any():
+        if auto.any():  # (only items without an op are measured; the others go through as planes there and are not looked at)
             preds = _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d_split)
-        typed_items.split_device(ctx, d_src, offs, widths, preds, d_split)
-        payload, offsets, crcs, raw = _encode_items(ctx, d_split, sub_offs, coder, checksum, gain)
-        return typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory, raw) + payload.tobytes()
+        if delta is None:
+            typed_items.split_device(ctx, d_src, offs, widths, preds, d_split)
+        else:
+            boffs = _base_offsets(lengths, ops)
+            base_items.split_device(ctx, d_src, d_ref if d_ref.numel() else None, offs, boffs[:-1], widths, preds, ops, d_split)
+        if base_check:
+            d_guard = torch.zeros(nitems, dtype=torch.int32, device="cuda")
+            if d_ref.numel():
+                ctx.crc32_items_device(d_ref, boffs, d_guard)
+        payload, offsets, crcs, raw = _encode_device(ctx, d_split, sub_offs, coder, checksum, gain)  # (one sync: the bases' CRCs are there too)
+        guard = np.where((ops != BASE_OP_NONE) & (lengths > 0), _crcs_of(d_guard), 0).astype(np.uint32) if base_check else None
+        return blob(preds, offsets, crcs, raw, guard) + payload.tobytes()
 
 
 def pack_typed_items(items, widths=None, predict=None, coder: int = 0, ctx=None, checksum: bool = False, directory: bytes = b"", stored=None) -> bytes:
@@ -814,52 +808,69 @@ def pack_typed_items(items, widths=None, predict=None, coder: int = 0, ctx=None,
     written without the option.  With widths=1 that is the stored item container (pack_items has none)."""
     gain = _gain(stored)
     sources = [_source(x) for x in items]
-    if widths is None:
-        each = [w for _, w in sources]
-        if any(w is None for w in each):
-            raise ContainerError("plain bytes have no element size: give the width")
-    else:
-        each = list(widths) if isinstance(widths, (list, tuple, np.ndarray)) else [widths] * len(sources)
-        if len(each) != len(sources):
-            raise ContainerError("one width per item")
-    if any(type(w) not in (int, np.uint8, np.int64, np.int32) or int(w) not in ITEM_WIDTHS for w in each):
-        raise ContainerError(f"an element is 1, 2, 4 or 8 bytes wide, not {each!r}")
-    w = np.array(each, dtype=np.uint8)
+    w = _item_widths(sources, widths)
     preds, auto = _item_predictors(predict, w)
     parts = [x for x, _ in sources]
     lengths = np.array([_size(x) for x in parts], dtype=np.uint64)
-    return _pack_typed_items_device(ctx, parts, lengths, w, preds, auto, coder, checksum, directory, gain)
+    return _pack_items_device(ctx, parts, lengths, w, preds, auto, coder, checksum, directory, gain)
 
 
-def _unpack_typed_items_device(ctx, c, pick, verify: bool):
-    """The picked items of a parsed RCXJ container, decoded, verified and joined on the device -> (the device buffer, the
-    table of where each pick lies in it).  Only the picks' sub-items are decoded and checked."""
-    import torch
+def _sub_items(sub_first, widths, lengths, pick):
+    """The picks' sub-items of an RCXJ container, in order: back to back they are the split text of the picks back to back
+    -> (the sub-items, the pick that owns each, the picks' offsets back to back, their sub-items' offsets).  pick: int64, not empty."""
     from . import rcx, typed_items
+    subs = np.concatenate([np.arange(sub_first[k], sub_first[k + 1], dtype=np.int64) for k in pick])
+    doffs = rcx.item_offsets(lengths[pick])
+    return subs, np.repeat(pick, widths[pick].astype(np.int64)), doffs, typed_items.sub_offsets(doffs, widths[pick])
+
+
+def _unpack_items_device(ctx, c, pick, verify: bool, delta=None):
+    """The picked items of a parsed RCXJ container, decoded, verified and joined on the device -> (the device buffer, the table of
+    where each pick lies in it).  Only the picks' sub-items are decoded and checked.  delta=None: RCXJ.  delta=(k, refs, name): c
+    is the inner container of the parsed RCXK container k and refs are the bases of the picks that have an op and bytes, in the
+    picks' order: they are verified first, on the device, back to back (a pick without a base has length 0 there;
+    BaseItemMismatchError carries name(item)), and the join is the one against the bases."""
+    import torch
+    from . import base_items, typed_items
     pick = np.asarray(pick, dtype=np.int64)
     widths, preds = c["widths"][pick], c["preds"][pick]
-    doffs = rcx.item_offsets(c["lengths"][pick])
+    subs, owner, doffs, soffs = _sub_items(c["sub_first"], c["widths"], c["lengths"], pick)
     n = int(doffs[-1])
     d_out = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
     if n == 0:
         return d_out, doffs
-    # the picks' sub-items, in order: back to back they are the split text of the picks back to back
-    subs = np.concatenate([np.arange(c["sub_first"][k], c["sub_first"][k + 1], dtype=np.int64) for k in pick])
-    owner = np.repeat(pick, widths.astype(np.int64))
-    soffs = typed_items.sub_offsets(doffs, widths)
+    if delta is not None:
+        k, refs, name = delta
+        ops = k["ops"][pick]
+        boffs = _base_offsets(c["lengths"][pick], ops)
+        d_ref = _gather_device(refs)
+        if int(boffs[-1]) != d_ref.numel():
+            raise ContainerError("the bases are not as long as their items")
+        if verify and k["base_crcs"] is not None and d_ref.numel():
+            ctx.verify_items_device(d_ref, boffs, _cuda(k["base_crcs"][pick]))
+            _raise_latched(ctx, lambda at: BaseItemMismatchError(int(pick[at]), name(int(pick[at]))), "the base of item")
     d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
-    if c.get("stored") is None:
-        ctx.decode_items_device(_cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), soffs, d_split, pick=subs.astype(np.uint64), coder=c["coder"])
-    else:  # version 2: the stored sub-items are copied
-        from . import stored as calls
-        calls.decode_device(ctx, _cuda(c["payload"]), len(c["payload"]), _cuda(c["offsets"]), c["stored"], soffs, d_split, pick=subs.astype(np.uint64),
-                            coder=c["coder"])
-    ctx.sync_status()
+    _decode_streams_device(ctx, c, soffs, d_split, subs.astype(np.uint64))  # (version 2: the stored sub-items are copied)
     if verify and c["crcs"] is not None:
-        ctx.verify_items_device(d_split, soffs, _cuda(c["crcs"][subs]))
-        _sync_checked(ctx, "item", lambda k: int(owner[k]))
-    typed_items.join_device(ctx, d_split, doffs, widths, preds, d_out)
+        _verify_items_device(ctx, d_split, soffs, c["crcs"][subs], "item", owner)
+    if delta is None:
+        typed_items.join_device(ctx, d_split, doffs, widths, preds, d_out)
+    else:
+        base_items.join_device(ctx, d_split, d_ref if d_ref.numel() else None, doffs, boffs[:-1], widths, preds, ops, d_out)
     return d_out, doffs
+
+
+def _picked(nitems: int, pick):
+    if pick is not None and any(not 0 <= int(k) < nitems for k in pick):
+        raise ContainerError("no such item")
+    return np.arange(nitems, dtype=np.int64) if pick is None else np.array([int(k) for k in pick], dtype=np.int64)
+
+
+def _unpack_picked(ctx, c, picked, verify: bool, delta=None) -> list:
+    with _scope(ctx) as ctx:
+        d_out, doffs = _unpack_items_device(ctx, c, picked, verify, delta)
+        out = d_out.cpu().numpy()
+        return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
 
 
 def unpack_typed_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
@@ -867,20 +878,15 @@ def unpack_typed_items(blob, pick=None, ctx=None, verify: bool = True) -> list:
     picked items' sub-items are decoded, and in a container with checksums only they are verified: a mismatch raises
     ChecksumError naming the item."""
     c = parse_typed_items(blob)
-    if pick is not None and any(not 0 <= int(k) < c["nitems"] for k in pick):
-        raise ContainerError("no such item")
-    picked = np.arange(c["nitems"], dtype=np.int64) if pick is None else np.array([int(k) for k in pick], dtype=np.int64)
+    picked = _picked(c["nitems"], pick)
     if len(picked) == 0:
         return []
     if int(c["lengths"][picked].sum()) == 0:
         return [b""] * len(picked)
-    with _scope(ctx) as ctx:
-        d_out, doffs = _unpack_typed_items_device(ctx, c, picked, verify)
-        out = d_out.cpu().numpy()
-        return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
+    return _unpack_picked(ctx, c, picked, verify)
 
 
-class OpenTypedItems:
+class OpenTypedItems(_Opened):
     """A typed item container on the device (open_typed_items): payload, stream table, stored flags, the items' lengths, widths
     and predictors and sub_first are uploaded once; decode_into enqueues the sub-items' decode into a staging buffer
     (include/rcx_picks.h) and their join to where the caller wants the items (include/rcx_typed_picks.h), picks, destinations
@@ -891,30 +897,18 @@ class OpenTypedItems:
 
     def __init__(self, c, ctx):
         import torch
-        from . import picks, rcx, typed_picks
-        self.coder, self.nitems, self.nsub = c["coder"], c["nitems"], c["nsub"]
-        self.lengths = np.array(c["lengths"], dtype=np.uint64)
+        from . import typed_picks
+        self.nsub = c["nsub"]
         self.widths, self.preds = np.array(c["widths"], dtype=np.uint8), np.array(c["preds"], dtype=np.uint8)
         self.sub_first = np.array(c["sub_first"], dtype=np.int64)
-        self.crcs = c["crcs"]
-        self.max_len = int(self.lengths.max()) if self.nitems else 0
         self.max_sub_len = int(c["sub_lengths"].max()) if self.nsub else 0
-        self._own = ctx is None
-        self.ctx = rcx.Context(0) if ctx is None else ctx
-        self.payload_size = len(c["payload"])
-        self.d_payload = torch.zeros(max(self.payload_size, 16), dtype=torch.uint8, device="cuda")
-        if self.payload_size:
-            self.d_payload[: self.payload_size] = _cuda(c["payload"])
-        self.d_offsets = _cuda(c["offsets"])
-        stored = c.get("stored")
-        self.d_stored = None if stored is None else _cuda(np.asarray(stored) != 0, dtype=np.uint8)
+        super().__init__(c, c["lengths"], c["offsets"], c.get("stored"), c["crcs"], ctx)
         some = self.nitems > 0
-        self.d_lengths = _cuda(self.lengths if some else np.zeros(1, np.uint64))
         self.d_widths = _cuda(self.widths if some else np.ones(1, np.uint8)).to(torch.int64)
         self.d_preds = _cuda(self.preds if some else np.zeros(1, np.uint8)).to(torch.int64)
         self.d_sub_first = _cuda(self.sub_first)
         self.max_bytes, self.d_stage = 0, None
-        self._picks, self._join = picks, typed_picks
+        self._join = typed_picks
 
     def reserve(self, max_pick: int, max_bytes: int) -> None:
         """The scratch of decode_into calls with at most max_pick picks of at most max_bytes together, and the staging buffer of
@@ -980,26 +974,11 @@ class OpenTypedItems:
         container with checksums over the sub-items in the staging buffer, on the device -> ChecksumError naming the item."""
         if self.crcs is None:
             return
-        from . import rcx, typed_items
         pick = np.asarray(pick, dtype=np.int64)
         if len(pick) == 0 or int(self.lengths[pick].sum()) == 0:
             return
-        subs = np.concatenate([np.arange(self.sub_first[k], self.sub_first[k + 1], dtype=np.int64) for k in pick])
-        owner = np.repeat(pick, self.widths[pick].astype(np.int64))
-        soffs = typed_items.sub_offsets(rcx.item_offsets(self.lengths[pick]), self.widths[pick])
-        self.ctx.verify_items_device(self.d_stage, soffs, _cuda(self.crcs[subs]))
-        _sync_checked(self.ctx, "item", lambda k: int(owner[k]))
-
-    def close(self) -> None:
-        if self._own and self.ctx is not None:
-            self.ctx.close()
-        self.ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        subs, owner, _, soffs = _sub_items(self.sub_first, self.widths, self.lengths, pick)
+        _verify_items_device(self.ctx, self.d_stage, soffs, self.crcs[subs], "item", owner)
 
 
 def open_typed_items(blob, ctx=None) -> OpenTypedItems:
@@ -1010,6 +989,54 @@ def open_typed_items(blob, ctx=None) -> OpenTypedItems:
 
 
 # ---- tensors with names, on top of the typed item container ---------------------------------------------------------------
+def _as_tensor(name, t):
+    import torch
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t if t.flags.c_contiguous else np.ascontiguousarray(t))
+    if type(t).__module__.split(".")[0] != "torch":
+        raise ContainerError(f"{name!r} is neither a numpy array nor a torch tensor")
+    return t
+
+
+def _same_kind(a, b) -> bool:
+    return a.dtype == b.dtype and tuple(a.shape) == tuple(b.shape)
+
+
+_Cut = collections.namedtuple("_Cut", "name tensor src width first lengths entry")  # a tensor as items: its bytes, its first item, the items' lengths, its entry
+
+
+def _cut_tensors(named, block: int):
+    """Every tensor of a state dict cut into typed items of element_size * block bytes, its superblocks, one after another -> _Cut.
+    A generator: what a caller checks of one tensor is checked before the next tensor is looked at."""
+    first = 0
+    for name, t in named.items():
+        t = _as_tensor(name, t)
+        src, width = _source(t)
+        if width not in ITEM_WIDTHS:
+            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
+        nbytes = _size(src)
+        count = -(-nbytes // (width * block))
+        lengths = [width * block] * (count - 1) + [nbytes - (count - 1) * width * block] if nbytes else []
+        yield _Cut(name, t, src, width, first, lengths,
+                   {"name": name, "dtype": str(t.dtype).replace("torch.", ""), "shape": tuple(t.shape), "first": first, "count": count})
+        first += count
+
+
+def _its_base(cut, base):
+    """The base's tensor of that name, if it has the same dtype and shape; else None."""
+    theirs = _as_tensor(cut.name, base[cut.name]) if cut.name in base else None
+    return theirs if theirs is not None and _same_kind(theirs, cut.tensor) else None
+
+
+def _of(option, name):
+    return option.get(name) if isinstance(option, dict) else option
+
+
+def _block_checked(block: int) -> None:
+    if not 16 <= block <= MAX_ITEM:
+        raise ContainerError("a block is 16 bytes to RCX_MAX_BLOCK")
+
+
 def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=None, checksum: bool = False, stored=None) -> bytes:
     """named: a dict of names -> numpy arrays or contiguous torch tensors (CPU or GPU) -> an RCXJ container whose directory
     names them.  Every tensor is cut into typed items of element_size * block bytes, its superblocks.  predict: None, a
@@ -1017,38 +1044,23 @@ def pack_tensors(named, block: int = 65536, predict=None, coder: int = 0, ctx=No
     predicted.  An element size outside 1, 2, 4, 8 raises ContainerError.  stored=True | fraction: as in pack_typed_items -- the
     sub-items are the blocks pack_typed(..., stored=...) would keep raw, the low mantissa planes of floating-point tensors."""
     gain = _gain(stored)
-    import torch
-    if not 16 <= block <= MAX_ITEM:
-        raise ContainerError("a block is 16 bytes to RCX_MAX_BLOCK")
+    _block_checked(block)
     parts, lengths, widths, entry_preds, entries = [], [], [], [], []
-    for name, t in named.items():
-        if isinstance(t, np.ndarray):
-            t = torch.from_numpy(t if t.flags.c_contiguous else np.ascontiguousarray(t))
-        if type(t).__module__.split(".")[0] != "torch":
-            raise ContainerError(f"{name!r} is neither a numpy array nor a torch tensor")
-        src, width = _source(t)
-        if width not in ITEM_WIDTHS:
-            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
-        nbytes = _size(src)
-        count = -(-nbytes // (width * block))
-        entries.append({"name": name, "dtype": str(t.dtype).replace("torch.", ""), "shape": tuple(t.shape), "first": len(lengths), "count": count})
-        each = predict.get(name) if isinstance(predict, dict) else predict
-        if nbytes:
-            parts.append(src)
-            lengths += [width * block] * (count - 1) + [nbytes - (count - 1) * width * block]
-            widths += [width] * count
-            entry_preds += [None if width == 1 else each] * count
+    for cut in _cut_tensors(named, block):
+        entries.append(cut.entry)
+        if cut.lengths:
+            parts.append(cut.src)
+            lengths += cut.lengths
+            widths += [cut.width] * len(cut.lengths)
+            entry_preds += [None if cut.width == 1 else _of(predict, cut.name)] * len(cut.lengths)
     w = np.array(widths, dtype=np.uint8)
     preds, auto = _item_predictors(entry_preds, w)
-    return _pack_typed_items_device(ctx, parts, np.array(lengths, dtype=np.uint64), w, preds, auto, coder, checksum, tensor_directory_bytes(entries), gain)
+    return _pack_items_device(ctx, parts, np.array(lengths, dtype=np.uint64), w, preds, auto, coder, checksum, tensor_directory_bytes(entries), gain)
 
 
-def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool = True) -> dict:
-    """-> a dict of torch tensors of the recorded dtype and shape, on `device` ("cuda": no download).  names: only those
-    tensors, and only their items are decoded (and verified)."""
+def _wanted(c, names):
+    """The directory of a parsed RCXJ container and the tensors asked for -> (the names, their entries by name, their items)."""
     import torch
-    from . import rcx
-    c = parse_typed_items(blob)
     entries = parse_tensor_directory(c["directory"], c["nitems"])
     by_name = {e["name"]: e for e in entries}
     wanted = [e["name"] for e in entries] if names is None else list(names)
@@ -1058,11 +1070,20 @@ def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool
         if not isinstance(getattr(torch, by_name[n]["dtype"], None), torch.dtype):
             raise ContainerError(f"{by_name[n]['dtype']!r} is no torch dtype")
     pick = np.concatenate([np.arange(by_name[n]["first"], by_name[n]["first"] + by_name[n]["count"], dtype=np.int64) for n in wanted] + [np.zeros(0, np.int64)])
+    return wanted, by_name, pick
+
+
+def _unpack_tensors(ctx, c, wanted, by_name, pick, device: str, verify: bool, delta=lambda: None) -> dict:
+    """The picked items of the parsed RCXJ container c, decoded if any has bytes (delta(): what _unpack_items_device takes, made
+    only then), and the wanted tensors rebuilt from them, on `device`."""
+    import torch
+    from . import rcx
     out, at = {}, 0
     flat, doffs = None, rcx.item_offsets(c["lengths"][pick])
     if int(doffs[-1]):
+        how = delta()
         with _scope(ctx) as ctx:
-            flat, _ = _unpack_typed_items_device(ctx, c, pick, verify)
+            flat, _ = _unpack_items_device(ctx, c, pick, verify, how)
             flat = flat if device == "cuda" else flat.cpu()
     for n in wanted:
         e = by_name[n]
@@ -1079,16 +1100,18 @@ def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool
     return out
 
 
+def unpack_tensors(blob, names=None, device: str = "cpu", ctx=None, verify: bool = True) -> dict:
+    """-> a dict of torch tensors of the recorded dtype and shape, on `device` ("cuda": no download).  names: only those
+    tensors, and only their items are decoded (and verified)."""
+    c = parse_typed_items(blob)
+    return _unpack_tensors(ctx, c, *_wanted(c, names), device, verify)
+
+
 # ---- RCXK: an op against a base of its own, or a predictor, or neither, per buffer ----------------------------------------------
-from .layout import (BASE_OP_NONE, DELTA_ITEMS_FLAG_BASE_CRC, DELTA_ITEMS_MAGIC, DELTA_ITEMS_VERSION, BaseItemMismatchError,  # noqa: E402,F401
-                     delta_items_header_bytes, parse_delta_items)
-
-
 def _item_ops(ops, has_base):
     """ops: a name for every item that has a base, or one entry per item (a name, or None: no op) -> uint8[nitems]"""
     nitems = len(has_base)
-    each = isinstance(ops, (list, tuple))
-    entries = list(ops) if each else [ops if has_base[i] else None for i in range(nitems)]
+    entries = list(ops) if isinstance(ops, (list, tuple)) else [ops if has_base[i] else None for i in range(nitems)]
     if len(entries) != nitems:
         raise ContainerError("one op per item")
     out = np.full(nitems, BASE_OP_NONE, np.uint8)
@@ -1109,38 +1132,8 @@ def _base_offsets(lengths, ops):
     return rcx.item_offsets(np.where(ops != BASE_OP_NONE, lengths, 0).astype(np.uint64))
 
 
-def _pack_delta_items_device(ctx, parts, refs, lengths, widths, preds, auto, ops, coder: int, checksum: bool, directory: bytes, gain, base_check: bool) -> bytes:
-    """parts, refs: the items that have bytes, and the bases of those of them that have an op -> the container: one gather each
-    (an upload unless all lie on the device), one split call, encode over the sub-items (and mix, and CRC-32 of the split text) as
-    _pack_typed_items_device does them, one CRC call over the bases for the guard, one download."""
-    lengths = np.asarray(lengths, dtype=np.uint64)
-    _typed_items_tables(lengths, widths, preds)
-    nsub, nitems = int(widths.astype(np.int64).sum()), len(widths)
-    if int(lengths.sum()) == 0:  # nothing to code: no GPU
-        inner = typed_items_header_bytes(coder, lengths, widths, preds, np.zeros(nsub + 1, np.uint64), np.zeros(nsub, np.uint32) if checksum else None, directory)
-        return delta_items_header_bytes(ops, np.zeros(nitems, np.uint32) if base_check else None) + inner
-    import torch
-    from . import base_items, rcx, typed_items
-    d_src, d_ref = _gather_device(parts), _gather_device(refs)
-    with _scope(ctx) as ctx:
-        offs, boffs = rcx.item_offsets(lengths), _base_offsets(lengths, ops)
-        sub_offs = typed_items.sub_offsets(offs, widths)
-        d_split = torch.empty(d_src.numel(), dtype=torch.uint8, device="cuda")
-        if auto.any():  # (only items without an op are measured; the others go through as planes there and are not looked at)
-            preds = _measured_item_predictors(ctx, d_src, offs, widths, sub_offs, preds, auto, d_split)
-        base_items.split_device(ctx, d_src, d_ref if d_ref.numel() else None, offs, boffs[:-1], widths, preds, ops, d_split)
-        if base_check:
-            d_guard = torch.zeros(nitems, dtype=torch.int32, device="cuda")
-            if d_ref.numel():
-                ctx.crc32_items_device(d_ref, boffs, d_guard)
-        payload, offsets, crcs, raw = _encode_items(ctx, d_split, sub_offs, coder, checksum, gain)  # (one sync: the bases' CRCs are there too)
-        guard = None
-        if base_check:
-            guard = np.where((ops != BASE_OP_NONE) & (lengths > 0), _crcs_of(d_guard), 0).astype(np.uint32)
-        return delta_items_header_bytes(ops, guard) + typed_items_header_bytes(coder, lengths, widths, preds, offsets, crcs, directory, raw) + payload.tobytes()
-
-
-def _delta_item_widths(sources, widths):
+def _item_widths(sources, widths):
+    """widths=None: each source's element size; else one width for all, or one per item -> uint8[nitems], checked."""
     if widths is None:
         each = [w for _, w in sources]
         if any(w is None for w in each):
@@ -1211,6 +1204,11 @@ def _delta_item_masks(ops, predict, has_base, widths):
     return masks, op_entries, pred_entries
 
 
+def _no_costs(nitems: int) -> np.ndarray:
+    """Nothing to measure: every cost is 0, and the rule says none."""
+    return np.zeros((nitems, len(CANDIDATES)), np.uint64)
+
+
 def _decided(costs, masks, op_entries, pred_entries, groups=None):
     """pick_candidate per measured item -- per group of items (first, count) on the sums over the group, if groups are given: a
     tensor takes its base entirely or not at all -> (ops, predict): a name or None per item."""
@@ -1227,33 +1225,35 @@ def _decided(costs, masks, op_entries, pred_entries, groups=None):
     return ops, preds
 
 
-def _measured_candidates(ctx, parts, theirs, lengths, widths, masks):
-    """One measuring call for everything a pack has to measure (include/rcx_typed_stats.h) -> (costs uint64[nitems, 6]; the
-    items as views of the one device buffer; the bases likewise, those the measurement did not need as they were).  One gather
-    (an upload unless all lie on the device) each for the items and for the bases of the items that ask for an op."""
+def _need(masks, lengths):
+    """The items whose base a measurement reads: their mask has an op bit and they have bytes."""
     from . import typed_stats
-    nitems = len(widths)
-    lengths = np.asarray(lengths, dtype=np.uint64)
-    need = ((masks & typed_stats.OP_BITS) != 0) & (lengths > 0)
-    costs, d_src, d_ref, offs, boffs = _measured_costs(ctx, [x for x in parts if _size(x)], [theirs[i] for i in np.flatnonzero(need)], lengths, widths, masks)
-    views = [d_src[int(offs[i]): int(offs[i + 1])] for i in range(nitems)]
-    bases = [d_ref[int(boffs[i]): int(boffs[i + 1])] if need[i] else theirs[i] for i in range(nitems)]
-    return costs, views, bases
+    return ((masks & typed_stats.OP_BITS) != 0) & (lengths > 0)
 
 
 def _measured_costs(ctx, live, needed, lengths, widths, masks):
-    """live: the buffers that have bytes, back to back the items in order; needed: likewise the bases of the items whose mask has
-    an op bit and that have bytes -> (costs uint64[nitems, 6], the two device buffers, the items' offsets in them)."""
+    """live: the buffers that have bytes, back to back the items in order; needed: likewise the bases of the items of _need
+    -> (costs uint64[nitems, 6], the two device buffers, the items' offsets in them).  One measuring call for everything a pack has
+    to measure (include/rcx_typed_stats.h); one gather (an upload unless all lie on the device) each for the items and the bases."""
     import torch
     from . import rcx, typed_stats
     nitems = len(widths)
-    need = ((masks & typed_stats.OP_BITS) != 0) & (lengths > 0)
     d_src, d_ref = _gather_device(live), _gather_device(needed)
-    offs, boffs = rcx.item_offsets(lengths), rcx.item_offsets(np.where(need, lengths, 0).astype(np.uint64))
-    d_cost = torch.zeros(len(CANDIDATES) * nitems, dtype=torch.int64, device="cuda")
+    offs, boffs = rcx.item_offsets(lengths), rcx.item_offsets(np.where(_need(masks, lengths), lengths, 0).astype(np.uint64))
+    d_cost = torch.zeros(typed_stats.CANDS * nitems, dtype=torch.int64, device="cuda")
     if masks.any():
         typed_stats.items_device(ctx, d_src, d_ref if d_ref.numel() else None, offs, boffs[:-1], widths, masks, d_cost)
-    return d_cost.cpu().numpy().view(np.uint64).reshape(nitems, len(CANDIDATES)), d_src, d_ref, offs, boffs
+    return d_cost.cpu().numpy().view(np.uint64).reshape(nitems, typed_stats.CANDS), d_src, d_ref, offs, boffs
+
+
+def _measured_candidates(ctx, parts, theirs, lengths, widths, masks):
+    """_measured_costs on items and their bases -> (costs; the items as views of the one device buffer; the bases likewise, those
+    the measurement did not need as they were)."""
+    need = _need(masks, lengths)
+    costs, d_src, d_ref, offs, boffs = _measured_costs(ctx, [x for x in parts if _size(x)], [theirs[i] for i in np.flatnonzero(need)], lengths, widths, masks)
+    views = [d_src[int(offs[i]): int(offs[i + 1])] for i in range(len(widths))]
+    bases = [d_ref[int(boffs[i]): int(boffs[i + 1])] if need[i] else theirs[i] for i in range(len(widths))]
+    return costs, views, bases
 
 
 def _delta_items_inputs(items, bases, widths):
@@ -1261,7 +1261,7 @@ def _delta_items_inputs(items, bases, widths):
     sources = [_source(x) for x in items]
     if len(bases) != len(sources):
         raise ContainerError("one base, or None, per item")
-    w = _delta_item_widths(sources, widths)
+    w = _item_widths(sources, widths)
     parts = [x for x, _ in sources]
     lengths = np.array([_size(x) for x in parts], dtype=np.uint64)
     theirs = [None if b is None else _source(b)[0] for b in bases]
@@ -1292,8 +1292,8 @@ def choose_delta_items(items, bases, widths=None, ops="auto", predict=None, ctx=
     measuring call on the GPU (include/rcx_typed_stats.h), the rule is pick_candidate."""
     parts, theirs, lengths, w = _delta_items_inputs(items, bases, widths)
     masks, op_entries, pred_entries = _delta_item_masks(ops, predict, [b is not None for b in theirs], w)
-    if not masks.any() or not int(lengths.sum()):  # nothing to measure: every cost is 0
-        return _decided(np.zeros((len(w), len(CANDIDATES)), np.uint64), masks, op_entries, pred_entries)
+    if not masks.any() or not int(lengths.sum()):  # nothing to measure
+        return _decided(_no_costs(len(w)), masks, op_entries, pred_entries)
     with _scope(ctx) as ctx:
         costs, _, _ = _measured_candidates(ctx, parts, theirs, lengths, w, masks)
     return _decided(costs, masks, op_entries, pred_entries)
@@ -1314,80 +1314,22 @@ def pack_delta_items(items, bases, widths=None, ops="subzz", predict=None, coder
     no base at all; such an item's predict entry is None, or "auto" to put the predictors into the comparison.  Then the path
     is the one of the named choices, and the container byte for byte what choose_delta_items' lists given here write."""
     gain = _gain(stored)
-    if isinstance(ops, (list, tuple)) and _says_auto(ops):
-        parts, theirs, lengths, w = _delta_items_inputs(items, bases, widths)
-        masks, op_entries, pred_entries = _delta_item_masks(ops, predict, [b is not None for b in theirs], w)
+    parts, theirs, lengths, w = _delta_items_inputs(items, bases, widths)
 
-        def finish(ctx, costs, parts, theirs):
-            chosen_ops, chosen_preds = _decided(costs, masks, op_entries, pred_entries)
-            o = _item_ops(chosen_ops, [b is not None for b in theirs])
-            preds, auto = _delta_item_predictors(chosen_preds, w, o)
-            refs = [b for b, op in zip(theirs, o) if op != BASE_OP_NONE and _size(b)]
-            return _pack_delta_items_device(ctx, [x for x in parts if _size(x)], refs, lengths, w, preds, auto, o, coder, checksum, directory, gain, base_check)
+    def named(ctx, ops, predict, parts, theirs):
+        o = _item_ops(ops, [b is not None for b in theirs])
+        preds, auto = _delta_item_predictors(predict, w, o)
+        refs = [b for b, op in zip(theirs, o) if op != BASE_OP_NONE and _size(b)]
+        return _pack_items_device(ctx, [x for x in parts if _size(x)], lengths, w, preds, auto, coder, checksum, directory, gain, (refs, o, base_check))
 
-        if not int(lengths.sum()):  # nothing to measure: every cost is 0, and the rule says none
-            return finish(ctx, np.zeros((len(w), len(CANDIDATES)), np.uint64), parts, theirs)
-        with _scope(ctx) as ctx:
-            return finish(ctx, *_measured_candidates(ctx, parts, theirs, lengths, w, masks))
-    sources = [_source(x) for x in items]
-    if len(bases) != len(sources):
-        raise ContainerError("one base, or None, per item")
-    w = _delta_item_widths(sources, widths)
-    parts = [x for x, _ in sources]
-    lengths = np.array([_size(x) for x in parts], dtype=np.uint64)
-    theirs = [None if b is None else _source(b)[0] for b in bases]
-    for i, b in enumerate(theirs):
-        if b is not None and _size(b) != int(lengths[i]):
-            raise ContainerError(f"the base of item {i} has {_size(b)} bytes, the item {int(lengths[i])}: a base is as long as its item")
-    o = _item_ops(ops, [b is not None for b in theirs])
-    preds, auto = _delta_item_predictors(predict, w, o)
-    refs = [b for b, op in zip(theirs, o) if op != BASE_OP_NONE and _size(b)]
-    return _pack_delta_items_device(ctx, [x for x in parts if _size(x)], refs, lengths, w, preds, auto, o, coder, checksum, directory, gain, base_check)
-
-
-def _unpack_delta_items_device(ctx, c, refs, pick, verify: bool, name=lambda k: None):
-    """The picked items of a parsed RCXK container -> (the device buffer, the table of where each pick lies in it).  refs: the
-    bases of the picks that have an op and bytes, in the picks' order.  The bases are verified first, on the device, back to back
-    (a pick without a base has length 0 there); then the picks' sub-items are decoded and checked as _unpack_typed_items_device
-    does it, and joined against the bases."""
-    import torch
-    from . import base_items, rcx, typed_items
-    inner = c["inner"]
-    pick = np.asarray(pick, dtype=np.int64)
-    widths, preds, ops = inner["widths"][pick], inner["preds"][pick], c["ops"][pick]
-    doffs = rcx.item_offsets(inner["lengths"][pick])
-    n = int(doffs[-1])
-    d_out = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
-    if n == 0:
-        return d_out, doffs
-    boffs = _base_offsets(inner["lengths"][pick], ops)
-    d_ref = _gather_device(refs)
-    if int(boffs[-1]) != d_ref.numel():
-        raise ContainerError("the bases are not as long as their items")
-    if verify and c["base_crcs"] is not None and d_ref.numel():
-        ctx.verify_items_device(d_ref, boffs, _cuda(c["base_crcs"][pick]))
-        st, bad = ctx.sync_status(raise_on_error=False)
-        if st == rcx.E_CORRUPT:
-            raise BaseItemMismatchError(int(pick[int(bad)]), name(int(pick[int(bad)])))
-        if st != rcx.OK:
-            raise rcx.RcxError(st, f"the base of item {bad}")
-    subs = np.concatenate([np.arange(inner["sub_first"][k], inner["sub_first"][k + 1], dtype=np.int64) for k in pick])
-    owner = np.repeat(pick, widths.astype(np.int64))
-    soffs = typed_items.sub_offsets(doffs, widths)
-    d_split = torch.empty(n, dtype=torch.uint8, device="cuda")
-    if inner.get("stored") is None:
-        ctx.decode_items_device(_cuda(inner["payload"]), len(inner["payload"]), _cuda(inner["offsets"]), soffs, d_split, pick=subs.astype(np.uint64),
-                                coder=inner["coder"])
-    else:  # version 2 of the inner container: the stored sub-items are copied
-        from . import stored as calls
-        calls.decode_device(ctx, _cuda(inner["payload"]), len(inner["payload"]), _cuda(inner["offsets"]), inner["stored"], soffs, d_split,
-                            pick=subs.astype(np.uint64), coder=inner["coder"])
-    ctx.sync_status()
-    if verify and inner["crcs"] is not None:
-        ctx.verify_items_device(d_split, soffs, _cuda(inner["crcs"][subs]))
-        _sync_checked(ctx, "item", lambda k: int(owner[k]))
-    base_items.join_device(ctx, d_split, d_ref if d_ref.numel() else None, doffs, boffs[:-1], widths, preds, ops, d_out)
-    return d_out, doffs
+    if not (isinstance(ops, (list, tuple)) and _says_auto(ops)):
+        return named(ctx, ops, predict, parts, theirs)
+    masks, op_entries, pred_entries = _delta_item_masks(ops, predict, [b is not None for b in theirs], w)
+    if not int(lengths.sum()):  # nothing to measure
+        return named(ctx, *_decided(_no_costs(len(w)), masks, op_entries, pred_entries), parts, theirs)
+    with _scope(ctx) as ctx:
+        costs, parts, theirs = _measured_candidates(ctx, parts, theirs, lengths, w, masks)
+        return named(ctx, *_decided(costs, masks, op_entries, pred_entries), parts, theirs)
 
 
 def _picked_bases(c, picked, base_of, what=lambda k: f"item {k}"):
@@ -1415,52 +1357,30 @@ def unpack_delta_items(blob, bases, pick=None, ctx=None, verify: bool = True) ->
     c = parse_delta_items(blob)
     if len(bases) != c["nitems"]:
         raise ContainerError("one base, or None, per item of the container")
-    if pick is not None and any(not 0 <= int(k) < c["nitems"] for k in pick):
-        raise ContainerError("no such item")
-    picked = np.arange(c["nitems"], dtype=np.int64) if pick is None else np.array([int(k) for k in pick], dtype=np.int64)
+    picked = _picked(c["nitems"], pick)
     if len(picked) == 0:
         return []
     if int(c["inner"]["lengths"][picked].sum()) == 0:
         return [b""] * len(picked)
     refs = _picked_bases(c, picked, lambda k: bases[k])
-    with _scope(ctx) as ctx:
-        d_out, doffs = _unpack_delta_items_device(ctx, c, refs, picked, verify)
-        out = d_out.cpu().numpy()
-        return [out[int(doffs[k]): int(doffs[k + 1])].tobytes() for k in range(len(picked))]
+    return _unpack_picked(ctx, c["inner"], picked, verify, (c, refs, lambda k: None))
 
 
-def _as_tensor(name, t):
-    import torch
-    if isinstance(t, np.ndarray):
-        t = torch.from_numpy(t if t.flags.c_contiguous else np.ascontiguousarray(t))
-    if type(t).__module__.split(".")[0] != "torch":
-        raise ContainerError(f"{name!r} is neither a numpy array nor a torch tensor")
-    return t
+_Row = collections.namedtuple("_Row", "name src ref first count op pred mask")  # a tensor of pack_tensors_delta: op, pred: None where measured
 
 
 def _tensor_candidates(named, base, block: int, op, predict):
-    """The items pack_tensors_delta cuts a state dict into, and what is to be measured of them -> dict(rows: per tensor (name,
-    its bytes, its base's bytes or None, first item, item count, the op entry, the predictor entry -- None where measured --,
-    the mask); lengths, widths, masks per item)."""
+    """The items pack_tensors_delta cuts a state dict into, and what is to be measured of them -> dict(rows: a _Row per tensor;
+    lengths, widths, masks per item)."""
     rows, lengths, widths, masks = [], [], [], []
-    for name, t in named.items():
-        t = _as_tensor(name, t)
-        src, width = _source(t)
-        if width not in ITEM_WIDTHS:
-            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
-        nbytes = _size(src)
-        count = -(-nbytes // (width * block)) if nbytes else 0
-        theirs = _as_tensor(name, base[name]) if name in base else None
-        if theirs is not None and (theirs.dtype != t.dtype or tuple(theirs.shape) != tuple(t.shape)):
-            theirs = None
-        each_op = (op.get(name) if isinstance(op, dict) else op) if theirs is not None else None
-        each = predict.get(name) if isinstance(predict, dict) else predict
-        m, o, p = _delta_item_masks([each_op], each, [theirs is not None], np.array([width], np.uint8))
-        rows.append((name, src, None if theirs is None else _source(theirs)[0], len(lengths), count, o[0], p[0], int(m[0])))
-        if nbytes:
-            lengths += [width * block] * (count - 1) + [nbytes - (count - 1) * width * block]
-            widths += [width] * count
-            masks += [int(m[0])] * count
+    for cut in _cut_tensors(named, block):
+        theirs = _its_base(cut, base)
+        each_op = _of(op, cut.name) if theirs is not None else None
+        m, o, p = _delta_item_masks([each_op], _of(predict, cut.name), [theirs is not None], np.array([cut.width], np.uint8))
+        rows.append(_Row(cut.name, cut.src, None if theirs is None else _source(theirs)[0], cut.first, len(cut.lengths), o[0], p[0], int(m[0])))
+        lengths += cut.lengths
+        widths += [cut.width] * len(cut.lengths)
+        masks += [int(m[0])] * len(cut.lengths)
     return {"rows": rows, "lengths": np.array(lengths, np.uint64), "widths": np.array(widths, np.uint8), "masks": np.array(masks, np.uint8)}
 
 
@@ -1468,15 +1388,18 @@ def tensor_delta_masks(named, base, block: int = 65536, op="auto", predict=None)
     """What choose_tensors_delta measures, without a GPU -> dict(lengths, widths, masks per item; first: name -> (its first item,
     its item count)): the tables typed_stats.costs_numpy takes for choose_tensors_delta_from_costs."""
     c = _tensor_candidates(named, base, block, op, predict)
-    return {"lengths": c["lengths"], "widths": c["widths"], "masks": c["masks"], "first": {r[0]: (r[3], r[4]) for r in c["rows"]}}
+    return {"lengths": c["lengths"], "widths": c["widths"], "masks": c["masks"], "first": {r.name: (r.first, r.count) for r in c["rows"]}}
 
 
-def _tensors_decided(c, costs):
+def _tensors_decided(c, costs=None):
+    """costs=None: nothing was measured."""
     rows = c["rows"]
-    ops, preds = _decided(costs, c["masks"], [r[5] for r in rows for _ in range(r[4])], [r[6] for r in rows for _ in range(r[4])],
-                          groups=[(r[3], r[4]) for r in rows])
+    costs = _no_costs(len(c["masks"])) if costs is None else costs
+    ops, preds = _decided(costs, c["masks"], [r.op for r in rows for _ in range(r.count)], [r.pred for r in rows for _ in range(r.count)],
+                          groups=[(r.first, r.count) for r in rows])
     # (a tensor without bytes has no item to ask: the rule on costs of 0 says none)
-    return ({r[0]: (ops[r[3]] if r[4] else None if r[7] else r[5]) for r in rows}, {r[0]: (preds[r[3]] if r[4] else None if r[7] else r[6]) for r in rows})
+    return ({r.name: (ops[r.first] if r.count else None if r.mask else r.op) for r in rows},
+            {r.name: (preds[r.first] if r.count else None if r.mask else r.pred) for r in rows})
 
 
 def choose_tensors_delta_from_costs(costs, named, base, block: int = 65536, op="auto", predict=None):
@@ -1490,11 +1413,11 @@ def choose_tensors_delta(named, base, block: int = 65536, op="auto", predict=Non
     tensor's items: a tensor needs its base entirely or not at all."""
     c = _tensor_candidates(named, base, block, op, predict)
     if not c["masks"].any():
-        return _tensors_decided(c, np.zeros((len(c["masks"]), len(CANDIDATES)), np.uint64))
+        return _tensors_decided(c)
     from . import typed_stats
     with _scope(ctx) as ctx:
-        live = [r[1] for r in c["rows"] if r[4]]
-        needed = [r[2] for r in c["rows"] if r[4] and r[7] & typed_stats.OP_BITS]
+        live = [r.src for r in c["rows"] if r.count]
+        needed = [r.ref for r in c["rows"] if r.count and r.mask & typed_stats.OP_BITS]
         return _tensors_decided(c, _measured_costs(ctx, live, needed, c["lengths"], c["widths"], c["masks"])[0])
 
 
@@ -1507,50 +1430,38 @@ def pack_tensors_delta(named, base, block: int = 65536, op="subzz", predict=None
     a name in the dict whose base is missing or of another dtype or shape raises ContainerError.  Every tensor is cut into
     items of element_size * block bytes, and its base with it."""
     gain = _gain(stored)
-    if not 16 <= block <= MAX_ITEM:
-        raise ContainerError("a block is 16 bytes to RCX_MAX_BLOCK")
+    _block_checked(block)
     if isinstance(op, dict):
         for name, e in op.items():
-            if e is not None and name in named and (name not in base or _as_tensor(name, base[name]).dtype != _as_tensor(name, named[name]).dtype
-                                                    or tuple(_as_tensor(name, base[name]).shape) != tuple(_as_tensor(name, named[name]).shape)):
+            if e is not None and name in named and not (name in base and _same_kind(_as_tensor(name, base[name]), _as_tensor(name, named[name]))):
                 raise ContainerError(f"{name!r} has an op, and the base has no tensor of that name, dtype and shape")
     if _says_auto(op):
         c = _tensor_candidates(named, base, block, op, predict)
         if not c["masks"].any():
-            op, predict = _tensors_decided(c, np.zeros((len(c["masks"]), len(CANDIDATES)), np.uint64))
-            return pack_tensors_delta(named, base, block, op, predict, coder, ctx, checksum, stored, base_check)
+            return pack_tensors_delta(named, base, block, *_tensors_decided(c), coder, ctx, checksum, stored, base_check)
         with _scope(ctx) as ctx:  # what is measured and then packed goes up once
             named = {name: _as_tensor(name, t).cuda() for name, t in named.items()}
             base = {name: _as_tensor(name, base[name]).cuda() for name in named if name in base}
             op, predict = choose_tensors_delta(named, base, block, op, predict, ctx)
             return pack_tensors_delta(named, base, block, op, predict, coder, ctx, checksum, stored, base_check)
     parts, refs, lengths, widths, entry_preds, entry_ops, entries = [], [], [], [], [], [], []
-    for name, t in named.items():
-        t = _as_tensor(name, t)
-        src, width = _source(t)
-        if width not in ITEM_WIDTHS:
-            raise ContainerError(f"{name!r}: an element is 1, 2, 4 or 8 bytes wide, not {width}")
-        nbytes = _size(src)
-        count = -(-nbytes // (width * block))
-        entries.append({"name": name, "dtype": str(t.dtype).replace("torch.", ""), "shape": tuple(t.shape), "first": len(lengths), "count": count})
-        theirs = _as_tensor(name, base[name]) if name in base else None
-        each_op = op.get(name) if isinstance(op, dict) else op
-        if theirs is None or theirs.dtype != t.dtype or tuple(theirs.shape) != tuple(t.shape):
-            each_op = None
-        each = None if each_op is not None else predict.get(name) if isinstance(predict, dict) else predict
-        if nbytes:
-            parts.append(src)
+    for cut in _cut_tensors(named, block):
+        entries.append(cut.entry)
+        theirs = _its_base(cut, base)
+        each_op = _of(op, cut.name) if theirs is not None else None
+        if cut.lengths:
+            parts.append(cut.src)
             if each_op is not None:
                 refs.append(_source(theirs)[0])
-            lengths += [width * block] * (count - 1) + [nbytes - (count - 1) * width * block]
-            widths += [width] * count
-            entry_preds += [None if width == 1 else each] * count
-            entry_ops += [each_op] * count
+            lengths += cut.lengths
+            widths += [cut.width] * len(cut.lengths)
+            entry_preds += [None if cut.width == 1 or each_op is not None else _of(predict, cut.name)] * len(cut.lengths)
+            entry_ops += [each_op] * len(cut.lengths)
     w = np.array(widths, dtype=np.uint8)
     o = _item_ops(entry_ops, [e is not None for e in entry_ops])
     preds, auto = _item_predictors(entry_preds, w)
-    return _pack_delta_items_device(ctx, parts, refs, np.array(lengths, dtype=np.uint64), w, preds, auto, o, coder, checksum, tensor_directory_bytes(entries),
-                                    gain, base_check)
+    return _pack_items_device(ctx, parts, np.array(lengths, dtype=np.uint64), w, preds, auto, coder, checksum, tensor_directory_bytes(entries), gain,
+                              (refs, o, base_check))
 
 
 def unpack_tensors_delta(blob, base, names=None, device: str = "cpu", ctx=None, verify: bool = True) -> dict:
@@ -1558,20 +1469,10 @@ def unpack_tensors_delta(blob, base, names=None, device: str = "cpu", ctx=None, 
     tensors; only their items are decoded (and verified), and only their bases are needed and verified: a tensor that was
     packed against a base and is missing from `base`, or has another size there, raises ContainerError, one whose bytes differ
     BaseItemMismatchError with the item and the tensor's name."""
-    import torch
-    from . import rcx
     c = parse_delta_items(blob)
     inner = c["inner"]
-    entries = parse_tensor_directory(inner["directory"], c["nitems"])
-    by_name = {e["name"]: e for e in entries}
-    wanted = [e["name"] for e in entries] if names is None else list(names)
-    if any(n not in by_name for n in wanted):
-        raise ContainerError("no such tensor")
-    for n in wanted:
-        if not isinstance(getattr(torch, by_name[n]["dtype"], None), torch.dtype):
-            raise ContainerError(f"{by_name[n]['dtype']!r} is no torch dtype")
-    pick = np.concatenate([np.arange(by_name[n]["first"], by_name[n]["first"] + by_name[n]["count"], dtype=np.int64) for n in wanted] + [np.zeros(0, np.int64)])
-    owner = {int(k): e["name"] for e in entries for k in range(e["first"], e["first"] + e["count"])}
+    wanted, by_name, pick = _wanted(inner, names)
+    owner = {int(k): e["name"] for e in by_name.values() for k in range(e["first"], e["first"] + e["count"])}
     # the bases of the wanted tensors, cut as the tensors were: item k of a tensor is the same bytes of its base
     cut = {}
     for n in wanted:
@@ -1588,23 +1489,5 @@ def unpack_tensors_delta(blob, base, names=None, device: str = "cpu", ctx=None, 
         for k in items:
             cut[k] = ref[at: at + int(inner["lengths"][k])]
             at += int(inner["lengths"][k])
-    out, at = {}, 0
-    flat, doffs = None, rcx.item_offsets(inner["lengths"][pick])
-    if int(doffs[-1]):
-        refs = _picked_bases(c, pick, cut.get, lambda k: f"item {k} of tensor {owner.get(k)!r}")
-        with _scope(ctx) as ctx:
-            flat, _ = _unpack_delta_items_device(ctx, c, refs, pick, verify, owner.get)
-            flat = flat if device == "cuda" else flat.cpu()
-    for n in wanted:
-        e = by_name[n]
-        dtype = getattr(torch, e["dtype"])
-        a, b = int(doffs[at]), int(doffs[at + e["count"]])
-        at += e["count"]
-        count = int(np.prod(e["shape"], dtype=np.int64)) if len(e["shape"]) else 1
-        if b - a != count * torch.empty(0, dtype=dtype).element_size():
-            raise ContainerError(f"{n!r}: the items do not hold the tensor the directory describes")
-        if b == a:
-            out[n] = torch.empty(e["shape"], dtype=dtype, device=device)
-        else:  # (a copy: a tensor begins where the one before ends, at any alignment)
-            out[n] = flat[a:b].clone().view(dtype).reshape(e["shape"])
-    return out
+    return _unpack_tensors(ctx, inner, wanted, by_name, pick, device, verify,
+                           lambda: (c, _picked_bases(c, pick, cut.get, lambda k: f"item {k} of tensor {owner.get(k)!r}"), owner.get))

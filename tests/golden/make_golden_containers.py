@@ -10,8 +10,9 @@ it uses only public names of `container`, so it runs unchanged on every commit t
     python tests/golden/make_golden_containers.py --gpu      # the GPU section, added to the file's CPU section
 
 The CPU section: header bytes and refusals of the four writers, the four parsers on damaged blobs, the calls that return
-without a GPU.  The GPU section, per case: SHA-256 and length of every blob and, per public call, the ordered names of the
-rcx.Context methods and module device calls it made.  tests/test_container_parity_cpu.py and
+without a GPU, the rules of "auto" on small tables, the public names.  The GPU section, per case: SHA-256 and length of every
+blob and, per public call, the ordered names of the rcx.Context methods and module device calls it made ("traces") and of its
+uploads and downloads ("copies").  tests/test_container_parity_cpu.py and
 tests/test_gpu_container_parity.py replay them.
 """
 import argparse

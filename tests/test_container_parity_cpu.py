@@ -46,7 +46,7 @@ def test_the_fixture_covers_what_it_should(golden):
         assert cuts == list(range(len(cuts))) and len(cuts) > fixed + 8 and "one byte more" in whats and len(blob) >= len(cuts) - 1, name
 
 
-@pytest.mark.parametrize("section", ("constants", "coded_size", "pick_predictor", "errors", "headers", "directory", "no_gpu"))
+@pytest.mark.parametrize("section", ("constants", "coded_size", "pick_predictor", "errors", "headers", "directory", "no_gpu", "decisions", "names"))
 def test_section_is_the_recorded_one(golden, replay, section):
     want, got = golden["sections"][section], replay[section]
     if isinstance(want, dict):
@@ -69,7 +69,10 @@ def test_container_re_exports_the_layouts():
     names = ("MAGIC", "VERSION", "VERSION_CRC", "VERSION_STORED", "FLAG_BLKSORT", "FLAG_CRC32", "FLAG_STORED", "ITEM_MAGIC", "ITEM_VERSION", "MAX_ITEM",
              "TYPED_MAGIC", "TYPED_VERSION", "TYPED_VERSION_PRED", "TYPED_VERSION_STORED", "PREDICTORS", "WIDTHS", "TYPED_ITEMS_MAGIC", "TYPED_ITEMS_VERSION",
              "ITEM_WIDTHS", "coded_size", "ContainerError", "ChecksumError", "header_bytes", "parse", "item_header_bytes", "parse_items", "typed_header_bytes",
-             "parse_typed", "typed_items_header_bytes", "parse_typed_items", "tensor_directory_bytes", "parse_tensor_directory")
+             "parse_typed", "typed_items_header_bytes", "parse_typed_items", "tensor_directory_bytes", "parse_tensor_directory",
+             "DELTA_MAGIC", "DELTA_VERSION", "DELTA_FLAG_BASE_CRC", "BASE_OPS", "BaseMismatchError", "delta_header_bytes", "parse_delta",
+             "DELTA_ITEMS_MAGIC", "DELTA_ITEMS_VERSION", "DELTA_ITEMS_FLAG_BASE_CRC", "BASE_OP_NONE", "BaseItemMismatchError", "delta_items_header_bytes",
+             "parse_delta_items", "TYPED_ITEMS_VERSION_STORED", "block_lengths")
     for name in names:
         assert getattr(container, name) is getattr(layout, name), name
     assert stored.block_lengths is layout.block_lengths and list(stored.block_lengths(40, 16)) == [16, 16, 8] and len(stored.block_lengths(0, 16)) == 0

@@ -15,7 +15,7 @@ section 21 quotes profiles/r20_typed_picks_rate.jsonl.
      and predictor: the walking median is no more than the host-planned kernels' median plus their min-max spread.
   C  max_pick = 200 000 with *d_count = 100, 1000, 10 000, 200 000 of A's entries: GPU time of the call.  Report only.
   D  container.open_typed_items(...).decode_into on A's items packed as RCXJ (adaptive coder), eager and as a graph replay,
-     beside unpack_typed_items' device path for the same picks without the download (container._unpack_typed_items_device: host
+     beside unpack_typed_items' device path for the same picks without the download (container._unpack_items_device: host
      plan, uploads, decode, join).  That path runs this build's library -- the container module binds one librcx a process --
      whose host-planned kernels tools/diag/kernel_diff.py shows unchanged from the parent.  Report only.
 
@@ -224,7 +224,7 @@ def part_d(w, args, emit):
         eager()
     c = container.parse_typed_items(blob)
     fns = {"graph_replay": g.replay, "eager": eager}
-    fns["unpack_typed_items_device_path_this_build"] = lambda: container._unpack_typed_items_device(ctx, c, pick, False)
+    fns["unpack_typed_items_device_path_this_build"] = lambda: container._unpack_items_device(ctx, c, pick, False)
     t = alternated(fns, args.repeats)
     ctx.sync_status()
     assert torch.equal(out[: want.numel()], want)
