@@ -212,26 +212,57 @@ struct Tree {
 // Sum of the first p entries of a group and the p-th entry, p in 0..3.  Written with 0/1 factors instead of
 // compares: (p > 0) = min(p, 1), (p > 1) = p >> 1, (p > 2) = p & (p >> 1), and the counts are < 2^24, so each
 // term is one v_mad_u32_u24 -- no compare whose mask the next instruction has to wait two slots for.
-RCX_DEV u32 rcx_min1(u32 p)
-{
-#if defined(RCX_HOST_SIM)
-    return p < 1u ? p : 1u;
-#else
-    u32 m; // opaque to the compiler, which would turn "x * min(p, 1)" back into compare + select
-    asm("v_min_u32 %0, 1, %1" : "=v"(m) : "v"(p));
-    return m;
-#endif
-}
+// The sums are chains: the first p entries as x*m1, + y*m2, + z*m3 (a multiply and two multiply-adds), the first p + 1 as
+// x + y*m1 + z*m2 + w*m3 (three multiply-adds onto x); the count of entry p is their difference.  Each is written as ONE
+// instruction sequence, v_min_u32 included: left to the compiler, a sum of such products is multiplies and a v_add3_u32,
+// one instruction more per group, and between separate asm statements that hand a register on it puts an s_nop.
 RCX_DEV u32 rcx_pre4(const U4& g, u32 p)
 {
-    const u32 m1 = rcx_min1(p), m2 = p >> 1, m3 = p & m2;
-    return rcx_mul24(g.x, m1) + rcx_mul24(g.y, m2) + rcx_mul24(g.z, m3);
+    const u32 m2 = p >> 1, m3 = p & m2;
+#if defined(RCX_HOST_SIM)
+    const u32 m1 = p < 1u ? p : 1u;
+    return rcx_mul24(g.z, m3) + (rcx_mul24(g.y, m2) + rcx_mul24(g.x, m1));
+#else
+    u32 sum, m1;
+    asm("v_min_u32 %[m1], 1, %[p]\n\t"
+        "v_mul_u32_u24 %[s], %[x], %[m1]\n\t"
+        "v_mad_u32_u24 %[s], %[y], %[m2], %[s]\n\t"
+        "v_mad_u32_u24 %[s], %[z], %[m3], %[s]"
+        : [s] "=&v"(sum), [m1] "=&v"(m1)
+        : [p] "v"(p), [m2] "v"(m2), [m3] "v"(m3), [x] "v"(g.x), [y] "v"(g.y), [z] "v"(g.z));
+    return sum;
+#endif
+}
+// Both of one group, for the leaf level: returns the sum of the first p, `count` = entry p.  The two chains share the
+// factors and run interleaved: a multiply, five multiply-adds and a subtraction.
+RCX_DEV u32 rcx_pre4_sel4(const U4& g, u32 p, u32& count)
+{
+    const u32 m2 = p >> 1, m3 = p & m2;
+#if defined(RCX_HOST_SIM)
+    const u32 m1 = p < 1u ? p : 1u;
+    const u32 sum = rcx_mul24(g.z, m3) + (rcx_mul24(g.y, m2) + rcx_mul24(g.x, m1));
+    count = rcx_mul24(g.w, m3) + (rcx_mul24(g.z, m2) + (rcx_mul24(g.y, m1) + g.x)) - sum;
+    return sum;
+#else
+    u32 sum, m1;
+    asm("v_min_u32 %[m1], 1, %[p]\n\t"
+        "v_mul_u32_u24 %[s], %[x], %[m1]\n\t"
+        "v_mad_u32_u24 %[f], %[y], %[m1], %[x]\n\t"
+        "v_mad_u32_u24 %[s], %[y], %[m2], %[s]\n\t"
+        "v_mad_u32_u24 %[f], %[z], %[m2], %[f]\n\t"
+        "v_mad_u32_u24 %[s], %[z], %[m3], %[s]\n\t"
+        "v_mad_u32_u24 %[f], %[w], %[m3], %[f]\n\t"
+        "v_sub_u32 %[f], %[f], %[s]"
+        : [s] "=&v"(sum), [f] "=&v"(count), [m1] "=&v"(m1)
+        : [p] "v"(p), [m2] "v"(m2), [m3] "v"(m3), [x] "v"(g.x), [y] "v"(g.y), [z] "v"(g.z), [w] "v"(g.w));
+    return sum;
+#endif
 }
 RCX_DEV u32 rcx_sel4(const U4& g, u32 p)
 {
-    const u32 m1 = rcx_min1(p), m2 = p >> 1, m3 = p & m2;
-    // (sum of the first p + 1) - (sum of the first p)
-    return g.x + rcx_mul24(g.y, m1) + rcx_mul24(g.z, m2) + rcx_mul24(g.w, m3) - (rcx_mul24(g.x, m1) + rcx_mul24(g.y, m2) + rcx_mul24(g.z, m3));
+    u32 count;
+    (void)rcx_pre4_sel4(g, p, count);
+    return count;
 }
 
 // Add `extra` into the `count` payload bytes already stored, from the newest backwards
@@ -429,8 +460,8 @@ struct EncLane {
         const U4 g2 = tree.group(RCX_G_L2 + (c >> 6));
         const U4 g1 = tree.group(RCX_G_L1 + (c >> 4));
         const U4 g0 = tree.group(RCX_G_L0 + (c >> 2));
-        const u32 cum = rcx_pre4(g3, c >> 6) + rcx_pre4(g2, (c >> 4) & 3) + rcx_pre4(g1, (c >> 2) & 3) + rcx_pre4(g0, c & 3);
-        const u32 f = rcx_sel4(g0, c & 3);
+        u32 f;
+        const u32 cum = rcx_pre4(g3, c >> 6) + rcx_pre4(g2, (c >> 4) & 3) + rcx_pre4(g1, (c >> 2) & 3) + rcx_pre4_sel4(g0, c & 3, f);
         code<TRACK>(cum, f, k, index);
         tree.update(c); // :712
     }
@@ -444,8 +475,8 @@ struct EncLane {
         const U4 g2 = tree.group(RCX_G_L2 + (c >> 6));
         const U4 g1 = tree.group(RCX_G_L1 + (c >> 4));
         const U4 g0 = tree.group(RCX_G_L0 + (c >> 2));
-        const u32 cum = rcx_pre4(g3, c >> 6) + rcx_pre4(g2, (c >> 4) & 3) + rcx_pre4(g1, (c >> 2) & 3) + rcx_pre4(g0, c & 3);
-        const u32 f = rcx_sel4(g0, c & 3);
+        u32 f;
+        const u32 cum = rcx_pre4(g3, c >> 6) + rcx_pre4(g2, (c >> 4) & 3) + rcx_pre4(g1, (c >> 2) & 3) + rcx_pre4_sel4(g0, c & 3, f);
         const u32 rec = arith_t(cum, f, range / total); // :703
         if (TRACK) track(index, rec & 1u, rec & 0xFFFFFF00u, rec & 0x18u);
         emit(rec);

@@ -552,10 +552,16 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                     else ws3[(s - 1) * RCX_LANES] = held, ws3[s * RCX_LANES] = cum3;
                 }
             } else {
+                // The symbol's count is READ (a ds_read_b32 at the address the bump computes anyway), directly in front of its own
+                // bump: LDS serves a wave's operations in order, so it holds every earlier symbol's bump and not its own.  From
+                // the group it is (sum of the first p + 1) - (sum of the first p), four instructions more (rcx_pre4_sel4).  Past
+                // a short block's end the read runs on, as the group read does; its value is not used there.
+                u32 fq[RCX_MC_CHUNK];
 #define RCX_M0_ISSUE(T)                                                       \
     {                                                                         \
         const u32 c_ = rcx_byte_of(piece, (T));                               \
         ga[T] = tree.group(RCX_G_L0 + (c_ >> 2));                             \
+        fq[T] = *tree.at(RCX_G_L0 + (c_ >> 2), c_ & 3);                       \
         if (FULL || i0 + (T) < len) tree.bump(RCX_G_L0 + (c_ >> 2), c_ & 3);  \
     }
 #pragma unroll
@@ -564,7 +570,7 @@ __device__ __forceinline__ void rcx_mc5_pipeline(u32 wave, u32 lane, u32 len, u3
                 for (u32 s = 0; s < RCX_MC_CHUNK; ++s) {
                     if (s + RCX_MODEL_AHEAD < RCX_MC_CHUNK) RCX_M0_ISSUE(s + RCX_MODEL_AHEAD);
                     const u32 cc = rcx_byte_of(piece, s);
-                    const u32 sum0 = rcx_pre4(ga[s], cc & 3), f0 = rcx_sel4(ga[s], cc & 3);
+                    const u32 sum0 = rcx_pre4(ga[s], cc & 3), f0 = fq[s];
                     if (FULL) { // (pairs: fields 2 and 3 are one aligned qword, and the compiler makes the four stores ONE ds_write2st64_b64)
                         if ((s & 1u) == 0) held = sum0, held_f = f0;
                         else {
