@@ -90,6 +90,10 @@ open_items(blob) (include/rcx_picks.h, cpprcoder_amd/picks.py) is for a reader t
 stored item container, is parsed once and its payload, stream table, stored flags and lengths are put on the device; decode_into
 takes picks, destinations and their count from device tensors, only enqueues, and can be captured in a graph and replayed
 against tables that device code rewrites.  A bad entry is skipped and latched (sync_status), every other entry decodes.
+open_typed_items(blob) does the same for an RCXJ container with the typed join behind the decode (include/rcx_typed_picks.h),
+and open_delta_items(blob, bases) (cpprcoder_amd/delta_open.py, reached as container.open_delta_items) for an RCXK container with
+the join against the bases (include/rcx_base_picks.h, cpprcoder_amd/base_picks.py): the bases are gathered into one device buffer once, the same object given for many items is one
+span, and the prefix's CRC-32 guard is checked at open.
 """
 import collections
 import contextlib
@@ -929,6 +933,16 @@ class OpenTypedItems(_Opened):
         items have at most its max_bytes between them (else nothing is joined and RCX_E_CAPACITY is latched).  Enqueues only, all of
         it on `stream` (a torch stream; None: the current one).  An entry that names no item is skipped and latched; entries at or past
         the count may hold anything.  Failures are the context's: sync_status(), its position through pick_of."""
+        t = self._expand(d_pick, d_dst_at, d_count, max_pick, stream)
+        self._picks.decode_device(self.ctx, self.d_payload, self.payload_size, self.d_offsets, t["sub_stream"], t["sub_at"], t["sub_len"], t["count"], self.d_stage,
+                                  self.max_sub_len, max_pick=t["slots"], stored=self.d_stored, coder=self.coder, stream=stream, dst_cap=self.max_bytes)
+        self._join.join_device(self.ctx, self.d_stage, t["from_at"], t["to_at"], t["item_len"], t["widths"], t["preds"], t["count"], d_dst,
+                               self.max_bytes, max_pick=t["slots"], stream=stream, src_cap=self.max_bytes)
+
+    def _expand(self, d_pick, d_dst_at, d_count, max_pick, stream, per_item=()):
+        """The lookup of decode_into, by torch ops on `stream`: the picks' items, lengths and widths, and both calls' tables of
+        SLOTS entries a pick -> dict.  per_item: (name, an int64 device table with an entry per item, what a pick that names no
+        item and the slots behind the first get, the dtype) -> that table's entry of the pick in its first slot, under `name`."""
         import torch
         if self.d_stage is None:
             raise ContainerError("reserve(max_pick, max_bytes) comes first: it makes the staging buffer")
@@ -963,11 +977,13 @@ class OpenTypedItems(_Opened):
             item_len = (length.unsqueeze(1) * first).contiguous()
             widths = (w.unsqueeze(1) * first + (1 - first)).to(torch.uint8).contiguous()
             preds = (torch.where(inside, self.d_preds[item], zero).unsqueeze(1) * first).to(torch.uint8).contiguous()
-            self._picks.decode_device(self.ctx, self.d_payload, self.payload_size, self.d_offsets, sub_stream.contiguous().view(-1), sub_at.contiguous().view(-1),
-                                      sub_len.contiguous().view(-1), count, self.d_stage, self.max_sub_len, max_pick=S * max_pick, stored=self.d_stored,
-                                      coder=self.coder, stream=stream, dst_cap=self.max_bytes)
-            self._join.join_device(self.ctx, self.d_stage, from_at.view(-1), to_at.view(-1), item_len.view(-1), widths.view(-1), preds.view(-1), count, d_dst,
-                                   self.max_bytes, max_pick=S * max_pick, stream=stream, src_cap=self.max_bytes)
+            out = {"slots": S * max_pick, "count": count, "sub_stream": sub_stream.contiguous().view(-1), "sub_at": sub_at.contiguous().view(-1),
+                   "sub_len": sub_len.contiguous().view(-1), "from_at": from_at.view(-1), "to_at": to_at.view(-1), "item_len": item_len.view(-1),
+                   "widths": widths.view(-1), "preds": preds.view(-1)}
+            for name, table, missing, dtype in per_item:
+                mine = torch.where(inside, table[item], torch.full_like(p, missing)).unsqueeze(1)
+                out[name] = (mine * first + missing * (1 - first)).to(dtype).contiguous().view(-1)
+            return out
 
     def verify(self, pick) -> None:
         """After decode_into whose picks were `pick` (a HOST table, all of them valid) and a synchronisation: the CRC-32 check of a
@@ -986,6 +1002,15 @@ def open_typed_items(blob, ctx=None) -> OpenTypedItems:
     once and put on the device -> OpenTypedItems, whose decode_into takes picks, destinations and their count from device memory,
     decodes and joins, and can be captured in a graph.  ctx=None: a context of its own, closed by close()."""
     return OpenTypedItems(parse_typed_items(blob), ctx)
+
+
+def __getattr__(name):
+    """container.open_delta_items and container.OpenDeltaItems: the RCXK container opened on the device lives in delta_open.py
+    (it builds on OpenTypedItems above) and is looked up there when it is asked for."""
+    if name in ("open_delta_items", "OpenDeltaItems"):
+        from . import delta_open
+        return getattr(delta_open, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 # ---- tensors with names, on top of the typed item container ---------------------------------------------------------------

@@ -32,6 +32,20 @@
 struct RcxBaseItemsTables {
     RcxTypedTables t; // the base set's classes, ufirst, at, len, rowtab (no scan list)
     const u64* bat;   // [nent] byte offset of the entry's span in the base
+    static constexpr bool PICKS = false; // (no member: the tables a kernel is handed stay as they are)
+};
+
+// The base set as the planner of rcx_base_picks.hpp leaves it in device memory: an entry is read at from[k] of the source and
+// bat[k] of the base and written at to[k].  rcx_base_items_step and rcx_base_items_rest take either kind (TB).
+struct RcxBasePickTables {
+    const RcxTypedClasses* classes;
+    const u64* ufirst; // [nent + 1]
+    const u64* from;   // [nent] byte offset of the entry in src
+    const u64* to;     // [nent] ... in dst
+    const u64* bat;    // [nent] ... of its span in the base
+    const u32* len;
+    const u32* rowtab;
+    static constexpr bool PICKS = true;
 };
 
 struct RcxBaseItemsPlan {
@@ -206,16 +220,21 @@ __device__ __forceinline__ void rcx_base_items_dispatch(u32 c, F f)
     }
 }
 
+// the classes, ufirst, len and rowtab of either kind of tables
+__device__ __forceinline__ const RcxTypedTables& rcx_base_items_set(const RcxBaseItemsTables& bt) { return bt.t; }
+__device__ __forceinline__ const RcxBasePickTables& rcx_base_items_set(const RcxBasePickTables& bt) { return bt; }
+
 // One step of a workgroup in a class of width W and op OP: rows row0 .. row0 + K - 1 of rowtab, units base + j * 256 + tid of
 // the class's `total`.  The K rows' entries are found side by side as in rcx_typed_step; then all loads of source (or
 // planes) and base, then the arithmetic in rcx_base_step's order, then the stores.  A width-1 entry is a flat run of units.
 // GUARD = false: every unit exists; GUARD = true: the class's last step.
-template <u32 W, bool JOIN, u32 OP, bool GUARD>
-__device__ __forceinline__ void rcx_base_items_step(const u8* __restrict__ src, const u8* __restrict__ ref, u8* __restrict__ dst, const RcxBaseItemsTables& bt,
+template <u32 W, bool JOIN, u32 OP, bool GUARD, class TB>
+__device__ __forceinline__ void rcx_base_items_step(const u8* __restrict__ src, const u8* __restrict__ ref, u8* __restrict__ dst, const TB& bt,
                                                     u64 ubase, u64 base, u64 total, u32 row0, u32 tid)
 {
+    static_assert(!TB::PICKS || JOIN, "device-planned tables are the join's");
     constexpr u32 K = RCX_BASE_ROWS(W);
-    const RcxTypedTables& t = bt.t;
+    const auto& t = rcx_base_items_set(bt);
     u32 w[K][4 * W], b[K][4 * W];
     u64 g[K];
     u32 lo[K], hi[K];
@@ -243,10 +262,17 @@ __device__ __forceinline__ void rcx_base_items_step(const u8* __restrict__ src, 
 #pragma unroll
     for (u32 j = 0; j < K; ++j) {
         const u32 u = (u32)(g[j] - t.ufirst[lo[j]]);
-        const u64 at = t.at[lo[j]];
-        m[j] = t.len[lo[j]] / W;
-        elements[j] = at + (u64)u * (16u * W);
-        planes[j] = at + 16ull * u; // plane p: + p * m
+        if constexpr (TB::PICKS) { // (join: the planes are read at `from`, the elements written at `to`)
+            const u64 from = t.from[lo[j]], to = t.to[lo[j]];
+            m[j] = t.len[lo[j]] / W;
+            elements[j] = to + (u64)u * (16u * W);
+            planes[j] = from + 16ull * u;
+        } else {
+            const u64 at = t.at[lo[j]];
+            m[j] = t.len[lo[j]] / W;
+            elements[j] = at + (u64)u * (16u * W);
+            planes[j] = at + 16ull * u; // plane p: + p * m
+        }
         theirs[j] = bt.bat[lo[j]] + (u64)u * (16u * W);
     }
 #pragma unroll
@@ -283,35 +309,59 @@ __device__ __forceinline__ void rcx_base_items_step(const u8* __restrict__ src, 
 
 // Rest lane r of a class of width W: byte r % 17W of the class's entry r / 17W, if it has one.  A byte of an element: the
 // lane makes the whole element and writes its one byte of it; a tail byte keeps the source's value.
-template <u32 W, bool JOIN, u32 OP>
-__device__ __forceinline__ void rcx_base_items_rest(const u8* __restrict__ src, const u8* __restrict__ ref, u8* __restrict__ dst, const RcxBaseItemsTables& bt,
+template <u32 W, bool JOIN, u32 OP, class TB>
+__device__ __forceinline__ void rcx_base_items_rest(const u8* __restrict__ src, const u8* __restrict__ ref, u8* __restrict__ dst, const TB& bt,
                                                     u32 first, u32 count, u64 r)
 {
     constexpr u32 PER = 17u * W;
     const u64 k = r / PER;
     if (k >= count) return;
-    const u32 j = (u32)(r - k * PER), len = bt.t.len[first + k], m = len / W;
-    const u64 at = bt.t.at[first + k];
-    u32 e, p;
-    const u32 kind = rcx_typed_rest_of<W>(len, j, e, p);
-    if (kind == 1) {
-        const u64 element = at + (u64)e * W, theirs = bt.bat[first + k] + (u64)e * W;
-        if constexpr (W == 1) {
-            dst[element] = (u8)rcx_base_elem<1, OP, JOIN>(src[element], ref[theirs]);
-        } else {
-            typedef typename RcxElem<W>::T T;
-            T x = 0;
-            if (JOIN) {
-#pragma unroll
-                for (u32 q = 0; q < W; ++q) x |= (T)src[at + (u64)q * m + e] << (8u * q);
+    if constexpr (TB::PICKS) { // (join only: the entry is read at `from` and written at `to`)
+        static_assert(!TB::PICKS || JOIN, "device-planned tables are the join's");
+        const u32 j = (u32)(r - k * PER), len = bt.len[first + k], m = len / W;
+        const u64 from = bt.from[first + k], to = bt.to[first + k];
+        u32 e, p;
+        const u32 kind = rcx_typed_rest_of<W>(len, j, e, p);
+        if (kind == 1) {
+            const u64 theirs = bt.bat[first + k] + (u64)e * W;
+            if constexpr (W == 1) {
+                dst[to + e] = (u8)rcx_base_elem<1, OP, true>(src[from + e], ref[theirs]);
             } else {
-                x = rcx_load_elem<W>(src + element);
+                typedef typename RcxElem<W>::T T;
+                T x = 0;
+#pragma unroll
+                for (u32 q = 0; q < W; ++q) x |= (T)src[from + (u64)q * m + e] << (8u * q);
+                const u64 v = rcx_base_elem<W, OP, true>(x, rcx_load_elem<W>(ref + theirs));
+                dst[to + (u64)e * W + p] = (u8)(v >> (8u * p));
             }
-            const u64 v = rcx_base_elem<W, OP, JOIN>(x, rcx_load_elem<W>(ref + theirs));
-            dst[JOIN ? element + p : at + (u64)p * m + e] = (u8)(v >> (8u * p));
+        } else if (kind == 2) {
+            dst[to + e] = src[from + e];
         }
-    } else if (kind == 2) {
-        dst[at + e] = src[at + e];
+        return;
+    } else {
+        const u32 j = (u32)(r - k * PER), len = bt.t.len[first + k], m = len / W;
+        const u64 at = bt.t.at[first + k];
+        u32 e, p;
+        const u32 kind = rcx_typed_rest_of<W>(len, j, e, p);
+        if (kind == 1) {
+            const u64 element = at + (u64)e * W, theirs = bt.bat[first + k] + (u64)e * W;
+            if constexpr (W == 1) {
+                dst[element] = (u8)rcx_base_elem<1, OP, JOIN>(src[element], ref[theirs]);
+            } else {
+                typedef typename RcxElem<W>::T T;
+                T x = 0;
+                if (JOIN) {
+#pragma unroll
+                    for (u32 q = 0; q < W; ++q) x |= (T)src[at + (u64)q * m + e] << (8u * q);
+                } else {
+                    x = rcx_load_elem<W>(src + element);
+                }
+                const u64 v = rcx_base_elem<W, OP, JOIN>(x, rcx_load_elem<W>(ref + theirs));
+                dst[JOIN ? element + p : at + (u64)p * m + e] = (u8)(v >> (8u * p));
+            }
+        } else if (kind == 2) {
+            dst[at + e] = src[at + e];
+        }
     }
 }
 
