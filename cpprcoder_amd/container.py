@@ -94,6 +94,12 @@ open_typed_items(blob) does the same for an RCXJ container with the typed join b
 and open_delta_items(blob, bases) (cpprcoder_amd/delta_open.py, reached as container.open_delta_items) for an RCXK container with
 the join against the bases (include/rcx_base_picks.h, cpprcoder_amd/base_picks.py): the bases are gathered into one device buffer once, the same object given for many items is one
 span, and the prefix's CRC-32 guard is checked at open.
+
+pack_items_device(ctx, d_src, d_src_at, d_src_len, d_count, max_items, max_len, max_bytes) (include/rcx_encode_picks.h;
+cpprcoder_amd/encode_picks.py, reached as container.pack_items_device) is the way in for a writer that picks on the GPU: the items'
+positions, lengths and count are device tensors, the call enqueues the encode and returns a PackedItems over the device-resident
+streams without a download or a synchronisation; its decode_into is open_items' decode_into, its to_bytes() the RCXI file that
+pack_items writes for the same items (no checksums).
 """
 import collections
 import contextlib
@@ -1006,10 +1012,14 @@ def open_typed_items(blob, ctx=None) -> OpenTypedItems:
 
 def __getattr__(name):
     """container.open_delta_items and container.OpenDeltaItems: the RCXK container opened on the device lives in delta_open.py
-    (it builds on OpenTypedItems above) and is looked up there when it is asked for."""
+    (it builds on OpenTypedItems above) and is looked up there when it is asked for.  container.pack_items_device and
+    container.PackedItems -- items that device code chose, encoded where they lie -- live in encode_picks.py in the same way."""
     if name in ("open_delta_items", "OpenDeltaItems"):
         from . import delta_open
         return getattr(delta_open, name)
+    if name in ("pack_items_device", "PackedItems"):
+        from . import encode_picks
+        return getattr(encode_picks, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(64) void rcx_enc_adaptive_k(const u8* __restrict__ 
     // second pass behind rcx_enc_mc5_k: only the blocks it marked (a carry through more output bytes than
     // it keeps in LDS: none on ordinary data)
     RCX_ENTRY_ONLY(g, blk, nblocks, n, block, only);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
 
     Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
     tree.reset();

@@ -8,7 +8,10 @@
 // table pointers, like sizes / redo / starts / models, are already advanced to the class's first entry, so a kernel
 // indexes all of them by `blk` as before.  RcxPicks (rcx_decode_picks_device, include/rcx_picks.h) is the item geometry
 // whose tables a kernel planned (rcx_picks.hpp): the launch is shaped by the most entries there can be, and how many of the
-// tables' entries are meant is a word in device memory that every wave reads when it opens (`counted`).
+// tables' entries are meant is a word in device memory that every wave reads when it opens (`counted`).  RcxEncPicks
+// (rcx_encode_picks_device, include/rcx_encode_picks.h) is the counted geometry of the encoders (`planned`): the work order
+// is laid out in UNITS of 64 entries, every length class begins a unit, and the stride and the base of the scratch slots
+// are the unit's -- one launch covers all classes, and its shape follows the most entries there can be.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,11 +20,13 @@
 struct RcxBlocks {
     static constexpr bool items = false;
     static constexpr bool counted = false;
+    static constexpr bool planned = false;
 };
 
 struct RcxItems {
     static constexpr bool items = true;
     static constexpr bool counted = false;
+    static constexpr bool planned = false;
     const u64* at;     // byte offset of the entry's bytes in d_src (encode) / d_dst (decode)
     const u32* len;    // its length, 1 .. RCX_MAX_BLOCK (an item of length 0 has no entry)
     const u32* id;     // what a failure reports: the item (encode, also its place in the offsets table), the pick position (decode)
@@ -34,6 +39,23 @@ struct RcxItems {
 struct RcxPicks : RcxItems {
     static constexpr bool counted = true;
     const u32* nlive;
+};
+
+// The encoders only.  Work entries 0 .. *nlive - 1 are laid out (a multiple of 64); an entry of length 0 among them is a
+// HOLE, the padding behind a class's last entry: it is not live and has no slot.  Entries 64 u .. 64 u + 63 have their
+// slots at slots + unit[u].base + (entry & 63) * unit[u].stride.  Every encoder's group of entries (a workgroup's
+// lanes_used, a wave's 64, an octet wave's 8) divides 64 and begins on a multiple of itself, so a group lies in one unit
+// and its stride is wave-uniform.
+struct RcxEncUnit {
+    u64 base;   // bytes into the slots
+    u32 stride; // rcx_block_bound_for(coder, the class's upper length)
+    u32 spare;
+};
+struct RcxEncPicks : RcxItems {
+    static constexpr bool counted = true;
+    static constexpr bool planned = true;
+    const u32* nlive;
+    const RcxEncUnit* unit;
 };
 
 // Where entry `blk` lies.  A lane without an entry has length 0 and the position of the launch's first entry -- with
@@ -51,13 +73,19 @@ __device__ __forceinline__ void rcx_where(const RcxItems& g, bool live, u64 blk,
 // marked (ONLY[blk] != 0), and a wave none of whose lanes has an entry returns.
 // With a counted geometry (RcxPicks) `live` also asks the device's count, and a wave none of whose lanes has an entry
 // returns: the launch is shaped for the most entries there can be, and no decoder has a barrier.  (`if constexpr` on a
-// dependent condition: the other geometries' kernels are instantiated without these lines.)
+// dependent condition: the other geometries' kernels are instantiated without these lines.)  With a planned geometry
+// (RcxEncPicks) a hole is not live either; the multi-wave encoders have barriers, but every wave of their workgroups
+// carries the same entries, so the workgroup returns as a whole or not at all.
 // Macros, not functions: a function is optimised on its own before it is inlined into the kernel, and what arrives
 // there differs enough from these lines written in place that 18 of the 50 kernels came out with different
 // instructions, down into their symbol loops (tools/diag/kernel_diff.py).
 #define RCX_ENTRY_COUNTED(GEOM, BLK)                                                                  \
     if constexpr (decltype(GEOM)::counted) {                                                          \
         live = live && (BLK) < (u64)(GEOM).nlive[0];                                                  \
+        if (!__any(live)) return;                                                                     \
+    }                                                                                                 \
+    if constexpr (decltype(GEOM)::planned) {                                                          \
+        live = live && (GEOM).len[BLK] != 0;                                                          \
         if (!__any(live)) return;                                                                     \
     }
 #define RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)                                                          \
@@ -76,6 +104,15 @@ __device__ __forceinline__ void rcx_where(const RcxItems& g, bool live, u64 blk,
         if (!__any(live)) return;                                                                     \
     }                                                                                                 \
     RCX_ENTRY_WHERE(GEOM, BLK, N, BLOCK)
+
+// Behind RCX_ENTRY in an encoder: with a planned geometry the kernel's SLOTS and SLOT (its parameters, which it goes on
+// to use as slots + entry * slot) become those of the unit of the wave's first lane, whose entry the launch always has.
+#define RCX_ENTRY_SLOTS(GEOM, BLK, SLOTS, SLOT)                                                       \
+    if constexpr (decltype(GEOM)::planned) {                                                          \
+        const u32 unit_ = __builtin_amdgcn_readfirstlane((u32)((BLK) >> 6));                          \
+        SLOT = (GEOM).unit[unit_].stride;                                                             \
+        SLOTS += (GEOM).unit[unit_].base - (u64)unit_ * 64u * (SLOT);                                 \
+    }
 
 // The fast paths' condition (16 bytes at a go, no per-symbol length test), behind RCX_ENTRY: every lane of the wave has
 // a whole block, blocks are multiples of 16 bytes and P, the buffer the blocks lie in, is 16-byte aligned.  Never with

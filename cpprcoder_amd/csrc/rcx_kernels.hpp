@@ -99,6 +99,10 @@ __global__ __launch_bounds__(256) void rcx_scatter_k(const u8* __restrict__ slot
                                                      const u32* __restrict__ starts, const G g = G())
 {
     const u64 blk = blockIdx.x;
+    if constexpr (G::planned) { // the launch is shaped for the most entries there can be: behind the laid-out ones, or a hole
+        if (blk >= (u64)g.nlive[0] || g.len[blk] == 0) return;
+        RCX_ENTRY_SLOTS(g, blk, slots, slot);
+    }
     const u32 size = sizes[blk];
     const u64 off = offsets[rcx_id(g, blk)]; // (the table is in the caller's order, the slots in work order)
     if (off + size > dst_cap) return; // flagged by the scan

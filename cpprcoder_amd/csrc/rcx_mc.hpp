@@ -606,6 +606,7 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     const bool in_use = lane < lanes_used;
     const u64 blk = in_use ? (u64)blockIdx.x * lanes_used + lane : nblocks;
     RCX_ENTRY(g, blk, nblocks, n, block);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
 
     Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
     u32* ring = reinterpret_cast<u32*>(lds + RCX_MC5_TREE_U4); // (no divisor staging behind the tree: rcx_mc5_pipeline)

@@ -179,6 +179,7 @@ __global__ __launch_bounds__(256) void rcx_enc_rans_k(const u8* __restrict__ src
     const u32 j = lane & 7u, oct = lane >> 3;
     const u64 blk = ((u64)blockIdx.x * 4 + wave) * RCX_RANS_BLOCKS + oct;
     RCX_ENTRY(g, blk, nblocks, n, block);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
     u32* cum = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_RANS_ENC_LDS_DW;
     u32* table = cum + 264;
     u8* stage = reinterpret_cast<u8*>(table + 256);
@@ -658,6 +659,9 @@ __global__ __launch_bounds__(256) void rcx_rans_model_k(const u8* __restrict__ s
     const u64 blk = ((u64)blockIdx.x * 4 + wave) * RCX_RANS_BLOCKS + oct;
     if (blk >= nblocks) return; // (an octet leaves together)
     RCX_ENTRY(g, blk, nblocks, n, block);
+    if constexpr (G::planned) {
+        if (!live) return; // a hole (an octet leaves together)
+    }
     u32* cum = lds_all + (wave * RCX_RANS_BLOCKS + oct) * RCX_RANS_ENC_LDS_DW;
     u32* table = cum + 264;
     const u8* in = src + at;
@@ -702,6 +706,7 @@ __global__ __launch_bounds__(64 * RCX_RANS1_ENC_WAVES) void rcx_enc_rans1_k(cons
     const bool in_use = lane < lanes_used;
     const u64 blk = in_use ? ((u64)blockIdx.x * RCX_RANS1_ENC_WAVES + wave) * lanes_used + lane : nblocks;
     RCX_ENTRY(g, blk, nblocks, n, block);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
     RcxRansSym* table = rcx_rans1_lds + wave * 256u * lanes_used + (in_use ? lane : 0u);
     if (live) {
         const RcxRansSym* m = reinterpret_cast<const RcxRansSym*>(models + blk * RCX_RANS_MODEL_DW + 264);
@@ -912,6 +917,7 @@ __global__ __launch_bounds__(128) void rcx_enc_rans1w_k(const u8* __restrict__ s
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const u64 blk = (u64)blockIdx.x * 64u + lane;
     RCX_ENTRY(g, blk, nblocks, n, block);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
     const u8* in = src + at;
     RcxRansSym* table = table_all + lane; // entry s at table[64 s]
     if (live) {

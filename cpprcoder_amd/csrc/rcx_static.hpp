@@ -88,6 +88,7 @@ __global__ __launch_bounds__(64) void rcx_enc_static_k(const u8* __restrict__ sr
     const u64 blk = (u64)blockIdx.x * RCX_LANES + lane;
     // second pass behind rcx_enc_static3_k: only the blocks it marked (none, on ordinary data)
     RCX_ENTRY_ONLY(g, blk, nblocks, n, block, only);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
 
@@ -284,6 +285,7 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     const bool in_use = lane < lanes_used; // see rcx_enc_mc5_k
     const u64 blk = in_use ? (u64)blockIdx.x * lanes_used + lane : nblocks;
     RCX_ENTRY(g, blk, nblocks, n, block);
+    RCX_ENTRY_SLOTS(g, blk, slots, slot);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
     U4* ring = reinterpret_cast<U4*>(lds + RCX_STATIC_LDS_DW); // 16-byte aligned: RCX_STATIC_LDS_DW = 257 * 64 dwords
