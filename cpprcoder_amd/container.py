@@ -99,7 +99,11 @@ pack_items_device(ctx, d_src, d_src_at, d_src_len, d_count, max_items, max_len, 
 cpprcoder_amd/encode_picks.py, reached as container.pack_items_device) is the way in for a writer that picks on the GPU: the items'
 positions, lengths and count are device tensors, the call enqueues the encode and returns a PackedItems over the device-resident
 streams without a download or a synchronisation; its decode_into is open_items' decode_into, its to_bytes() the RCXI file that
-pack_items writes for the same items (no checksums).
+pack_items writes for the same items (no checksums).  pack_typed_items_device(ctx, d_src, d_src_at, d_len, d_widths, d_preds,
+d_count, max_items, max_len, max_bytes) (include/rcx_typed_split_picks.h; cpprcoder_amd/typed_split_picks.py, reached as
+container.pack_typed_items_device) is the same for typed items: the device-planned split into a staging buffer in front of that
+encode, a width and a predictor per item read on the device; its PackedTypedItems decodes and joins with open_typed_items'
+decode_into, and its to_bytes() is the RCXJ file that pack_typed_items writes for the same items (no checksums).
 """
 import collections
 import contextlib
@@ -1013,13 +1017,18 @@ def open_typed_items(blob, ctx=None) -> OpenTypedItems:
 def __getattr__(name):
     """container.open_delta_items and container.OpenDeltaItems: the RCXK container opened on the device lives in delta_open.py
     (it builds on OpenTypedItems above) and is looked up there when it is asked for.  container.pack_items_device and
-    container.PackedItems -- items that device code chose, encoded where they lie -- live in encode_picks.py in the same way."""
+    container.PackedItems -- items that device code chose, encoded where they lie -- live in encode_picks.py in the same way, and
+    container.pack_typed_items_device and container.PackedTypedItems -- typed items that device code chose, split and encoded where
+    they lie -- in typed_split_picks.py."""
     if name in ("open_delta_items", "OpenDeltaItems"):
         from . import delta_open
         return getattr(delta_open, name)
     if name in ("pack_items_device", "PackedItems"):
         from . import encode_picks
         return getattr(encode_picks, name)
+    if name in ("pack_typed_items_device", "PackedTypedItems"):
+        from . import typed_split_picks
+        return getattr(typed_split_picks, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -24,6 +24,7 @@
 #include "rcx_typed_picks_api.hpp" // the typed join per item planned on the device, capturable (include/rcx_typed_picks.h)
 #include "rcx_base_picks_api.hpp" // the base join per item planned on the device, capturable (include/rcx_base_picks.h)
 #include "rcx_encode_picks_api.hpp" // item encode planned on the device: every table in HBM, capturable (include/rcx_encode_picks.h)
+#include "rcx_typed_split_picks_api.hpp" // the typed split per item planned on the device, capturable (include/rcx_typed_split_picks.h)
 
 extern "C" {
 

@@ -399,14 +399,30 @@ __device__ __forceinline__ void rcx_typed_rest(const u8* __restrict__ src, u8* _
     if (k >= count) return;
     const u32 j = (u32)(r - k * PER), len = t.len[first + k], m = len / W;
     u64 at;
-    if constexpr (TB::PICKS) { // (join without a predictor only: the entry lies elsewhere in dst)
-        static_assert(!TB::PICKS || (JOIN && PRED == 0), "device-planned tables are the join's");
+    if constexpr (TB::PICKS) { // (the entry lies elsewhere in dst; join: without a predictor only)
+        static_assert(!TB::PICKS || !JOIN || PRED == 0, "a device-planned join with a predictor is the scan kernel's");
         at = t.from[first + k];
         const u64 to = t.to[first + k];
         u32 e, p;
         const u32 kind = rcx_typed_rest_of<W>(len, j, e, p);
-        if (kind == 1) dst[to + (u64)e * W + p] = src[at + (u64)p * m + e];
-        else if (kind == 2) dst[to + e] = src[at + e];
+        if constexpr (JOIN) {
+            if (kind == 1) dst[to + (u64)e * W + p] = src[at + (u64)p * m + e];
+            else if (kind == 2) dst[to + e] = src[at + e];
+        } else { // split: the element, or its difference against the one in front of it (0 in front of the entry), to its planes
+            if (kind == 1) {
+                if constexpr (PRED != 0) {
+                    typedef typename RcxElem<W>::T T;
+                    const u8* element = src + at + (u64)e * W;
+                    const T here = rcx_load_elem<W>(element), front = e ? rcx_load_elem<W>(element - W) : (T)0;
+                    const T d = (T)(here - front) & rcx_elem_mask<W>();
+                    dst[to + (u64)p * m + e] = (u8)((PRED == 2 ? rcx_zigzag<W>(d) : d) >> (8u * p));
+                } else {
+                    dst[to + (u64)p * m + e] = src[at + (u64)e * W + p];
+                }
+            } else if (kind == 2) {
+                dst[to + e] = src[at + e];
+            }
+        }
         return;
     } else {
         at = t.at[first + k];
@@ -433,7 +449,8 @@ __device__ __forceinline__ void rcx_typed_rest(const u8* __restrict__ src, u8* _
 // Split (every class), and join of the classes without a predictor.  A fixed grid loops over the steps, then over the
 // blocks of rest lanes; the class of a step or block is found on scalars and branched on once.
 // ===========================================================================
-// (rcx_typed_picks_items_k below repeats these two loops for the device-planned tables: a change here goes there too)
+// (rcx_typed_picks_items_k and rcx_typed_split_picks_k below repeat these two loops for the device-planned tables: a change
+// here goes to both of them too)
 template <bool JOIN>
 __global__ __launch_bounds__(RCX_PLANES_THREADS) void rcx_typed_items_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedTables t)
 {
@@ -467,11 +484,45 @@ __global__ __launch_bounds__(RCX_PLANES_THREADS) void rcx_typed_items_k(const u8
 // The same walk with the tables the device planned (rcx_typed_picks.hpp): join only, the classes without a predictor.  A
 // kernel of its own with the loops written out again, not a shared body: with the loops in a function that both kernels
 // inline, the compiler turned the loop tests of the kernel above round, and that kernel is to stay what it was.
+// (rcx_typed_split_picks_k below is the third copy, for the split: a change here goes there and above too.)
 // (four waves a SIMD, as rcx_typed_items_k<true> has by itself: the second position table costs registers, and at three
 // waves the kernel lost 6 % on large items)
 __global__ __launch_bounds__(RCX_PLANES_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void rcx_typed_picks_items_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedPickTables t)
 {
     constexpr bool JOIN = true;
+    const RcxTypedClasses* const cl = t.classes;
+    const u32 tid = threadIdx.x;
+    const u64 steps = cl->step_end[RCX_TYPED_CLASSES - 1];
+    for (u64 s = blockIdx.x; s < steps; s += gridDim.x) {
+        const u32 c = rcx_typed_class_of(cl->step_end, s);
+        const u64 local = s - (c ? cl->step_end[c - 1] : 0);
+        const u64 ubase = cl->ubase[c], total = cl->ubase[c + 1] - ubase;
+        const u32 rows = cl->row_first[c];
+        rcx_typed_dispatch<JOIN>(c, [&](auto w_, auto p_) {
+            constexpr u32 W = decltype(w_)::value, PRED = decltype(p_)::value, K = RCX_PLANES_U4 / W, STEP = K * RCX_TYPED_ROW;
+            const u64 base = local * STEP;
+            const u32 row0 = rows + (u32)(local * K);
+            if (base + STEP <= total) rcx_typed_step<W, JOIN, PRED, false>(src, dst, t, ubase, base, total, row0, tid);
+            else rcx_typed_step<W, JOIN, PRED, true>(src, dst, t, ubase, base, total, row0, tid);
+        });
+    }
+    const u64 blocks = cl->rest_end[RCX_TYPED_CLASSES - 1];
+    for (u64 b = blockIdx.x; b < blocks; b += gridDim.x) {
+        const u32 c = rcx_typed_class_of(cl->rest_end, b);
+        const u64 r = (b - (c ? cl->rest_end[c - 1] : 0)) * RCX_TYPED_ROW + tid;
+        const u32 first = cl->ent_first[c], count = cl->ent_first[c + 1] - first;
+        rcx_typed_dispatch<JOIN>(c, [&](auto w_, auto p_) {
+            rcx_typed_rest<decltype(w_)::value, JOIN, decltype(p_)::value>(src, dst, t, first, count, r);
+        });
+    }
+}
+
+// ... and the split over the tables the device planned (rcx_typed_split_picks.hpp): every class, with or without a predictor,
+// an entry read at from[k] and written at to[k]; the scan members of the tables are not looked at.  The two loops a third
+// time, for the reason above: a change in rcx_typed_items_k goes here and to rcx_typed_picks_items_k too.
+__global__ __launch_bounds__(RCX_PLANES_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void rcx_typed_split_picks_k(const u8* __restrict__ src, u8* __restrict__ dst, RcxTypedPickTables t)
+{
+    constexpr bool JOIN = false;
     const RcxTypedClasses* const cl = t.classes;
     const u32 tid = threadIdx.x;
     const u64 steps = cl->step_end[RCX_TYPED_CLASSES - 1];
