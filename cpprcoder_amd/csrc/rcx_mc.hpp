@@ -81,11 +81,21 @@ static __device__ unsigned long long rcx_stamp_out[16];
 #define RCX_OUT_RING_WORDS 64 /* per block: 256 bytes of output waiting in LDS */
 #define RCX_OUT_MARGIN 32     /* bytes kept back from the drain */
 #define RCX_MC5_OUT_DW (RCX_OUT_RING_WORDS * RCX_LANES + 3 * RCX_LANES)
+// The writer forms a ring word's LDS address as (running position bits & RCX_OUT_SLOT_MASK) | the lane's address in slot 0
+// (StagedWriter::emit): an OR, so the ring begins at a multiple of its own size in the workgroup's LDS.  Both kernels put
+// McOutput first in an array aligned to it (RCX_MC_OUTPUT_AT_DW).
+#define RCX_OUT_RING_BYTES (RCX_OUT_RING_WORDS * RCX_LANES * 4)
+#define RCX_OUT_SLOT_MASK ((RCX_OUT_RING_WORDS - 1u) * RCX_LANES * 4u) /* 0x3F00: slots are 256 bytes, bits 8-13 */
+#define RCX_MC_OUTPUT_AT_DW 0                                            /* where McOutput begins in either kernel's LDS array */
+#define RCX_MC_OUTPUT_DW (RCX_LANES + RCX_MC5_OUT_DW)                    /* ring, slot 64, final_low, pos, drained */
+static_assert(RCX_OUT_RING_BYTES == 16384 && RCX_OUT_SLOT_MASK == 0x3F00u, "the output ring: 64 slots of 256 bytes");
+static_assert((RCX_MC_OUTPUT_AT_DW * 4) % RCX_OUT_RING_BYTES == 0, "the output ring starts at a multiple of 16 KiB");
+static_assert(RCX_MC_OUTPUT_DW % 4 == 0, "what follows McOutput stays 16-byte aligned");
 // The level-3 wave's sums: a fifth value per symbol and lane, in a dword plane of its own beside the ring (the ring's record
 // stays the 16 bytes per lane that the arithmetic wave reads at once), double-buffered like it, behind the output rings.
 #define RCX_MC5_RING3_DW (2 * RCX_MC_CHUNK * RCX_LANES)
 #define RCX_MC5_TREE_U4 (RCX_GROUPS * RCX_LANES) /* the model's groups; no staged divisors behind them (RCX_LDS_U4 has 64) */
-#define RCX_MC5_LDS_U4 (RCX_MC5_TREE_U4 + RCX_MC_RING_U4 + RCX_MC5_RING2_DW / 4 + RCX_LANES / 4 + RCX_MC5_OUT_DW / 4 + RCX_MC5_RING3_DW / 4)
+#define RCX_MC5_LDS_U4 (RCX_MC_OUTPUT_DW / 4 + RCX_MC5_TREE_U4 + RCX_MC_RING_U4 + RCX_MC5_RING2_DW / 4 + RCX_MC5_RING3_DW / 4)
 
 struct __attribute__((packed, aligned(4))) RcxU4Unaligned {
     u32 x, y, z, w;
@@ -179,7 +189,11 @@ __device__ __forceinline__ u32 rcx_drain_piece(const u32* ring_lane, u8* payload
 // finish() takes the newest word from the window).
 struct StagedWriter {
     u64 acc;        // the newest 8 bytes of the payload as a number, newest byte lowest (before the stream: zeroes)
-    u32 pos8;       // 8 x the payload bytes produced so far (the reference's initial buffer_ = 0 is the first: EncLane)
+    // pos8 = 8 x the payload bytes produced so far (the reference's initial buffer_ = 0 is the first: EncLane), kept as the two
+    // values a symbol needs of it, each moved by the symbol's k8 with one instruction (u32 arithmetic, wrap-around and all):
+    u32 np;         // 0 - pos8: np & 24 is the shift that moves the window's end up to a word boundary
+    u32 q;          // (pos8 - 40) << 3: q & RCX_OUT_SLOT_MASK is the byte offset of the older word's slot in the ring,
+                    // ((pos - 1) / 4 - 1) mod 64 slots of 256 bytes (before the stream's fifth byte: slot 63, whose place is free)
     u32 pos;        // pos8 / 8 as of the last chunk_begins() / chunk_ends()
     u32 safe_from;  // bytes below this may have been drained (pos at the start of the chunk - RCX_OUT_MARGIN)
     u32 redo;
@@ -188,28 +202,30 @@ struct StagedWriter {
     __device__ __forceinline__ void begin(u32* ring, u32* /*slot 64 follows the ring*/, u32 lane)
     {
         acc = 0;
-        pos8 = 8;
+        np = 0u - 8u;
+        q = (8u - 40u) << 3;
         pos = 1;
         safe_from = 0;
         redo = 0;
         ring_lane = ring + lane;
     }
+    __device__ __forceinline__ u32 pos8() const { return 0u - np; }
+    // the lane's address in slot 0 as a number: a multiple of RCX_OUT_RING_BYTES + 4 x lane (McOutput), so a slot is ORed in
+    __device__ __forceinline__ u32 slot0() const { return (u32)reinterpret_cast<uintptr_t>(ring_lane); }
     __device__ __forceinline__ void chunk_begins()
     {
-        pos = pos8 >> 3;
+        pos = pos8() >> 3;
         safe_from = pos > RCX_OUT_MARGIN ? pos - RCX_OUT_MARGIN : 0u;
     }
     __device__ __forceinline__ u32 chunk_ends()
     {
-        pos = pos8 >> 3;
+        pos = pos8() >> 3;
         return pos;
     }
     // the two aligned words that hold the newest 5..8 bytes, from the window
     __device__ __forceinline__ void mirror()
     {
-        const u32 sh8 = (0u - pos8) & 24u;            // the window's end moved up to a word boundary
-        const u32 s0 = ((pos8 - 40u) >> 5) % RCX_OUT_RING_WORDS; // slot of the older word: ((pos - 1) / 4 - 1) mod 64
-        mirror_at(sh8, (u32)reinterpret_cast<uintptr_t>(ring_lane + s0 * RCX_LANES));
+        mirror_at(np & 24u, (q & RCX_OUT_SLOT_MASK) | slot0());
     }
     __device__ __forceinline__ void mirror_at(u32 sh8, u32 at_lds) // (an LDS address as a number: it passes through an asm statement)
     {
@@ -224,26 +240,28 @@ struct StagedWriter {
         const u32 lo1 = lo0 + (rec & 1u);                  // cpprcoder.h:767-781
         const bool far = lo1 < lo0;                        // ... through all of the newest four bytes
         // (where the words go depends on the position alone: worked out between the two halves of the add, whose second
-        // half may not follow the first at once)
-        u32 sh8 = (0u - pos8) & 24u;
-        u32 at = (u32)reinterpret_cast<uintptr_t>(ring_lane + (((pos8 - 40u) >> 5) % RCX_OUT_RING_WORDS) * RCX_LANES);
-        asm volatile("" : "+v"(sh8), "+v"(at));
+        // half may not follow the first at once.  The mask keeps the address inside the ring whatever q holds.)
+        u32 sh8 = np & 24u;
+        u32 at = (q & RCX_OUT_SLOT_MASK) | slot0();
+        // (q passes through as well: seen through, the compiler keeps the sum of the k8 instead and pays an add a symbol for it)
+        asm volatile("" : "+v"(sh8), "+v"(at), "+v"(q));
         acc = ((u64)((u32)(acc >> 32) + (far ? 1u : 0u)) << 32) | lo1;
         // (the far carry is looked at BEHIND the words' write: a branch on VCC directly behind the add that sets it held the
         // wave for 24 cycles a symbol.  rcx_stage_far_carry writes the two newest words itself, so the order does not matter
         // to what the ring holds afterwards.)
         mirror_at(sh8, at);
-        if (rcx_any(far)) redo |= rcx_stage_far_carry(ring_lane, acc, pos8, safe_from, far ? 1u : 0u);
+        if (rcx_any(far)) redo |= rcx_stage_far_carry(ring_lane, acc, pos8(), safe_from, far ? 1u : 0u);
         const u32 k8 = rec & 0x18u;
         acc = (acc << k8) | __builtin_amdgcn_ubfe(rec, 32u - k8, k8); // the k8 / 8 bytes that leave through the top of low
-        pos8 += k8;
+        np -= k8;
+        q += k8 << 3; // (one v_lshl_add_u32)
     }
     // After the last symbol: the words below the newest one are in the ring (returns how many bytes that is); the newest
     // 1..4 bytes are handed over as EncLane's held bytes.
     __device__ __forceinline__ u32 finish(EncLane& enc)
     {
         mirror();
-        pos = pos8 >> 3;
+        pos = pos8() >> 3;
         const u32 flushed = ((pos - 1u) >> 2) << 2;
         enc.nacc8 = 8u * (pos - flushed);
         enc.acc = acc & ((1ull << enc.nacc8) - 1ull);
@@ -257,20 +275,21 @@ struct StagedWriter {
 // writer wave, the drain of its rings and the closing stage.  Macros where the text sits inside the waves' loops, for
 // RCX_ENTRY's reason (rcx_geom.hpp).
 // ---------------------------------------------------------------------------
-// The writer's side of a workgroup's LDS, dword arrays of one entry per lane behind the record ring:
+// The writer's side of a workgroup's LDS, dword arrays of one entry per lane.  BASE: the kernel's LDS array, aligned to
+// RCX_OUT_RING_BYTES, + RCX_MC_OUTPUT_AT_DW (the ring comes first: StagedWriter ORs the slot into its address).
 struct McOutput {
-    u32* final_low; // the arithmetic wave's last low, for the writer's finish()
     u32* ring;      // RCX_OUT_RING_WORDS x 64: the writer's words on their way to global memory
     u32* dummy;     // (ring slot 64: repeats slot 0 for the writer's pair (63, 64))
+    u32* final_low; // the arithmetic wave's last low, for the writer's finish()
     u32* pos;       // writer -> drain: bytes in the ring so far
     u32* drained;   // drain -> writer's finish: bytes stored so far
 };
 #define RCX_MC_OUTPUT(OUT, BASE)                                                                                       \
     McOutput OUT;                                                                                                      \
-    OUT.final_low = (BASE);                                                                                            \
-    OUT.ring = OUT.final_low + RCX_LANES;                                                                              \
+    OUT.ring = (BASE);                                                                                                 \
     OUT.dummy = OUT.ring + RCX_OUT_RING_WORDS * RCX_LANES;                                                             \
-    OUT.pos = OUT.dummy + RCX_LANES;                                                                                   \
+    OUT.final_low = OUT.dummy + RCX_LANES;                                                                             \
+    OUT.pos = OUT.final_low + RCX_LANES;                                                                               \
     OUT.drained = OUT.pos + RCX_LANES
 
 // The writer wave in pipeline step K: the records of chunk K-2 from RING2[(K-2)&1], in pairs (one ds_read2st64_b32);
@@ -598,7 +617,8 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
                                                                 const u32* __restrict__ divq, u32* status,
                                                                 u32* __restrict__ redo, u32 lanes_used, const G g = G())
 {
-    __shared__ U4 lds[RCX_MC5_LDS_U4];
+    __shared__ __attribute__((aligned(RCX_OUT_RING_BYTES))) U4 lds[RCX_MC5_LDS_U4]; // (McOutput first: RCX_MC_OUTPUT)
+    static_assert(__alignof__(lds) % RCX_OUT_RING_BYTES == 0 && RCX_MC5_LDS_U4 * 16 <= 160 * 1024, "the output ring's place in LDS");
     const u32 lane = threadIdx.x & 63u;
     const u32 wave = RCX_MC5_ROLE(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); // the wave's ROLE (see RCX_MC5_ROLE)
     // lanes_used (1..64) of the 64 lanes carry a block; the others idle along (rcx_api.hip picks it from the
@@ -608,11 +628,12 @@ __global__ __launch_bounds__(RCX_MC5_THREADS) void rcx_enc_mc5_k(const u8* __res
     RCX_ENTRY(g, blk, nblocks, n, block);
     RCX_ENTRY_SLOTS(g, blk, slots, slot);
 
-    Tree tree{reinterpret_cast<u32*>(lds) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
-    u32* ring = reinterpret_cast<u32*>(lds + RCX_MC5_TREE_U4); // (no divisor staging behind the tree: rcx_mc5_pipeline)
-    u32* ring2 = reinterpret_cast<u32*>(lds + RCX_MC5_TREE_U4 + RCX_MC_RING_U4);
-    RCX_MC_OUTPUT(oq, ring2 + RCX_MC5_RING2_DW);
-    u32* ring3 = oq.drained + RCX_LANES;
+    RCX_MC_OUTPUT(oq, reinterpret_cast<u32*>(lds) + RCX_MC_OUTPUT_AT_DW);
+    U4* behind = lds + (RCX_MC_OUTPUT_AT_DW + RCX_MC_OUTPUT_DW) / 4;
+    Tree tree{reinterpret_cast<u32*>(behind) + (RCX_TREE_PLANAR ? 1 : 4) * lane};
+    u32* ring = reinterpret_cast<u32*>(behind + RCX_MC5_TREE_U4); // (no divisor staging behind the tree: rcx_mc5_pipeline)
+    u32* ring2 = reinterpret_cast<u32*>(behind + RCX_MC5_TREE_U4 + RCX_MC_RING_U4);
+    u32* ring3 = ring2 + RCX_MC5_RING2_DW;
 
     const u32 maxlen = rcx_wave_max(len);
     bool full;

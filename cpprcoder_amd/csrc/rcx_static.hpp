@@ -279,7 +279,9 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
                                                                     u8* __restrict__ slots, u64 slot, u32* __restrict__ sizes,
                                                                     u32* status, u32* __restrict__ redo, u32 lanes_used, const G g = G())
 {
-    __shared__ __attribute__((aligned(16))) u32 lds[RCX_ST3_LDS_DW];
+    __shared__ __attribute__((aligned(RCX_OUT_RING_BYTES))) u32 lds_all[RCX_ST3_LDS_DW]; // (McOutput first: RCX_MC_OUTPUT)
+    static_assert(__alignof__(lds_all) % RCX_OUT_RING_BYTES == 0, "the output ring's place in LDS");
+    u32* lds = lds_all + RCX_MC_OUTPUT_AT_DW + RCX_MC_OUTPUT_DW;
     const u32 lane = threadIdx.x & 63u;
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool in_use = lane < lanes_used; // see rcx_enc_mc5_k
@@ -288,9 +290,9 @@ __global__ __launch_bounds__(RCX_ST3_THREADS) void rcx_enc_static3_k(const u8* _
     RCX_ENTRY_SLOTS(g, blk, slots, slot);
     const u8* in = src + at;
     StaticTable tab{lds + lane};
-    U4* ring = reinterpret_cast<U4*>(lds + RCX_STATIC_LDS_DW); // 16-byte aligned: RCX_STATIC_LDS_DW = 257 * 64 dwords
+    U4* ring = reinterpret_cast<U4*>(lds + RCX_STATIC_LDS_DW); // 16-byte aligned: RCX_STATIC_LDS_DW = 257 * 64 dwords, behind 68 * 64
     u32* ring2 = reinterpret_cast<u32*>(ring + RCX_MC_RING_U4);
-    RCX_MC_OUTPUT(oq, ring2 + RCX_MC5_RING2_DW);
+    RCX_MC_OUTPUT(oq, lds_all + RCX_MC_OUTPUT_AT_DW);
 
     const u32 maxlen = rcx_wave_max(len);
     // (RCX_ALL_FULL, but for the lanes that carry no block: they do not count)
