@@ -21,14 +21,13 @@ from . import rcx
 from .base_items import NO_BASE
 from .base import SUBZZ
 from .predict import ZIGZAG
-from .typed_picks import (BINS, HEAD_BYTES, MAX_BLOCK, MAX_BYTES, MAX_PICK, PLAN_THREADS, ROW_BYTES, _table, bin_of)  # noqa: F401  (the planner's constants are shared)
+from .typed_picks import (BINS, HEAD_BYTES, MAX_BLOCK, MAX_BYTES, MAX_PICK, PLAN_THREADS, ROW, ROW_BYTES, TYPED_STEP_ROWS, _table, bin_of,  # noqa: F401
+                          set_tables as _set_tables)  # (the planner's constants and its rendering of a set are shared)
 
 # every symbol include/rcx_base_picks.h declares
 EXPORTS = ("rcx_base_picks_reserve", "rcx_base_picks_scratch_bytes", "rcx_base_join_picks_device", "rcx_base_join_picks")
 
 NONE, ROWS, SCAN, BASE = 0, 1, 2, 3  # an entry's route: not joined; the typed set's classes; its scan list; the base set
-ROW = 256                            # RCX_TYPED_ROW: units of a row
-TYPED_STEP_ROWS = {1: 16, 2: 8, 4: 4, 8: 2}  # RCX_PLANES_U4 / w: rows of a workgroup step of the typed set
 BASE_STEP_ROWS = {1: 8, 2: 4, 4: 2, 8: 1}    # RCX_BASE_ROWS(w): ... of the base set
 
 _ready = False
@@ -64,50 +63,6 @@ def scratch_formula(max_pick: int, max_bytes: int) -> int:
 
 def _class_of(w: int, second: int) -> int:
     return 3 * (1, 2, 4, 8).index(w) + second
-
-
-def _set_tables(placed, step_rows):
-    """One set's tables from its entries [(class, k, len, width)] in the caller's order -> dict(ent_first, row_first, ubase,
-    step_end, rest_end: the head; ufirst; entry: which entry of the call stands at each place; rowtab)."""
-    nent, units = [0] * 12, [0] * 12
-    for c, _, n, w in placed:
-        nent[c] += 1
-        units[c] += (n // w) >> 4
-    ent_first, row_first, ubase, step_end, rest_end = [], [], [], [], []
-    ents = rows = ub = steps = rests = 0
-    for c in range(12):
-        w = 1 << (c // 3)
-        ent_first.append(ents), row_first.append(rows), ubase.append(ub)
-        step = step_rows[w] * ROW
-        steps += -(-units[c] // step)
-        rests += -(-nent[c] * 17 * w // ROW)
-        step_end.append(steps), rest_end.append(rests)
-        ents += nent[c]
-        ub += units[c]
-        if nent[c]:
-            rows += -(-units[c] // ROW) + 1
-    ent_first.append(ents), row_first.append(rows), ubase.append(ub)
-    ufirst, entry = np.zeros(ents + 1, np.uint64), np.zeros(ents, np.int64)
-    nxt, unit = list(ent_first[:12]), list(ubase[:12])
-    for c, k, n, w in placed:
-        ufirst[nxt[c]], entry[nxt[c]] = unit[c], k
-        nxt[c] += 1
-        unit[c] += (n // w) >> 4
-    ufirst[ents] = ub
-    rowtab = np.zeros(rows, np.uint32)
-    for c in range(12):
-        if not nent[c]:
-            continue
-        last, k = ent_first[c + 1] - 1, ent_first[c]
-        nrow = -(-units[c] // ROW)
-        for r in range(nrow):
-            g = ubase[c] + r * ROW
-            while k < last and int(ufirst[k + 1]) <= g:
-                k += 1
-            rowtab[row_first[c] + r] = k
-        rowtab[row_first[c] + nrow] = last
-    return {"ent_first": np.array(ent_first, np.uint32), "row_first": np.array(row_first, np.uint32), "ubase": np.array(ubase, np.uint64),
-            "step_end": np.array(step_end, np.uint64), "rest_end": np.array(rest_end, np.uint64), "ufirst": ufirst, "entry": entry, "rowtab": rowtab}
 
 
 def plan_numpy(src_at, base_at, dst_at, length, widths, preds, ops, count: int, max_bytes: int, src_cap: int, base_cap: int, dst_cap: int):

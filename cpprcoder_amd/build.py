@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librcx.so")
 LIB_VARIANTS = os.path.join(HERE, "librcx_variants.so")  # diagnostic: + the superseded kernels of csrc/variants/ (RCX_LIBRARY=...)
 SOURCES = ["rcx_api.hip", "rcx_comm.hip"]
-HEADERS = ["rcx_lane.hpp", "rcx_geom.hpp", "rcx_buf.hpp", "rcx_ctx.hpp", "rcx_launch.hpp", "rcx_items.hpp", "rcx_host.hpp", "rcx_streams.hpp", "rcx_bwt_api.hpp", "rcx_divtab.hpp", "rcx_kernels.hpp", "rcx_adaptive.hpp", "rcx_quad.hpp", "rcx_mc.hpp", "rcx_static.hpp", "rcx_rans.hpp", "rcx_bwt.hpp", "rcx_bwt_tie.hpp", "rcx_crc.hpp", "rcx_crc_api.hpp", "rcx_stats.hpp", "rcx_stats_api.hpp", "rcx_stored.hpp", "rcx_stored_api.hpp", "rcx_stored_items.hpp", "rcx_stored_items_api.hpp", "rcx_planes.hpp", "rcx_predict.hpp", "rcx_typed_api.hpp", "rcx_typed_items.hpp", "rcx_typed_items_api.hpp", "rcx_base.hpp", "rcx_base_api.hpp", "rcx_base_items.hpp", "rcx_base_items_api.hpp", "rcx_typed_stats.hpp", "rcx_typed_stats_api.hpp", "rcx_picks.hpp", "rcx_picks_api.hpp", "rcx_typed_picks.hpp", "rcx_typed_picks_api.hpp", "rcx_base_picks.hpp", "rcx_base_picks_api.hpp", "rcx_encode_picks.hpp", "rcx_encode_picks_api.hpp", "rcx_typed_split_picks.hpp", "rcx_typed_split_picks_api.hpp", os.path.join("variants", "rcx_variants.hpp"), "rcx_comm.hip", os.path.join("..", "..", "include", "rcx.h"), os.path.join("..", "..", "include", "rcx_planes.h"), os.path.join("..", "..", "include", "rcx_predict.h"), os.path.join("..", "..", "include", "rcx_stats.h"), os.path.join("..", "..", "include", "rcx_stored.h"), os.path.join("..", "..", "include", "rcx_stored_items.h"), os.path.join("..", "..", "include", "rcx_typed_items.h"), os.path.join("..", "..", "include", "rcx_base.h"), os.path.join("..", "..", "include", "rcx_base_items.h"), os.path.join("..", "..", "include", "rcx_typed_stats.h"), os.path.join("..", "..", "include", "rcx_picks.h"), os.path.join("..", "..", "include", "rcx_typed_picks.h"), os.path.join("..", "..", "include", "rcx_base_picks.h"), os.path.join("..", "..", "include", "rcx_encode_picks.h"), os.path.join("..", "..", "include", "rcx_typed_split_picks.h")]
+HEADERS = ["rcx_lane.hpp", "rcx_geom.hpp", "rcx_buf.hpp", "rcx_ctx.hpp", "rcx_launch.hpp", "rcx_items.hpp", "rcx_host.hpp", "rcx_streams.hpp", "rcx_bwt_api.hpp", "rcx_divtab.hpp", "rcx_kernels.hpp", "rcx_adaptive.hpp", "rcx_quad.hpp", "rcx_mc.hpp", "rcx_static.hpp", "rcx_rans.hpp", "rcx_bwt.hpp", "rcx_bwt_tie.hpp", "rcx_crc.hpp", "rcx_crc_api.hpp", "rcx_stats.hpp", "rcx_stats_api.hpp", "rcx_stored.hpp", "rcx_stored_api.hpp", "rcx_stored_items.hpp", "rcx_stored_items_api.hpp", "rcx_planes.hpp", "rcx_predict.hpp", "rcx_typed_api.hpp", "rcx_typed_items.hpp", "rcx_typed_items_api.hpp", "rcx_base.hpp", "rcx_base_api.hpp", "rcx_base_items.hpp", "rcx_base_items_api.hpp", "rcx_typed_stats.hpp", "rcx_typed_stats_api.hpp", "rcx_picks.hpp", "rcx_picks_api.hpp", "rcx_class_plan.hpp", "rcx_typed_picks.hpp", "rcx_typed_picks_api.hpp", "rcx_base_picks.hpp", "rcx_base_picks_api.hpp", "rcx_encode_picks.hpp", "rcx_encode_picks_api.hpp", "rcx_typed_split_picks.hpp", "rcx_typed_split_picks_api.hpp", os.path.join("variants", "rcx_variants.hpp"), "rcx_comm.hip", os.path.join("..", "..", "include", "rcx.h"), os.path.join("..", "..", "include", "rcx_planes.h"), os.path.join("..", "..", "include", "rcx_predict.h"), os.path.join("..", "..", "include", "rcx_stats.h"), os.path.join("..", "..", "include", "rcx_stored.h"), os.path.join("..", "..", "include", "rcx_stored_items.h"), os.path.join("..", "..", "include", "rcx_typed_items.h"), os.path.join("..", "..", "include", "rcx_base.h"), os.path.join("..", "..", "include", "rcx_base_items.h"), os.path.join("..", "..", "include", "rcx_typed_stats.h"), os.path.join("..", "..", "include", "rcx_picks.h"), os.path.join("..", "..", "include", "rcx_typed_picks.h"), os.path.join("..", "..", "include", "rcx_base_picks.h"), os.path.join("..", "..", "include", "rcx_encode_picks.h"), os.path.join("..", "..", "include", "rcx_typed_split_picks.h")]
 
 
 def hipcc() -> str:

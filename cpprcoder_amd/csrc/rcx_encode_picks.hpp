@@ -26,7 +26,6 @@
 
 #define RCX_EPICK_CLASSES 21u // uppers 2^24 (as RCX_MAX_BLOCK), 2^23, ... 16: longest first
 #define RCX_EPICK_BINS RCX_PICK_CODED_BINS
-#define RCX_EPICK_SCAN_PER ((RCX_EPICK_BINS + RCX_PICK_SCAN_THREADS - 1) / RCX_PICK_SCAN_THREADS)
 #define RCX_EPICK_PAD (64u * (RCX_EPICK_CLASSES + 1u)) // work positions beyond max_items: a unit's padding per class, the launch's
 
 // the upper length of class c (what item_class_upper gives its lengths), and the bin of a length 1 .. RCX_MAX_BLOCK
@@ -66,12 +65,6 @@ struct RcxEpickPlan {
     u32* counts;      // [4]: positions laid out (a multiple of 64), 1 = the total is above max_bytes
 };
 
-__device__ __forceinline__ u64 rcx_epick_count(const RcxEpickTables& t)
-{
-    const u64 c = t.count[0];
-    return c < t.max_items ? c : t.max_items;
-}
-
 __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_epicks_clear_k(const RcxEpickPlan p)
 {
     const u32 b = blockIdx.x * RCX_PICK_THREADS + threadIdx.x;
@@ -81,7 +74,7 @@ __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_epicks_clear_k(const Rcx
 
 __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_epicks_classify_k(const RcxEpickTables t, const RcxEpickPlan p, u32* status)
 {
-    const u64 count = rcx_epick_count(t);
+    const u64 count = rcx_pick_count(t.count, t.max_items);
     if (blockIdx.x == 0 && threadIdx.x == 0 && t.count[0] > t.max_items) rcx_flag(status, RCX_ST_CAPACITY, t.max_items);
     u64 bytes = 0;
     // whole waves: every lane of a wave that has a table entry goes round
@@ -116,33 +109,14 @@ __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_epicks_classify_k(const 
 
 __global__ __launch_bounds__(RCX_PICK_SCAN_THREADS) void rcx_epicks_scan_k(const RcxEpickTables tb, const RcxEpickPlan p, const RcxEpickClasses cl, u32* status)
 {
-    __shared__ u32 part[RCX_PICK_SCAN_THREADS];
+    __shared__ u32 lds[RCX_PICK_SCAN_THREADS / 64u];
     __shared__ u32 pre[RCX_EPICK_BINS + 1];        // entries in the bins before b
     __shared__ u32 cstart[RCX_EPICK_CLASSES + 1];  // the class's first work position; [21] = the positions laid out
     __shared__ u64 cbase[RCX_EPICK_CLASSES];       // where its slots begin
     __shared__ u32 over;
-    const u32 t = threadIdx.x, b0 = t * RCX_EPICK_SCAN_PER;
-    u32 mine[RCX_EPICK_SCAN_PER], sum = 0;
-#pragma unroll
-    for (u32 j = 0; j < RCX_EPICK_SCAN_PER; ++j) {
-        mine[j] = b0 + j < RCX_EPICK_BINS ? p.bins[b0 + j] : 0u;
-        sum += mine[j];
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (u32 o = 1; o < RCX_PICK_SCAN_THREADS; o <<= 1) { // inclusive, in place
-        const u32 add = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    u32 before = part[t] - sum;
-#pragma unroll
-    for (u32 j = 0; j < RCX_EPICK_SCAN_PER; ++j) {
-        if (b0 + j < RCX_EPICK_BINS) pre[b0 + j] = before;
-        before += mine[j];
-    }
-    if (t == RCX_PICK_SCAN_THREADS - 1) pre[RCX_EPICK_BINS] = part[t];
+    const u32 t = threadIdx.x;
+    const u32 all = rcx_bins_scan<RCX_EPICK_BINS>(p.bins, lds, [&](u32 b, u32 before, u32) { pre[b] = before; });
+    if (t == 0) pre[RCX_EPICK_BINS] = all;
     __syncthreads();
     if (t == 0) {
         u32 pos = 0;
@@ -159,18 +133,14 @@ __global__ __launch_bounds__(RCX_PICK_SCAN_THREADS) void rcx_epicks_scan_k(const
         over = too_many ? 1u : 0u;
         p.counts[0] = too_many ? 0u : pos;
         p.counts[1] = over;
-        if (too_many) rcx_flag(status, RCX_ST_CAPACITY, rcx_epick_count(tb));
+        if (too_many) rcx_flag(status, RCX_ST_CAPACITY, rcx_pick_count(tb.count, tb.max_items));
     }
     __syncthreads();
     if (over) return; // (every thread: nothing of the layout is read)
-#pragma unroll
-    for (u32 j = 0; j < RCX_EPICK_SCAN_PER; ++j) {
-        const u32 b = b0 + j;
-        if (b < RCX_EPICK_BINS) {
-            u32 c = 0;
-            while (b >= cl.first_bin[c + 1]) ++c; // (first_bin[21] = RCX_EPICK_BINS)
-            p.cursor[b] = cstart[c] + (pre[b] - pre[cl.first_bin[c]]);
-        }
+    for (u32 b = t; b < RCX_EPICK_BINS; b += RCX_PICK_SCAN_THREADS) {
+        u32 c = 0;
+        while (b >= cl.first_bin[c + 1]) ++c; // (first_bin[21] = RCX_EPICK_BINS)
+        p.cursor[b] = cstart[c] + (pre[b] - pre[cl.first_bin[c]]);
     }
     const u32 laid = cstart[RCX_EPICK_CLASSES];
     for (u32 u = t; u < laid / 64u; u += RCX_PICK_SCAN_THREADS) {
@@ -189,7 +159,7 @@ __global__ __launch_bounds__(RCX_PICK_SCAN_THREADS) void rcx_epicks_scan_k(const
 __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_epicks_scatter_k(const RcxEpickTables t, const RcxEpickPlan p)
 {
     if (p.counts[1]) return;
-    const u64 count = rcx_epick_count(t);
+    const u64 count = rcx_pick_count(t.count, t.max_items);
     for (u64 k0 = (u64)blockIdx.x * RCX_PICK_THREADS; k0 < count; k0 += (u64)gridDim.x * RCX_PICK_THREADS) {
         const u64 k = k0 + threadIdx.x;
         const u32 bin = k < count ? p.keys[k] : RCX_PICK_NONE;

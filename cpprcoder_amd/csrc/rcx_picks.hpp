@@ -26,29 +26,38 @@
 // picks of one length -- pages -- that is one atomic a wave and not 64 to one address.
 // No LDS apart from the scan's, no inline assembly, no scratch; nothing is read behind min(*d_count, max_pick).
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include "rcx_stored.hpp"
+#include "rcx_lane.hpp"
 
 #define RCX_PICK_EXACT 512u                                          // lengths below this have a bin each
-#define RCX_PICK_CODED_BINS (RCX_PICK_EXACT + (24u - 9u) * 256u)      // 4352
+#define RCX_LEN_BINS(top_bits) (RCX_PICK_EXACT + ((top_bits) - 9u) * 256u) // the bins of the lengths below 2^top_bits
+#define RCX_PICK_CODED_BINS RCX_LEN_BINS(24u)                        // 4352
 #define RCX_PICK_BINS (RCX_PICK_CODED_BINS + 2u)                     // + stored long, stored short
 #define RCX_PICK_NONE 0xFFFFFFFFu
 #define RCX_PICK_THREADS 256
 #define RCX_PICK_SCAN_THREADS 1024
-#define RCX_PICK_SCAN_PER ((RCX_PICK_BINS + RCX_PICK_SCAN_THREADS - 1) / RCX_PICK_SCAN_THREADS)
 
-// the bin of a coded pick of `len` bytes, 1 <= len < 2^24: ascending bins = descending length
-RCX_HD u32 rcx_pick_bin(u32 len)
+// the bin of `len` bytes, 1 <= len < 2^top_bits, among RCX_LEN_BINS(top_bits): ascending bins = descending length.  The one
+// rule of every work order here: rcx_pick_bin, rcx_epick_bin (rcx_encode_picks.hpp), rcx_tpick_bin (rcx_typed_picks.hpp).
+RCX_HD u32 rcx_len_bin(u32 len, u32 top_bits)
 {
     u32 up = len;
     if (len >= RCX_PICK_EXACT) {
         u32 e = 9;
-        while ((len >> e) > 1u) ++e; // the leading one, 9 .. 23
+        while ((len >> e) > 1u) ++e; // the leading one, 9 .. top_bits - 1
         up = RCX_PICK_EXACT + (e - 9u) * 256u + ((len >> (e - 8u)) & 255u);
     }
-    return RCX_PICK_CODED_BINS - 1u - up;
+    return RCX_LEN_BINS(top_bits) - 1u - up;
 }
+
+// the bin of a coded pick of `len` bytes, 1 <= len < 2^24
+RCX_HD u32 rcx_pick_bin(u32 len) { return rcx_len_bin(len, 24u); }
+
+#if !defined(RCX_HOST_SIM)
+
+#include <hip/hip_runtime.h>
+
+#include "rcx_predict.hpp" // rcx_wave_scan
+#include "rcx_stored.hpp"
 
 // What the call is given, as the kernels take it.
 struct RcxPickTables {
@@ -94,11 +103,55 @@ __device__ __forceinline__ u32 rcx_pick_take(u32* counters, u32 bin, bool has)
     return place;
 }
 
-// how many of the entries are meant
-__device__ __forceinline__ u64 rcx_pick_count(const RcxPickTables& t)
+// how many of the `most` entries are meant
+__device__ __forceinline__ u64 rcx_pick_count(const u64* count, u64 most)
 {
-    const u64 c = t.count[0];
-    return c < t.max_pick ? c : t.max_pick;
+    const u64 c = count[0];
+    return c < most ? c : most;
+}
+
+// Inclusive sums over the RCX_PICK_SCAN_THREADS threads of the one workgroup; all = the workgroup's total.  lds: 16 words; in
+// step at its end.
+template <class T>
+__device__ __forceinline__ T rcx_group_scan(T x, T* lds, T& all)
+{
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    T upto = rcx_wave_scan<T>(x, lane);
+    if (lane == 63u) lds[wave] = upto;
+    __syncthreads();
+    T front = 0;
+    all = 0;
+#pragma unroll
+    for (u32 w = 0; w < RCX_PICK_SCAN_THREADS / 64u; ++w) {
+        const T v = lds[w];
+        front += w < wave ? v : (T)0;
+        all += v;
+    }
+    __syncthreads();
+    return upto + front;
+}
+
+// The exclusive sum of bins[BINS] by the one workgroup: each(b, before, mine) for every bin b, before = the entries of the
+// bins in front of it, mine = its own; -> the entries of all bins.  lds: 16 words.
+template <u32 BINS, class F>
+__device__ __forceinline__ u32 rcx_bins_scan(const u32* bins, u32* lds, F&& each)
+{
+    constexpr u32 PER = (BINS + RCX_PICK_SCAN_THREADS - 1) / RCX_PICK_SCAN_THREADS;
+    const u32 b0 = threadIdx.x * PER;
+    u32 mine[PER], sum = 0;
+#pragma unroll
+    for (u32 j = 0; j < PER; ++j) {
+        mine[j] = b0 + j < BINS ? bins[b0 + j] : 0u;
+        sum += mine[j];
+    }
+    u32 all;
+    u32 before = rcx_group_scan<u32>(sum, lds, all) - sum;
+#pragma unroll
+    for (u32 j = 0; j < PER; ++j) {
+        if (b0 + j < BINS) each(b0 + j, before, mine[j]);
+        before += mine[j];
+    }
+    return all;
 }
 
 __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_picks_clear_k(const RcxPickPlan p)
@@ -109,7 +162,7 @@ __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_picks_clear_k(const RcxP
 
 __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_picks_classify_k(const RcxPickTables t, const RcxPickPlan p, u32* status)
 {
-    const u64 count = rcx_pick_count(t);
+    const u64 count = rcx_pick_count(t.count, t.max_pick);
     if (blockIdx.x == 0 && threadIdx.x == 0 && t.count[0] > t.max_pick) rcx_flag(status, RCX_ST_CAPACITY, t.max_pick);
     // whole waves: every lane of a wave that has an entry goes round
     for (u64 k0 = (u64)blockIdx.x * RCX_PICK_THREADS; k0 < count; k0 += (u64)gridDim.x * RCX_PICK_THREADS) {
@@ -139,40 +192,20 @@ __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_picks_classify_k(const R
 
 __global__ __launch_bounds__(RCX_PICK_SCAN_THREADS) void rcx_picks_scan_k(const RcxPickPlan p)
 {
-    __shared__ u32 part[RCX_PICK_SCAN_THREADS];
-    const u32 t = threadIdx.x, b0 = t * RCX_PICK_SCAN_PER;
-    u32 mine[RCX_PICK_SCAN_PER], sum = 0;
-#pragma unroll
-    for (u32 j = 0; j < RCX_PICK_SCAN_PER; ++j) {
-        mine[j] = b0 + j < RCX_PICK_BINS ? p.bins[b0 + j] : 0u;
-        sum += mine[j];
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (u32 o = 1; o < RCX_PICK_SCAN_THREADS; o <<= 1) { // inclusive, in place
-        const u32 add = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    u32 before = part[t] - sum;
-#pragma unroll
-    for (u32 j = 0; j < RCX_PICK_SCAN_PER; ++j) {
-        if (b0 + j < RCX_PICK_BINS) {
-            p.cursor[b0 + j] = before;
-            if (b0 + j == RCX_PICK_CODED_BINS) {
-                p.counts[0] = before;
-                p.counts[1] = mine[j];
-            }
-            if (b0 + j == RCX_PICK_CODED_BINS + 1u) p.counts[2] = mine[j];
+    __shared__ u32 lds[RCX_PICK_SCAN_THREADS / 64u];
+    (void)rcx_bins_scan<RCX_PICK_BINS>(p.bins, lds, [&](u32 b, u32 before, u32 mine) {
+        p.cursor[b] = before;
+        if (b == RCX_PICK_CODED_BINS) {
+            p.counts[0] = before;
+            p.counts[1] = mine;
         }
-        before += mine[j];
-    }
+        if (b == RCX_PICK_CODED_BINS + 1u) p.counts[2] = mine;
+    });
 }
 
 __global__ __launch_bounds__(RCX_PICK_THREADS) void rcx_picks_scatter_k(const RcxPickTables t, const RcxPickPlan p)
 {
-    const u64 count = rcx_pick_count(t);
+    const u64 count = rcx_pick_count(t.count, t.max_pick);
     for (u64 k0 = (u64)blockIdx.x * RCX_PICK_THREADS; k0 < count; k0 += (u64)gridDim.x * RCX_PICK_THREADS) {
         const u64 k = k0 + threadIdx.x;
         const u32 bin = k < count ? p.keys[k] : RCX_PICK_NONE;
@@ -215,3 +248,5 @@ struct RcxCountedPickEntries {
         return true;
     }
 };
+
+#endif // !RCX_HOST_SIM

@@ -49,17 +49,23 @@ def lib() -> C.CDLL:
 
 
 # ---- the planner's rules, in numpy -----------------------------------------------------------------------------------------
-def bin_of(length: int) -> int:
-    """The bin of a coded pick of `length` bytes, 1 <= length < 2^24, in work order: ascending bins are descending lengths.
-    A length below 512 has a bin of its own; above, the bin is the length's leading one and the eight bits behind it."""
+def len_bin(length: int, top_bits: int) -> int:
+    """rcx_len_bin, the one bin rule: the bin of `length` bytes, 1 <= length < 2^top_bits, in work order: ascending bins are
+    descending lengths.  A length below 512 has a bin of its own; above, the bin is the length's leading one and the eight bits
+    behind it."""
     length = int(length)
-    if not 1 <= length < 1 << 24:
-        raise ValueError("a coded pick has 1 .. 2^24 - 1 bytes")
+    if not 1 <= length < 1 << top_bits:
+        raise ValueError(f"an entry has 1 .. 2^{top_bits} - 1 bytes")
     up = length
     if length >= EXACT:
         e = length.bit_length() - 1
         up = EXACT + (e - 9) * 256 + ((length >> (e - 8)) & 255)
-    return CODED_BINS - 1 - up
+    return EXACT + (top_bits - 9) * 256 - 1 - up
+
+
+def bin_of(length: int) -> int:
+    """The bin of a coded pick of `length` bytes, 1 <= length < 2^24: len_bin among CODED_BINS."""
+    return len_bin(length, 24)
 
 
 def plan_numpy(pick, dst_at, dst_len, count: int, max_len: int, nstreams: int, dst_cap: int, stored=None, comp_offsets=None, comp_size: int | None = None):

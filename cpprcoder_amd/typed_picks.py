@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import rcx
+from .picks import len_bin
 from .predict import ZIGZAG
 
 # every symbol include/rcx_typed_picks.h declares
@@ -32,6 +33,8 @@ EXACT = 512                  # RCX_TPICK_EXACT: scan list lengths below this hav
 BINS = EXACT + (27 - 9) * 256  # RCX_TPICK_BINS
 ROW_BYTES = 4096             # bytes of a row of 256 units at the least
 HEAD_BYTES = 400             # sizeof(RcxTypedClasses)
+ROW = 256                    # RCX_TYPED_ROW: units of a row
+TYPED_STEP_ROWS = {1: 16, 2: 8, 4: 4, 8: 2}  # RCX_PLANES_U4 / w: rows of a workgroup step of the typed kernels
 NONE, ROWS, SCAN = 0, 1, 2   # an entry's route: not joined; the classes without a predictor; the scan list
 
 _ready = False
@@ -55,16 +58,59 @@ def lib() -> C.CDLL:
 
 # ---- the planner's rules, in numpy -----------------------------------------------------------------------------------------
 def bin_of(length: int) -> int:
-    """The bin of a scan list entry of `length` bytes, 1 <= length < 2^27: ascending bins are descending lengths.  A length
-    below 512 has a bin of its own; above, the bin is the length's leading one and the eight bits behind it."""
-    length = int(length)
-    if not 1 <= length < 1 << 27:
-        raise ValueError("a typed entry has 1 .. 2^27 - 1 bytes")
-    up = length
-    if length >= EXACT:
-        e = length.bit_length() - 1
-        up = EXACT + (e - 9) * 256 + ((length >> (e - 8)) & 255)
-    return BINS - 1 - up
+    """The bin of a scan list entry of `length` bytes, 1 <= length < 2^27: picks.len_bin among BINS."""
+    return len_bin(length, 27)
+
+
+def head_of(nent, units, step_rows):
+    """rcx_class_head: the head of a set from its 12 classes' entries and whole units; step_rows[w] = the rows of a workgroup
+    step of width w -> (ent_first[13], row_first[13], ubase[13], step_end[12], rest_end[12]) of Python integers."""
+    ent_first, row_first, ubase, step_end, rest_end = [], [], [], [], []
+    ents = rows = ub = steps = rests = 0
+    for c in range(12):
+        w = 1 << (c // 3)
+        n, un = int(nent[c]), int(units[c])
+        ent_first.append(ents), row_first.append(rows), ubase.append(ub)
+        step = step_rows[w] * ROW
+        steps += -(-un // step)
+        rests += -(-n * 17 * w // ROW)
+        step_end.append(steps), rest_end.append(rests)
+        ents, ub = ents + n, ub + un
+        if n:
+            rows += -(-un // ROW) + 1
+    return ent_first + [ents], row_first + [rows], ubase + [ub], step_end, rest_end
+
+
+def set_tables(placed, step_rows):
+    """One set's tables from its entries [(class, k, len, width)] in the caller's order -> dict(ent_first, row_first, ubase,
+    step_end, rest_end: the head; ufirst; entry: which entry of the call stands at each place; rowtab)."""
+    nent, units = [0] * 12, [0] * 12
+    for c, _, n, w in placed:
+        nent[c] += 1
+        units[c] += (n // w) >> 4
+    ent_first, row_first, ubase, step_end, rest_end = head_of(nent, units, step_rows)
+    ents, rows = ent_first[12], row_first[12]
+    ufirst, entry = np.zeros(ents + 1, np.uint64), np.zeros(ents, np.int64)
+    nxt, unit = list(ent_first[:12]), list(ubase[:12])
+    for c, k, n, w in placed:
+        ufirst[nxt[c]], entry[nxt[c]] = unit[c], k
+        nxt[c] += 1
+        unit[c] += (n // w) >> 4
+    ufirst[ents] = ubase[12]
+    rowtab = np.zeros(rows, np.uint32)
+    for c in range(12):
+        if not nent[c]:
+            continue
+        last, k = ent_first[c + 1] - 1, ent_first[c]
+        nrow = -(-units[c] // ROW)
+        for r in range(nrow):
+            g = ubase[c] + r * ROW
+            while k < last and int(ufirst[k + 1]) <= g:
+                k += 1
+            rowtab[row_first[c] + r] = k
+        rowtab[row_first[c] + nrow] = last
+    return {"ent_first": np.array(ent_first, np.uint32), "row_first": np.array(row_first, np.uint32), "ubase": np.array(ubase, np.uint64),
+            "step_end": np.array(step_end, np.uint64), "rest_end": np.array(rest_end, np.uint64), "ufirst": ufirst, "entry": entry, "rowtab": rowtab}
 
 
 def scratch_formula(max_pick: int, max_bytes: int) -> int:

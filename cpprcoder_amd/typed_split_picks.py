@@ -23,13 +23,13 @@ import numpy as np
 
 from . import rcx
 from .predict import ZIGZAG
-from .typed_picks import HEAD_BYTES, MAX_BLOCK, MAX_BYTES, MAX_PICK, PLAN_GRID, PLAN_THREADS, PLAN_TOP, ROW_BYTES, _table  # noqa: F401  (the planner's shapes are shared)
+from .typed_picks import (HEAD_BYTES, MAX_BLOCK, MAX_BYTES, MAX_PICK, PLAN_GRID, PLAN_THREADS, PLAN_TOP, ROW, ROW_BYTES, TYPED_STEP_ROWS, _table,  # noqa: F401
+                          head_of, set_tables)  # (the planner's shapes and its rendering of a set are shared)
 
 # every symbol include/rcx_typed_split_picks.h declares
 EXPORTS = ("rcx_typed_split_picks_reserve", "rcx_typed_split_picks_scratch_bytes", "rcx_typed_split_picks_device", "rcx_typed_split_picks")
 
 CLASSES = 12         # RCX_TYPED_CLASSES: class = 3 * log2(width) + predictor; 1 and 2 stay empty (width 1 takes no predictor)
-ROW = 256            # RCX_TYPED_ROW: units of a row
 PLANES_U4 = 16       # RCX_PLANES_U4: a workgroup step is PLANES_U4 / width rows
 NO_CLASS = -1
 
@@ -70,20 +70,8 @@ def scratch_formula(max_pick: int, max_bytes: int) -> int:
 def head_numpy(nent, units):
     """The head of the tables from the 12 classes' entries and whole units, as rcx_typed_plan(..., scan = false) computes it ->
     dict(step_end[12], rest_end[12], ubase[13], ent_first[13], row_first[13]) of Python integers."""
-    step_end, rest_end, ubase, ent_first, row_first = [], [], [], [], []
-    ents = rows = ub = steps = rests = 0
-    for c in range(CLASSES):
-        w = 1 << (c // 3)
-        n, un = int(nent[c]), int(units[c])
-        ent_first.append(ents), row_first.append(rows), ubase.append(ub)
-        step = PLANES_U4 // w * ROW
-        steps += -(-un // step)
-        rests += -(-(n * 17 * w) // ROW)
-        step_end.append(steps), rest_end.append(rests)
-        ents, ub = ents + n, ub + un
-        if n:
-            rows += -(-un // ROW) + 1
-    return {"step_end": step_end, "rest_end": rest_end, "ubase": ubase + [ub], "ent_first": ent_first + [ents], "row_first": row_first + [rows]}
+    ent_first, row_first, ubase, step_end, rest_end = head_of(nent, units, TYPED_STEP_ROWS)
+    return {"step_end": step_end, "rest_end": rest_end, "ubase": ubase, "ent_first": ent_first, "row_first": row_first}
 
 
 def plan_numpy(src_at, dst_at, length, widths, preds, count: int, max_bytes: int, src_cap: int, dst_cap: int):
@@ -129,17 +117,15 @@ def plan_numpy(src_at, dst_at, length, widths, preds, count: int, max_bytes: int
     overflow = total > max_bytes
     if overflow:
         capacity.append(meant)
-    placed = np.flatnonzero(valid & (not overflow))
-    order = placed[np.argsort(klass[placed], kind="stable")]  # by class, the caller's order within it
+    placed = [] if overflow else [(int(klass[k]), int(k), int(length[k]), int(widths[k])) for k in np.flatnonzero(valid)]
+    t = set_tables(placed, TYPED_STEP_ROWS)  # by class, the caller's order within it
+    order, ufirst = t["entry"], t["ufirst"]
     place = np.full(max_pick, -1, dtype=np.int64)
     place[order] = np.arange(len(order))
-    units = (length[order] // widths[order].astype(np.uint64)) >> np.uint64(4)  # the whole units of the entries, in the placed order
-    ufirst = np.concatenate([[0], np.cumsum(units)]).astype(np.uint64)
-    nent = [int(np.sum(klass[order] == c)) for c in range(CLASSES)]
-    class_units = [int(units[klass[order] == c].sum()) for c in range(CLASSES)]
     kept = np.where(place >= 0, length, np.uint64(0)).astype(np.uint64)
+    head = {key: [int(x) for x in t[key]] for key in ("step_end", "rest_end", "ubase", "ent_first", "row_first")}
     failing = corrupt + capacity
-    return {"count": meant, "valid": valid, "klass": klass, "place": place, "ufirst": ufirst, "order": order, "head": head_numpy(nent, class_units),
+    return {"count": meant, "valid": valid, "klass": klass, "place": place, "ufirst": ufirst, "order": order, "head": head,
             "kept": kept, "bytes": total, "overflow": overflow,
             "status": rcx.E_CORRUPT if corrupt else rcx.E_CAPACITY if capacity else rcx.OK, "position": min(failing) if failing else None}
 

@@ -1,6 +1,6 @@
 // base_picks_san.cpp -- the planner's rules of cpprcoder_amd/csrc/rcx_base_picks.hpp (rcx_bpick_validate, rcx_bpick_key,
-// rcx_bpick_head, rcx_bpick_rows_most and, from rcx_typed_picks.hpp, rcx_tpick_units, rcx_tpick_bin, rcx_tpick_head,
-// rcx_tpick_row: plain functions, the same text the kernels compile) in a program of its own, to be built with
+// and, from rcx_typed_picks.hpp and the class planner, rcx_tpick_units, rcx_tpick_bin, rcx_class_head, rcx_class_row,
+// rcx_class_rows_most: plain functions, the same text the kernels compile) in a program of its own, to be built with
 // -fsanitize=address,undefined (tests/test_base_picks_cpu.py does).  It reads the batches base_items_cases.write_cases writes,
 // plans each in the planner's steps -- keys and the 16 sums a tile, the sums over the tiles and both heads, the places, both
 // row tables -- and checks
@@ -10,13 +10,7 @@
 //                   its own entry; both row counts are within their bounds
 // The tables lie in heap blocks of exactly their size, so a step outside is an error of the sanitizer as well.
 // Test tooling, not part of librcx.so.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../cpprcoder_amd/csrc/rcx_base_picks.hpp"
-
-uint64_t rcx_sim_counters[4];
+#include "picks_san.hpp"
 
 namespace
 {
@@ -27,16 +21,6 @@ struct Batch {
     u64 first = 0, base_first = 0, base_bytes = 0;
 };
 
-#define CHECK(cond, ...)                 \
-    do {                                 \
-        if (!(cond)) {                   \
-            printf("batch %d: ", which); \
-            printf(__VA_ARGS__);         \
-            printf("\n");                \
-            return false;                \
-        }                                \
-    } while (0)
-
 struct Set {
     RcxTypedClasses cl;
     std::vector<u64> ufirst, from, bat;
@@ -44,29 +28,14 @@ struct Set {
     std::vector<u8> placed;
 };
 
-// every unit of every class, searched between its row's bounds, lies in its own entry
-bool units_found(const Set& s, int which, const char* name)
-{
-    for (u32 c = 0; c < RCX_TYPED_CLASSES; ++c) {
-        const u64 total = s.cl.ubase[c + 1] - s.cl.ubase[c];
-        for (u64 u = 0; u < total; ++u) {
-            const u64 g = s.cl.ubase[c] + u;
-            const u32 row = s.cl.row_first[c] + (u32)(u / RCX_TYPED_ROW);
-            const u32 k = rcx_typed_locate(s.ufirst.data(), s.rowtab.at(row), s.rowtab.at(row + 1), g);
-            CHECK(k >= s.cl.ent_first[c] && k < s.cl.ent_first[c + 1] && s.ufirst[k] <= g && g < s.ufirst[k + 1], "%s set: unit %llu of class %u found in entry %u",
-                  name, (unsigned long long)u, c, k);
-        }
-    }
-    return true;
-}
-
 bool run(const Batch& b, int which)
 {
     const u64 n = b.widths.size(), count = n, tiles = rcx_tpick_tiles(count);
     const u64 bytes_all = b.offs[n] - b.offs[0], src_cap = b.offs[n], base_cap = b.base_first + b.base_bytes;
     // classify
     std::vector<u32> keys(n, RCX_TPICK_NONE), bins(RCX_TPICK_BINS, 0);
-    std::vector<u64> tile_sum(tiles * RCX_BPICK_SUMS, 0);
+    constexpr u32 SUMS = RCX_BPICK_KEYS + 1u;
+    std::vector<u64> tile_sum(tiles * SUMS, 0);
     for (u64 k = 0; k < count; ++k) {
         const u64 len = b.offs[k + 1] - b.offs[k];
         if (len == 0) continue;
@@ -75,30 +44,23 @@ bool run(const Batch& b, int which)
         CHECK(bad == RCX_TPICK_OK, "entry %llu is refused with %u", (unsigned long long)k, bad);
         keys[k] = rcx_bpick_key((u32)len, w, pr, op);
         const u64 tile = k / RCX_TPICK_THREADS;
-        if (keys[k] < RCX_BPICK_KEYS) tile_sum.at(tile * RCX_BPICK_SUMS + keys[k]) += (1ull << RCX_TPICK_COUNT_SHIFT) | rcx_tpick_units((u32)len, w);
+        if (keys[k] < RCX_BPICK_KEYS) tile_sum.at(tile * SUMS + keys[k]) += sim_value(len, w);
         else bins.at(keys[k] - RCX_BPICK_KEYS) += 1;
-        tile_sum.at(tile * RCX_BPICK_SUMS + RCX_BPICK_KEYS) += len;
+        tile_sum.at(tile * SUMS + RCX_BPICK_KEYS) += len;
     }
     // top
-    std::vector<u64> tile_units(tiles * RCX_BPICK_KEYS, 0);
-    std::vector<u32> tile_ents(tiles * RCX_BPICK_KEYS, 0);
-    u64 totals[2 * RCX_BPICK_KEYS] = {}, bytes = 0;
-    for (u64 t = 0; t < tiles; ++t) {
-        for (u32 c = 0; c < RCX_BPICK_KEYS; ++c) {
-            const u64 v = tile_sum[t * RCX_BPICK_SUMS + c];
-            tile_ents[t * RCX_BPICK_KEYS + c] = (u32)totals[c];
-            tile_units[t * RCX_BPICK_KEYS + c] = totals[RCX_BPICK_KEYS + c];
-            totals[c] += v >> RCX_TPICK_COUNT_SHIFT;
-            totals[RCX_BPICK_KEYS + c] += v & ((1ull << RCX_TPICK_COUNT_SHIFT) - 1ull);
-        }
-        bytes += tile_sum[t * RCX_BPICK_SUMS + RCX_BPICK_KEYS];
-    }
+    std::vector<u64> tile_units;
+    std::vector<u32> tile_ents;
+    u64 totals[2 * RCX_BPICK_KEYS];
+    const u64 bytes = sim_top<RCX_BPICK_KEYS>(tile_sum, tile_ents, tile_units, totals);
     CHECK(bytes == bytes_all, "%llu bytes of %llu", (unsigned long long)bytes, (unsigned long long)bytes_all);
     Set set[2];
     memset(&set[0].cl, 0, sizeof(RcxTypedClasses));
     memset(&set[1].cl, 0, sizeof(RcxTypedClasses));
-    rcx_tpick_head(totals, totals + RCX_BPICK_KEYS, set[0].cl);
-    rcx_bpick_head(totals + RCX_BPICK_TYPED, totals + RCX_BPICK_KEYS + RCX_BPICK_TYPED, set[1].cl);
+    u64 of_class[2 * RCX_TYPED_CLASSES] = {}; // the typed set: key c = class 3 c
+    for (u32 c = 0; c < RCX_BPICK_TYPED; ++c) of_class[3 * c] = totals[c], of_class[RCX_TYPED_CLASSES + 3 * c] = totals[RCX_BPICK_KEYS + c];
+    rcx_class_head(of_class, of_class + RCX_TYPED_CLASSES, [](u32 w) { return rcx_base_items_rows(0u, w); }, set[0].cl);
+    rcx_class_head(totals + RCX_BPICK_TYPED, totals + RCX_BPICK_KEYS + RCX_BPICK_TYPED, [](u32 w) { return rcx_base_items_rows(1u, w); }, set[1].cl);
     for (Set& s : set) {
         const u32 nent = s.cl.ent_first[RCX_TYPED_CLASSES];
         s.ufirst.assign(nent + 1, ~0ull), s.from.assign(nent, 0), s.bat.assign(nent, 0), s.len.assign(nent, 0), s.placed.assign(nent, 0);
@@ -127,11 +89,11 @@ bool run(const Batch& b, int which)
                 const u64 place = (u64)s.cl.ent_first[c] + tile_ents[t * RCX_BPICK_KEYS + key] + (before[key] >> RCX_TPICK_COUNT_SHIFT);
                 CHECK(place < s.placed.size() && !s.placed[place], "entry %llu: place %llu", (unsigned long long)k, (unsigned long long)place);
                 s.placed[place] = 1;
-                s.ufirst[place] = s.cl.ubase[c] + tile_units[t * RCX_BPICK_KEYS + key] + (before[key] & ((1ull << RCX_TPICK_COUNT_SHIFT) - 1ull));
+                s.ufirst[place] = s.cl.ubase[c] + tile_units[t * RCX_BPICK_KEYS + key] + (before[key] & SIM_LOW);
                 s.from[place] = b.offs[k];
                 s.bat[place] = based ? b.boffs[k] : 0;
                 s.len[place] = len;
-                before[key] += (1ull << RCX_TPICK_COUNT_SHIFT) | rcx_tpick_units(len, w);
+                before[key] += sim_value(len, w);
             } else {
                 const u32 at = cursor.at(key - RCX_BPICK_KEYS)++;
                 CHECK(at < nscan, "entry %llu: scan place %u of %u", (unsigned long long)k, at, nscan);
@@ -140,13 +102,11 @@ bool run(const Batch& b, int which)
         }
     }
     // rows
-    const u64 bound[2] = {rcx_tpick_rows_most(bytes), rcx_bpick_rows_most(bytes)};
+    const u64 bound[2] = {rcx_class_rows_most(bytes, RCX_BPICK_TYPED), rcx_class_rows_most(bytes, RCX_TYPED_CLASSES)};
     for (u32 i = 0; i < 2; ++i) {
         Set& s = set[i];
-        const u32 rows = s.cl.row_first[RCX_TYPED_CLASSES];
-        CHECK(rows <= bound[i], "set %u: %u rows, bound %llu", i, rows, (unsigned long long)bound[i]);
-        s.rowtab.resize(rows);
-        for (u32 r = 0; r < rows; ++r) s.rowtab[r] = rcx_tpick_row(s.cl, s.ufirst.data(), r);
+        s.rowtab = sim_rows(s.cl, s.ufirst);
+        CHECK(s.rowtab.size() <= bound[i], "set %u: %llu rows, bound %llu", i, (unsigned long long)s.rowtab.size(), (unsigned long long)bound[i]);
         for (u8 p : s.placed) CHECK(p, "set %u: a place is empty", i);
     }
     // the host plan of the same items in the same order
@@ -172,7 +132,7 @@ bool run(const Batch& b, int which)
                          (unsigned long long)bt.bat[k]);
         }
         for (u64 r = 0; r < s.rowtab.size(); ++r) CHECK(t.rowtab[r] == s.rowtab[r], "set %u row %llu: entry %u, the host plan has %u", i, (unsigned long long)r, s.rowtab[r], t.rowtab[r]);
-        if (!units_found(s, which, i ? "base" : "typed")) return false;
+        if (!units_found(s.cl, s.ufirst, s.rowtab, which, i ? "base" : "typed")) return false;
     }
     // the scan list: the host plan's items, in work order (ascending bins = descending lengths)
     CHECK(nscan == tt.nscan, "%u scan entries, the host plan has %llu", nscan, (unsigned long long)tt.nscan);

@@ -1,5 +1,5 @@
 // typed_picks_san.cpp -- the planner's rules of cpprcoder_amd/csrc/rcx_typed_picks.hpp (rcx_tpick_validate, rcx_tpick_key,
-// rcx_tpick_units, rcx_tpick_bin, rcx_tpick_head, rcx_tpick_row: plain functions, the same text the kernels compile) in a
+// rcx_tpick_units, rcx_tpick_bin, and the class planner's rcx_class_head, rcx_class_row: plain functions, the same text the kernels compile) in a
 // program of its own, to be built with -fsanitize=address,undefined (tests/test_typed_picks_cpu.py does).  It reads batches of
 // entries and what typed_picks.plan_numpy says of them from a file, plans each batch in the planner's steps -- keys and tile
 // sums, the sums over the tiles and the head, the places, the rows -- and checks
@@ -10,38 +10,13 @@
 //                 rcx_typed_plan computes for the same entries; the scan list is in work order
 // The tables lie in heap blocks of exactly their size, so a step outside is an error of the sanitizer as well.
 // Test tooling, not part of librcx.so.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../cpprcoder_amd/csrc/rcx_typed_picks.hpp"
-
-uint64_t rcx_sim_counters[4];
+#include "picks_san.hpp"
 
 namespace
 {
 
-struct Batch {
-    u64 count = 0, max_bytes = 0, src_cap = 0, dst_cap = 0;
-    std::vector<u64> src_at, dst_at, len;
-    std::vector<u8> widths, preds;
-    int status = 0;
-    long long position = -1;
-    std::vector<int> route;
-    std::vector<long long> bins;
-};
-
-#define CHECK(cond, ...)                 \
-    do {                                 \
-        if (!(cond)) {                   \
-            printf("batch %d: ", which); \
-            printf(__VA_ARGS__);         \
-            printf("\n");                \
-            return false;                \
-        }                                \
-    } while (0)
-
-bool run(const Batch& b, int which)
+// (the model's columns: model0 = the entry's route, model1 = its bin)
+bool run(const TypedBatch& b, int which)
 {
     const u64 max_pick = b.len.size(), count = b.count < max_pick ? b.count : max_pick, tiles = rcx_tpick_tiles(count);
     u32 flags = 0;
@@ -65,32 +40,25 @@ bool run(const Batch& b, int which)
         }
         keys[k] = rcx_tpick_key((u32)len, w, pr);
         const u64 tile = k / RCX_TPICK_THREADS;
-        if (keys[k] < 4u) tile_sum.at(tile * 5 + keys[k]) += (1ull << RCX_TPICK_COUNT_SHIFT) | rcx_tpick_units((u32)len, w);
+        if (keys[k] < 4u) tile_sum.at(tile * 5 + keys[k]) += sim_value(len, w);
         else bins.at(keys[k] - 4u) += 1;
         tile_sum.at(tile * 5 + 4) += len;
     }
     // top: sums over the tiles, the head, the cursors
-    std::vector<u64> tile_units(tiles * 4, 0);
-    std::vector<u32> tile_ents(tiles * 4, 0);
-    u64 ents[4] = {}, units[4] = {}, bytes = 0;
-    for (u64 t = 0; t < tiles; ++t) {
-        for (u32 c = 0; c < 4; ++c) {
-            const u64 v = tile_sum[t * 5 + c];
-            tile_ents[t * 4 + c] = (u32)ents[c];
-            tile_units[t * 4 + c] = units[c];
-            ents[c] += v >> RCX_TPICK_COUNT_SHIFT;
-            units[c] += v & ((1ull << RCX_TPICK_COUNT_SHIFT) - 1ull);
-        }
-        bytes += tile_sum[t * 5 + 4];
-    }
+    std::vector<u64> tile_units;
+    std::vector<u32> tile_ents;
+    u64 totals[8];
+    const u64 bytes = sim_top<4>(tile_sum, tile_ents, tile_units, totals);
     const bool over = bytes > b.max_bytes;
     if (over) {
         flag(RCX_TPICK_CAPACITY, count);
-        for (u32 c = 0; c < 4; ++c) ents[c] = units[c] = 0;
+        for (u64& x : totals) x = 0;
     }
+    u64 of_class[2 * RCX_TYPED_CLASSES] = {}; // key c = class 3 c
+    for (u32 c = 0; c < 4; ++c) of_class[3 * c] = totals[c], of_class[RCX_TYPED_CLASSES + 3 * c] = totals[4 + c];
     RcxTypedClasses cl;
     memset(&cl, 0, sizeof(cl));
-    rcx_tpick_head(ents, units, cl);
+    rcx_class_head(of_class, of_class + RCX_TYPED_CLASSES, [](u32 w) { return RCX_PLANES_U4 / w; }, cl);
     const u32 nent = cl.ent_first[RCX_TYPED_CLASSES];
     std::vector<u32> cursor(RCX_TPICK_BINS, 0);
     u32 nscan = 0;
@@ -105,9 +73,9 @@ bool run(const Batch& b, int which)
     CHECK((flags ? (long long)first_bad : -1) == b.position, "position %lld, the model says %lld", flags ? (long long)first_bad : -1, b.position);
     for (u64 k = 0; k < max_pick; ++k) {
         const int route = over || keys[k] == RCX_TPICK_NONE ? 0 : keys[k] < 4u ? 1 : 2;
-        CHECK(route == b.route[k], "entry %llu: route %d, the model says %d", (unsigned long long)k, route, b.route[k]);
+        CHECK(route == b.model0[k], "entry %llu: route %d, the model says %lld", (unsigned long long)k, route, b.model0[k]);
         const long long bin = keys[k] != RCX_TPICK_NONE && keys[k] >= 4u ? (long long)keys[k] - 4 : -1;
-        CHECK(bin == b.bins[k], "entry %llu: bin %lld, the model says %lld", (unsigned long long)k, bin, b.bins[k]);
+        CHECK(bin == b.model1[k], "entry %llu: bin %lld, the model says %lld", (unsigned long long)k, bin, b.model1[k]);
     }
     if (over) {
         CHECK(nent == 0 && cl.step_end[RCX_TYPED_CLASSES - 1] == 0 && cl.rest_end[RCX_TYPED_CLASSES - 1] == 0, "an overflowing call has work");
@@ -127,10 +95,10 @@ bool run(const Batch& b, int which)
                 const u64 place = (u64)cl.ent_first[c] + tile_ents[t * 4 + key] + (before[key] >> RCX_TPICK_COUNT_SHIFT);
                 CHECK(place < nent && !placed[place], "entry %llu: place %llu", (unsigned long long)k, (unsigned long long)place);
                 placed[place] = 1;
-                ufirst[place] = cl.ubase[c] + tile_units[t * 4 + key] + (before[key] & ((1ull << RCX_TPICK_COUNT_SHIFT) - 1ull));
+                ufirst[place] = cl.ubase[c] + tile_units[t * 4 + key] + (before[key] & SIM_LOW);
                 len_of[place] = b.len[k];
                 width_of[place] = b.widths[k];
-                before[key] += (1ull << RCX_TPICK_COUNT_SHIFT) | rcx_tpick_units((u32)b.len[k], b.widths[k]);
+                before[key] += sim_value(b.len[k], b.widths[k]);
             } else {
                 const u32 s = cursor.at(key - 4u)++;
                 CHECK(s < nscan, "entry %llu: scan place %u of %u", (unsigned long long)k, s, nscan);
@@ -159,55 +127,15 @@ bool run(const Batch& b, int which)
         CHECK(memcmp(t.classes, &cl, sizeof(cl)) == 0, "the head is not the host plan's");
         CHECK(p.nent == nent && memcmp(t.ufirst, ufirst.data(), (nent + 1) * sizeof(u64)) == 0, "ufirst is not the host plan's");
         // the rows: every one as the host plan has it
-        const u32 rows = cl.row_first[RCX_TYPED_CLASSES];
-        CHECK(rows == p.nrows && rows <= rcx_tpick_rows_most(b.max_bytes), "%u rows, bound %llu", rows, (unsigned long long)rcx_tpick_rows_most(b.max_bytes));
-        std::vector<u32> rowtab(rows);
-        for (u32 r = 0; r < rows; ++r) rowtab[r] = rcx_tpick_row(cl, ufirst.data(), r);
+        const std::vector<u32> rowtab = sim_rows(cl, ufirst);
+        const u32 rows = (u32)rowtab.size();
+        CHECK(rows == p.nrows && rows <= rcx_class_rows_most(b.max_bytes, 4u), "%u rows, bound %llu", rows, (unsigned long long)rcx_class_rows_most(b.max_bytes, 4u));
         for (u32 r = 0; r < rows; ++r) CHECK(rowtab[r] == t.rowtab[r], "row %u: entry %u, the host plan has %u", r, rowtab[r], t.rowtab[r]);
-        // every unit, searched between its row's bounds as the kernels search, lies in its own entry
-        for (u32 c = 0; c < RCX_TYPED_CLASSES; ++c) {
-            const u64 total = cl.ubase[c + 1] - cl.ubase[c];
-            for (u64 u = 0; u < total; ++u) {
-                const u64 g = cl.ubase[c] + u;
-                const u32 row = cl.row_first[c] + (u32)(u / RCX_TYPED_ROW);
-                const u32 k = rcx_typed_locate(ufirst.data(), rowtab.at(row), rowtab.at(row + 1), g);
-                CHECK(k >= cl.ent_first[c] && k < cl.ent_first[c + 1] && ufirst[k] <= g && g < ufirst[k + 1], "unit %llu of class %u found in entry %u",
-                      (unsigned long long)u, c, k);
-            }
-        }
+        if (!units_found(cl, ufirst, rowtab, which, "typed")) return false;
     }
     return true;
 }
 
 } // namespace
 
-int main(int argc, char** argv)
-{
-    if (argc < 2) return 2;
-    FILE* f = fopen(argv[1], "r");
-    if (!f) return 2;
-    int nbatches = 0;
-    if (fscanf(f, "%d", &nbatches) != 1) return 2;
-    u64 entries = 0;
-    for (int i = 0; i < nbatches; ++i) {
-        Batch b;
-        unsigned long long n, count, max_bytes, src_cap, dst_cap;
-        if (fscanf(f, "%llu %llu %llu %llu %llu %d %lld", &n, &count, &max_bytes, &src_cap, &dst_cap, &b.status, &b.position) != 7) return 2;
-        b.count = count, b.max_bytes = max_bytes, b.src_cap = src_cap, b.dst_cap = dst_cap;
-        for (u64 k = 0; k < n; ++k) {
-            unsigned long long a, d, len;
-            unsigned w, p;
-            int route;
-            long long bin;
-            if (fscanf(f, "%llu %llu %llu %u %u %d %lld", &a, &d, &len, &w, &p, &route, &bin) != 7) return 2;
-            b.src_at.push_back(a), b.dst_at.push_back(d), b.len.push_back(len);
-            b.widths.push_back((u8)w), b.preds.push_back((u8)p);
-            b.route.push_back(route), b.bins.push_back(bin);
-        }
-        if (!run(b, i)) return 1;
-        entries += n;
-    }
-    fclose(f);
-    printf("typed_picks_san ok: %d batches, %llu entries\n", nbatches, (unsigned long long)entries);
-    return 0;
-}
+int main(int argc, char** argv) { return sim_typed_main<false>(argc, argv, "typed_picks_san", run); }

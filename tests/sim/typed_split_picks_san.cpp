@@ -1,5 +1,5 @@
 // typed_split_picks_san.cpp -- the planner's rules of cpprcoder_amd/csrc/rcx_typed_split_picks.hpp (rcx_tpick_validate,
-// rcx_typed_class, rcx_tpick_units, rcx_tpick_tiles, rcx_spick_head, rcx_tpick_row: plain functions, the same text the kernels
+// rcx_typed_class, rcx_tpick_units, rcx_tpick_tiles, and the class planner's rcx_class_head, rcx_class_row: plain functions, the same text the kernels
 // compile) in a program of its own, to be built with -fsanitize=address,undefined (tests/test_typed_split_picks_cpu.py does).
 // It reads batches of entries and what typed_split_picks.plan_numpy says of them from a file, plans each batch in the planner's
 // steps -- keys and tile sums, the sums over the tiles and the head, the places and kept, the rows -- and checks
@@ -10,41 +10,16 @@
 //                 rows are what rcx_typed_plan(..., scan = false) computes for the same entries in the placed order
 // The tables lie in heap blocks of exactly their size, so a step outside is an error of the sanitizer as well.
 // Test tooling, not part of librcx.so.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../cpprcoder_amd/csrc/rcx_typed_split_picks.hpp"
-
-uint64_t rcx_sim_counters[4];
+#include "picks_san.hpp"
 
 namespace
 {
 
-struct Batch {
-    u64 count = 0, max_bytes = 0, src_cap = 0, dst_cap = 0;
-    std::vector<u64> src_at, dst_at, len, kept;
-    std::vector<u8> widths, preds;
-    int status = 0;
-    long long position = -1;
-    std::vector<int> klass;
-    std::vector<long long> place;
-};
-
-#define CHECK(cond, ...)                 \
-    do {                                 \
-        if (!(cond)) {                   \
-            printf("batch %d: ", which); \
-            printf(__VA_ARGS__);         \
-            printf("\n");                \
-            return false;                \
-        }                                \
-    } while (0)
-
-bool run(const Batch& b, int which)
+// (the model's columns: model0 = the entry's class, model1 = its place, model2 = its kept)
+bool run(const TypedBatch& b, int which)
 {
-    constexpr u32 NC = RCX_SPICK_KEYS, NS = RCX_SPICK_SUMS;
-    constexpr u64 LOW = (1ull << RCX_TPICK_COUNT_SHIFT) - 1ull;
+    constexpr u32 NC = RCX_SPICK_KEYS, NS = NC + 1u;
+    constexpr u64 LOW = SIM_LOW;
     const u64 max_pick = b.len.size(), count = b.count < max_pick ? b.count : max_pick, tiles = rcx_tpick_tiles(count);
     u32 flags = 0;
     u64 first_bad = ~0ull;
@@ -68,31 +43,22 @@ bool run(const Batch& b, int which)
         keys[k] = rcx_typed_class(w, pr);
         CHECK(keys[k] < NC, "entry %llu: class %u", (unsigned long long)k, keys[k]);
         const u64 tile = k / RCX_TPICK_THREADS;
-        tile_sum.at(tile * NS + keys[k]) += (1ull << RCX_TPICK_COUNT_SHIFT) | rcx_tpick_units((u32)len, w);
+        tile_sum.at(tile * NS + keys[k]) += sim_value(len, w);
         tile_sum.at(tile * NS + NC) += len;
     }
     // top: sums over the tiles, the head
-    std::vector<u64> tile_units(tiles * NC, 0);
-    std::vector<u32> tile_ents(tiles * NC, 0);
-    u64 ents[NC] = {}, units[NC] = {}, bytes = 0;
-    for (u64 t = 0; t < tiles; ++t) {
-        for (u32 c = 0; c < NC; ++c) {
-            const u64 v = tile_sum[t * NS + c];
-            tile_ents[t * NC + c] = (u32)ents[c];
-            tile_units[t * NC + c] = units[c];
-            ents[c] += v >> RCX_TPICK_COUNT_SHIFT;
-            units[c] += v & LOW;
-        }
-        bytes += tile_sum[t * NS + NC];
-    }
+    std::vector<u64> tile_units;
+    std::vector<u32> tile_ents;
+    u64 totals[2 * NC];
+    const u64 bytes = sim_top<NC>(tile_sum, tile_ents, tile_units, totals);
     const bool over = bytes > b.max_bytes;
     if (over) {
         flag(RCX_TPICK_CAPACITY, count);
-        for (u32 c = 0; c < NC; ++c) ents[c] = units[c] = 0;
+        for (u64& x : totals) x = 0;
     }
     RcxTypedClasses cl;
     memset(&cl, 0, sizeof(cl));
-    rcx_spick_head(ents, units, cl);
+    rcx_class_head(totals, totals + NC, [](u32 w) { return RCX_PLANES_U4 / w; }, cl);
     const u32 nent = cl.ent_first[RCX_TYPED_CLASSES];
     // the model's status and classes
     const int status = (flags & RCX_TPICK_CORRUPT) ? 2 : (flags & RCX_TPICK_CAPACITY) ? 1 : 0; // as the file has it: corrupt, capacity, ok
@@ -100,7 +66,7 @@ bool run(const Batch& b, int which)
     CHECK((flags ? (long long)first_bad : -1) == b.position, "position %lld, the model says %lld", flags ? (long long)first_bad : -1, b.position);
     for (u64 k = 0; k < max_pick; ++k) {
         const int klass = keys[k] == RCX_TPICK_NONE ? -1 : (int)keys[k];
-        CHECK(klass == b.klass[k], "entry %llu: class %d, the model says %d", (unsigned long long)k, klass, b.klass[k]);
+        CHECK(klass == b.model0[k], "entry %llu: class %d, the model says %lld", (unsigned long long)k, klass, b.model0[k]);
     }
     // apply: the places and kept, for every entry of the tables
     std::vector<u64> ufirst(nent + 1, ~0ull), len_of(nent, 0), kept(max_pick, ~0ull);
@@ -124,13 +90,13 @@ bool run(const Batch& b, int which)
             pred_of[place] = b.preds[k];
             place_of[k] = (long long)place;
             kept[k] = b.len[k];
-            before[key] += (1ull << RCX_TPICK_COUNT_SHIFT) | rcx_tpick_units((u32)b.len[k], b.widths[k]);
+            before[key] += sim_value(b.len[k], b.widths[k]);
         }
     }
     ufirst[nent] = cl.ubase[RCX_TYPED_CLASSES];
     for (u64 k = 0; k < max_pick; ++k) {
-        CHECK(place_of[k] == b.place[k], "entry %llu: place %lld, the model says %lld", (unsigned long long)k, place_of[k], b.place[k]);
-        CHECK(kept[k] == b.kept[k], "entry %llu: kept %llu, the model says %llu", (unsigned long long)k, (unsigned long long)kept[k], (unsigned long long)b.kept[k]);
+        CHECK(place_of[k] == b.model1[k], "entry %llu: place %lld, the model says %lld", (unsigned long long)k, place_of[k], b.model1[k]);
+        CHECK(kept[k] == b.model2[k], "entry %llu: kept %llu, the model says %llu", (unsigned long long)k, (unsigned long long)kept[k], (unsigned long long)b.model2[k]);
     }
     if (over) {
         CHECK(nent == 0 && cl.step_end[RCX_TYPED_CLASSES - 1] == 0 && cl.rest_end[RCX_TYPED_CLASSES - 1] == 0, "an overflowing call has work");
@@ -154,55 +120,16 @@ bool run(const Batch& b, int which)
         CHECK(memcmp(t.classes, &cl, sizeof(cl)) == 0, "the head is not the host plan's");
         CHECK(p.nent == nent && p.nscan == 0 && memcmp(t.ufirst, ufirst.data(), (nent + 1) * sizeof(u64)) == 0, "ufirst is not the host plan's");
         for (u32 k = 0; k < nent; ++k) CHECK(t.len[k] == len_of[k], "place %u: %llu bytes, the host plan has %u", k, (unsigned long long)len_of[k], t.len[k]);
-        const u32 rows = cl.row_first[RCX_TYPED_CLASSES];
-        CHECK(rows == p.nrows && rows <= rcx_spick_rows_most(b.max_bytes), "%u rows, bound %llu", rows, (unsigned long long)rcx_spick_rows_most(b.max_bytes));
-        std::vector<u32> rowtab(rows);
-        for (u32 r = 0; r < rows; ++r) rowtab[r] = rcx_tpick_row(cl, ufirst.data(), r);
+        const std::vector<u32> rowtab = sim_rows(cl, ufirst);
+        const u32 rows = (u32)rowtab.size();
+        const u64 bound = rcx_class_rows_most(b.max_bytes, RCX_TYPED_CLASSES);
+        CHECK(rows == p.nrows && rows <= bound, "%u rows, bound %llu", rows, (unsigned long long)bound);
         for (u32 r = 0; r < rows; ++r) CHECK(rowtab[r] == t.rowtab[r], "row %u: entry %u, the host plan has %u", r, rowtab[r], t.rowtab[r]);
-        // every unit, searched between its row's bounds as the kernels search, lies in its own entry
-        for (u32 c = 0; c < RCX_TYPED_CLASSES; ++c) {
-            const u64 total = cl.ubase[c + 1] - cl.ubase[c];
-            for (u64 u = 0; u < total; ++u) {
-                const u64 g = cl.ubase[c] + u;
-                const u32 row = cl.row_first[c] + (u32)(u / RCX_TYPED_ROW);
-                const u32 k = rcx_typed_locate(ufirst.data(), rowtab.at(row), rowtab.at(row + 1), g);
-                CHECK(k >= cl.ent_first[c] && k < cl.ent_first[c + 1] && ufirst[k] <= g && g < ufirst[k + 1], "unit %llu of class %u found in entry %u",
-                      (unsigned long long)u, c, k);
-            }
-        }
+        if (!units_found(cl, ufirst, rowtab, which, "typed")) return false;
     }
     return true;
 }
 
 } // namespace
 
-int main(int argc, char** argv)
-{
-    if (argc < 2) return 2;
-    FILE* f = fopen(argv[1], "r");
-    if (!f) return 2;
-    int nbatches = 0;
-    if (fscanf(f, "%d", &nbatches) != 1) return 2;
-    u64 entries = 0;
-    for (int i = 0; i < nbatches; ++i) {
-        Batch b;
-        unsigned long long n, count, max_bytes, src_cap, dst_cap;
-        if (fscanf(f, "%llu %llu %llu %llu %llu %d %lld", &n, &count, &max_bytes, &src_cap, &dst_cap, &b.status, &b.position) != 7) return 2;
-        b.count = count, b.max_bytes = max_bytes, b.src_cap = src_cap, b.dst_cap = dst_cap;
-        for (u64 k = 0; k < n; ++k) {
-            unsigned long long a, d, len, kept;
-            unsigned w, p;
-            int klass;
-            long long place;
-            if (fscanf(f, "%llu %llu %llu %u %u %d %lld %llu", &a, &d, &len, &w, &p, &klass, &place, &kept) != 8) return 2;
-            b.src_at.push_back(a), b.dst_at.push_back(d), b.len.push_back(len), b.kept.push_back(kept);
-            b.widths.push_back((u8)w), b.preds.push_back((u8)p);
-            b.klass.push_back(klass), b.place.push_back(place);
-        }
-        if (!run(b, i)) return 1;
-        entries += n;
-    }
-    fclose(f);
-    printf("typed_split_picks_san ok: %d batches, %llu entries\n", nbatches, (unsigned long long)entries);
-    return 0;
-}
+int main(int argc, char** argv) { return sim_typed_main<true>(argc, argv, "typed_split_picks_san", run); }

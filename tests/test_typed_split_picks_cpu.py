@@ -196,10 +196,18 @@ def test_the_header_and_the_library():
     assert all(h in build.HEADERS for h in ("rcx_typed_split_picks.hpp", "rcx_typed_split_picks_api.hpp"))
     assert any(h.endswith("rcx_typed_split_picks.h") for h in build.HEADERS)
     assert (tsp.PLAN_THREADS, tsp.PLAN_GRID, tsp.PLAN_TOP) == (typed_picks.PLAN_THREADS, typed_picks.PLAN_GRID, typed_picks.PLAN_TOP) == (256, 512, 1024)
-    source = open(os.path.join(ROOT, "cpprcoder_amd", "csrc", "rcx_typed_split_picks.hpp")).read()
+    csrc = os.path.join(ROOT, "cpprcoder_amd", "csrc")
+    source = open(os.path.join(csrc, "rcx_typed_split_picks.hpp")).read()
     assert "rcx_tpick_validate(" in source and "RCX_HD u32 rcx_tpick_validate" not in source  # the rule is reused, not copied
-    api = open(os.path.join(ROOT, "cpprcoder_amd", "csrc", "rcx_typed_split_picks_api.hpp")).read()
-    assert "hipMemsetAsync" not in api and "rcx_tpick_clear_k" not in api  # kernel nodes alone, and no clear launch
+    every = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip")))
+    for rule in ("u32 rcx_tpick_validate(", "void rcx_class_head(", "u32 rcx_len_bin("):  # one definition of each in csrc/
+        assert every.count(rule) == 1, rule
+    assert "_head(const u64*" not in every.replace("rcx_class_head(const u64*", "")  # and no second head under another name
+    api = open(os.path.join(csrc, "rcx_typed_split_picks_api.hpp")).read()
+    assert "hipMemset" not in api and "_clear_k" not in api  # kernel nodes alone, and no clear launch of its own;
+    assert re.search(r"SCAN = false\b", source)  # the shared launches clear for a policy with a scan list only, and the split has none
+    shared = open(os.path.join(csrc, "rcx_typed_picks_api.hpp")).read()
+    assert shared.count("_clear_k") == 1 and "if (P::SCAN) hipLaunchKernelGGL(rcx_class_clear_k" in shared and "hipMemset" not in shared
     assert hasattr(container, "pack_typed_items_device") and container.PackedTypedItems is tsp.PackedTypedItems
     assert issubclass(tsp.PackedTypedItems, container.OpenTypedItems) and "_expand" not in vars(tsp.PackedTypedItems)
 

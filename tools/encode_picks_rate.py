@@ -18,9 +18,7 @@ context of its own), never this tree's.
      spread over the launch (not built): the rows say what a call costs as it is.
   D  A's workload: a captured graph's replay against the eager call, wall and GPU time.
 """
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -32,7 +30,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from cpprcoder_amd import encode_picks as ep, rcx, workloads  # noqa: E402
-from picks_rate import CODER_NAMES, alternated, dev64, spread  # noqa: E402
+from picks_rate import CODER_NAMES, alternated, dev64, opened, spread  # noqa: E402
 
 
 class Baseline:
@@ -183,24 +181,7 @@ def part_d(w, args, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r23_encode_picks_rate.jsonl"))
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--parts", default="A,B,C,D")
-    ap.add_argument("--baseline-library", required=True, help="the librcx.so of the parent commit: the host-planned call is its")
-    args = ap.parse_args()
-    args.parts = args.parts.split(",")
-    if args.repeats < 5:
-        ap.error("at least 5 passes")
-    rows = []
-
-    def emit(row):
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-        with open(args.out, "w") as f:  # (kept up to date: a run that is cut short leaves what it measured)
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-
+    args, emit, rows = opened("r23_encode_picks_rate.jsonl")
     base = Baseline(args.baseline_library)
     if {"A", "C", "D"} & set(args.parts):
         w = SmallItems(base)

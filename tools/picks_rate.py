@@ -44,9 +44,15 @@ def spread(ms):
     return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4), "passes": len(ms)}
 
 
-def alternated(fns, repeats, warmup=2, after=None):
+def dev8(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint8))).cuda()
+
+
+def alternated(fns, repeats, warmup=2, after=None, before=None):
     """Several calls measured in turn -> {name: {"gpu_ms": [...], "wall_ms": [...], "after": [...]}}: device events around the
-    call, and the host clock from the call to the return of a device synchronise; after(name) is called behind each."""
+    call, and the host clock from the call to the return of a device synchronise; before(name) runs in front of the first
+    event (what it enqueues is outside the events and keeps the device busy while the call's host side runs), after(name) is
+    called behind each."""
     for _ in range(warmup):
         for k, fn in fns.items():
             fn()
@@ -58,6 +64,8 @@ def alternated(fns, repeats, warmup=2, after=None):
         for k, fn in fns.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
+            if before:
+                before(k)
             t0 = time.perf_counter()
             a.record()
             fn()
@@ -68,6 +76,40 @@ def alternated(fns, repeats, warmup=2, after=None):
             if after:
                 out[k]["after"].append(after(k))
     return out
+
+
+def opened(out_name, baseline_required=True):
+    """The command line of a *_picks_rate tool -> (args, emit, rows): emit(row) prints the row and rewrites args.out with every
+    row so far (a run that is cut short leaves what it had)."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", out_name))
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--parts", default="A,B,C,D")
+    ap.add_argument("--baseline-library", required=baseline_required, help="a librcx.so of the parent commit: the host-planned side")
+    ap.add_argument("--build-note", default=None, help="goes into every row as `build`: which build of the library a run measured")
+    args = ap.parse_args()
+    args.parts = args.parts.split(",")
+    if args.repeats < 5:
+        ap.error("at least 5 passes")
+    rows = []
+
+    def emit(row):
+        if args.build_note:
+            row["build"] = args.build_note
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+    return args, emit, rows
+
+
+def marks_missed(rows):
+    failed = [r for r in rows if r.get("pass") is False]
+    if failed:
+        print(f"{len(failed)} pass mark(s) missed", file=sys.stderr)
+        raise SystemExit(1)
 
 
 class Baseline:
@@ -206,21 +248,7 @@ def part_d(w, args, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_picks_rate.jsonl"))
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--parts", default="A,B,C,D")
-    ap.add_argument("--baseline-library", default=None, help="a librcx.so of the parent commit for the host-planned call of part A")
-    args = ap.parse_args()
-    args.parts = args.parts.split(",")
-    if args.repeats < 5:
-        ap.error("at least 5 passes")
-    rows = []
-
-    def emit(row):
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-
+    args, emit, rows = opened("r10_picks_rate.jsonl", baseline_required=False)
     base = Baseline(args.baseline_library) if args.baseline_library else None
     if {"A", "C", "D"} & set(args.parts):
         w = SmallItems()
@@ -234,13 +262,7 @@ def main():
         del w
     if "B" in args.parts:
         part_b(args, emit, None)
-    with open(args.out, "w") as f:
-        for row in rows:
-            f.write(json.dumps(row) + "\n")
-    failed = [r for r in rows if r.get("pass") is False]
-    if failed:
-        print(f"{len(failed)} pass mark(s) missed", file=sys.stderr)
-        raise SystemExit(1)
+    marks_missed(rows)
 
 
 if __name__ == "__main__":

@@ -21,13 +21,9 @@ section 21 quotes profiles/r20_typed_picks_rate.jsonl.
 
 --baseline-library: a librcx.so of the parent commit: the host-planned side of parts A and B is that library, never this build.
 """
-import argparse
 import ctypes as C
-import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,69 +32,31 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from cpprcoder_amd import container, predict, rcx, typed_items, typed_picks, workloads  # noqa: E402
+from picks_rate import alternated, dev8, dev64, marks_missed, opened, spread  # noqa: E402,F401  (the method is that tool's)
 
 WIDTHS = (2, 4, 8)
 BLOCK = 65536
 
 
-def dev64(a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint64)).view(np.int64)).cuda()
-
-
-def dev8(a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint8))).cuda()
-
-
-def spread(ms):
-    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4), "passes": len(ms)}
-
-
-def alternated(fns, repeats, warmup=2, after=None, before=None):
-    """Several calls measured in turn -> {name: {"gpu_ms": [...], "wall_ms": [...], "after": [...]}}: device events around the
-    call, and the host clock from the call to the return of a device synchronise; before(name) runs in front of the first
-    event (what it enqueues is outside the events and keeps the device busy while the call's host side runs), after(name) is
-    called behind each."""
-    for _ in range(warmup):
-        for k, fn in fns.items():
-            fn()
-            torch.cuda.synchronize()
-            if after:
-                after(k)
-    out = {k: {"gpu_ms": [], "wall_ms": [], "after": []} for k in fns}
-    for _ in range(repeats):
-        for k, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            if before:
-                before(k)
-            t0 = time.perf_counter()
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out[k]["wall_ms"].append((time.perf_counter() - t0) * 1e3)
-            out[k]["gpu_ms"].append(a.elapsed_time(b))
-            if after:
-                out[k]["after"].append(after(k))
-    return out
-
-
 class Baseline:
-    """rcx_typed_items_join_device of another build of the library (plain ctypes), on a context of its own."""
+    """rcx_typed_items_join_device (or the call `name` of its signature) of another build of the library (plain ctypes), on a
+    context of its own."""
 
-    def __init__(self, path):
+    def __init__(self, path, name="rcx_typed_items_join_device"):
         self.L = C.CDLL(path)
         vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int
         self.L.rcx_ctx_create.argtypes = [i32, C.POINTER(vp)]
-        self.L.rcx_typed_items_join_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
+        self.fn = getattr(self.L, name)
+        self.fn.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
         self.L.rcx_ctx_destroy.argtypes = [vp]
         self.h = vp()
         assert self.L.rcx_ctx_create(0, C.byref(self.h)) == 0
 
     def join(self, src, offs, widths, preds, dst):
-        st = self.L.rcx_typed_items_join_device(self.h, src.data_ptr(), offs.ctypes.data, widths.ctypes.data, preds.ctypes.data, len(widths), dst.data_ptr(),
-                                                torch.cuda.current_stream().cuda_stream)
+        st = self.fn(self.h, src.data_ptr(), offs.ctypes.data, widths.ctypes.data, preds.ctypes.data, len(widths), dst.data_ptr(), torch.cuda.current_stream().cuda_stream)
         assert st == 0
+
+    split = join  # (typed_split_picks_rate.py: the same call with the split's name)
 
 
 class Ragged:
@@ -238,27 +196,7 @@ def part_d(w, args, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20_typed_picks_rate.jsonl"))
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--parts", default="A,B,C,D")
-    ap.add_argument("--baseline-library", required=True, help="a librcx.so of the parent commit: the host-planned side")
-    ap.add_argument("--build-note", default=None, help="goes into every row as `build`: which build of the library a run measured")
-    args = ap.parse_args()
-    args.parts = args.parts.split(",")
-    if args.repeats < 5:
-        ap.error("at least 5 passes")
-    rows = []
-
-    def emit(row):
-        if args.build_note:
-            row["build"] = args.build_note
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-        with open(args.out, "w") as f:  # (kept up to date: a run that is cut short leaves what it had)
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-
+    args, emit, rows = opened("r20_typed_picks_rate.jsonl")
     base = Baseline(args.baseline_library)
     ctx = rcx.Context(0)
     if {"A", "C", "D"} & set(args.parts):
@@ -273,10 +211,7 @@ def main():
     if "B" in args.parts:
         part_b(ctx, args, emit, base)
     ctx.close()
-    failed = [r for r in rows if r.get("pass") is False]
-    if failed:
-        print(f"{len(failed)} pass mark(s) missed", file=sys.stderr)
-        raise SystemExit(1)
+    marks_missed(rows)
 
 
 if __name__ == "__main__":

@@ -21,9 +21,6 @@ section 24 quotes profiles/r24_typed_split_picks_rate.jsonl.
 
 --baseline-library: a librcx.so of the parent commit: the host-planned side of parts A and B is that library, never this build.
 """
-import argparse
-import ctypes as C
-import json
 import os
 import sys
 
@@ -36,46 +33,15 @@ import torch  # noqa: E402
 
 from cpprcoder_amd import container, encode_picks, picks, predict, rcx, typed_items, typed_picks, workloads  # noqa: E402
 from cpprcoder_amd import typed_split_picks as tsp  # noqa: E402
-from typed_picks_rate import BLOCK, WIDTHS, alternated, dev8, dev64, spread  # noqa: E402  (the method is that tool's)
+import typed_picks_rate  # noqa: E402
+from typed_picks_rate import BLOCK, WIDTHS, Baseline, alternated, dev8, dev64, marks_missed, opened, spread  # noqa: E402,F401  (the method is that tool's)
 
 
-class Baseline:
-    """rcx_typed_items_split_device of another build of the library (plain ctypes), on a context of its own."""
-
-    def __init__(self, path):
-        self.L = C.CDLL(path)
-        vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int
-        self.L.rcx_ctx_create.argtypes = [i32, C.POINTER(vp)]
-        self.L.rcx_typed_items_split_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
-        self.L.rcx_ctx_destroy.argtypes = [vp]
-        self.h = vp()
-        assert self.L.rcx_ctx_create(0, C.byref(self.h)) == 0
-
-    def split(self, src, offs, widths, preds, dst):
-        st = self.L.rcx_typed_items_split_device(self.h, src.data_ptr(), offs.ctypes.data, widths.ctypes.data, preds.ctypes.data, len(widths), dst.data_ptr(),
-                                                 torch.cuda.current_stream().cuda_stream)
-        assert st == 0
-
-
-class Ragged:
-    """Part A's batch: 200 000 items, and their split text by the host-planned call of this build."""
+class Ragged(typed_picks_rate.Ragged):
+    """Part A's batch: that tool's 200 000 items and their split text by the host-planned call of this build."""
 
     def __init__(self, ctx, count=200_000):
-        rs = np.random.RandomState(13)
-        self.count = count
-        self.lengths = rs.randint(0, 4097, count).astype(np.uint64)
-        self.widths = np.array(WIDTHS, np.uint8)[rs.randint(0, 3, count)]
-        self.preds = rs.randint(0, 3, count).astype(np.uint8)
-        self.offs = rcx.item_offsets(self.lengths)
-        self.total = int(self.offs[-1])
-        self.ctx = ctx
-        self.items = torch.from_numpy(workloads.uniform(self.total, 12345)).cuda()
-        self.split = torch.zeros_like(self.items)
-        self.out = torch.zeros_like(self.items)
-        typed_items.split_device(ctx, self.items, self.offs, self.widths, self.preds, self.split)
-        ctx.sync_status()
-        self.d_at, self.d_len = dev64(self.offs[:-1]), dev64(self.lengths)
-        self.d_w, self.d_p, self.d_count = dev8(self.widths), dev8(self.preds), dev64([count])
+        super().__init__(ctx, count)
         self.d_kept = torch.zeros(count, dtype=torch.int64, device="cuda")
         tsp.reserve(ctx, count, self.total)
 
@@ -202,28 +168,8 @@ def part_d(w, args, emit, count=20_000):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r24_typed_split_picks_rate.jsonl"))
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--parts", default="A,B,C,D")
-    ap.add_argument("--baseline-library", required=True, help="a librcx.so of the parent commit: the host-planned side")
-    ap.add_argument("--build-note", default=None, help="goes into every row as `build`: which build of the library a run measured")
-    args = ap.parse_args()
-    args.parts = args.parts.split(",")
-    if args.repeats < 5:
-        ap.error("at least 5 passes")
-    rows = []
-
-    def emit(row):
-        if args.build_note:
-            row["build"] = args.build_note
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-        with open(args.out, "w") as f:  # (kept up to date: a run that is cut short leaves what it had)
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-
-    base = Baseline(args.baseline_library)
+    args, emit, rows = opened("r24_typed_split_picks_rate.jsonl")
+    base = Baseline(args.baseline_library, "rcx_typed_items_split_device")
     ctx = rcx.Context(0)
     if {"A", "C", "D"} & set(args.parts):
         w = Ragged(ctx)
@@ -237,10 +183,7 @@ def main():
     if "B" in args.parts:
         part_b(ctx, args, emit, base)
     ctx.close()
-    failed = [r for r in rows if r.get("pass") is False]
-    if failed:
-        print(f"{len(failed)} pass mark(s) missed", file=sys.stderr)
-        raise SystemExit(1)
+    marks_missed(rows)
 
 
 if __name__ == "__main__":
